@@ -7,7 +7,12 @@ per-beam ray-cast + Gaussian log-likelihood) -> weight normalisation -> systemat
 (SURVEY.md 8(d)), all inputs resident in HBM except the per-ping 512 ranges (2 KiB).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--map mesh|grid|mesh-general|mesh-tin]
-                    [--particles P] [--scaling weak|strong] [--total-particles T]
+                    [--particles P] [--scaling weak|strong] [--total-particles T] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps (`ms_per_step` = their wall clock / K, `value` the
+steps/s that gives), writes the last step's outputs if --dump-outputs is given, and prints the JSON line.  Everything
+else -- the timed block repeated to >= 200 steps (median / p95), per-phase HIP events and the roofline, the CPU baseline,
+the RMSE against the oracle, the extra workload legs -- runs with --full.
 
 N > 1: one rank per GPU over RCCL.  Either an external launcher provides RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* (python -m torch.distributed.run ... bench.py --gpus N), or -- when WORLD_SIZE is
@@ -57,8 +62,15 @@ def parse(argv=None):
     ap.add_argument('--beams', type=int, default=512)
     ap.add_argument('--map', default='mesh', choices=['grid', 'mesh', 'mesh-general', 'mesh-adjacency', 'mesh-tin', 'mesh-tin-shuffled', 'mesh-soup'])
     ap.add_argument('--mesh-general', action='store_true', help='same as --map mesh-general')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the extra workload legs (N = 1 runs them by default)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the timed block repeated to >= %d steps (median / p95), per-phase '
+                         'HIP events and roofline, cloud statistics, the exchange report (N > 1), and at N = 1 the CPU '
+                         'baseline, RMSE against the oracle and the extra workload legs' % MIN_TIMED_STEPS)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (mean / cov, the mean poses of the timed '
+                         'steps, a fixed sample of the particles, weights and ancestor indices) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip the extra workload legs (N = 1 runs them by default)')
     ap.add_argument('--only-main', action='store_true', help='same as --no-extra --no-cpu-baseline (profiling runs)')
     ap.add_argument('--cpu-particles', type=int, default=0, help='oracle sample size (0 = auto)')
     ap.add_argument('--rmse-particles', type=int, default=1048576,
@@ -603,6 +615,31 @@ def setup_comm(e, engine, dist, rank, world, want_overlap):
     sys.exit(3)
 
 
+DUMP_SAMPLE = 262144   # particles --dump-outputs writes of a larger shard (a fixed, seeded sample)
+
+
+def dump_outputs(d, e, rank, n_hist):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step, as DIR/<name>.npy (float64) --
+    the step's mean pose, mean yaw and covariance (mcl_last_mean_cov), the mean poses of the last n_hist steps
+    (mcl_mean_history), and for a fixed, seeded sample of at most DUMP_SAMPLE particles of this shard their states,
+    weights and ancestor indices (about 19 MB in all at 1 M particles).  Every rank makes the same calls (after a sharded
+    step some of them are collective); rank 0 writes."""
+    import numpy as np
+    mean6, yaw, cov9 = e.last_mean_cov()
+    hist = e.mean_history(n_hist)
+    soa, w = e.get_particles(weights=True)
+    idx = e.last_indices()
+    n = soa.shape[1]
+    pick = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.RandomState(12345).choice(n, DUMP_SAMPLE, replace=False))
+    if rank != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    arrays = {'mean6': mean6, 'yaw_mean': [yaw], 'cov9': cov9, 'mean_history': hist,
+              'particle_ids': pick, 'particles': soa[:, pick], 'weights': w[pick], 'ancestor_indices': idx[pick]}
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def worker(a, rank, world, local_rank):
     import numpy as np
     dist = None
@@ -622,9 +659,12 @@ def worker(a, rank, world, local_rank):
         sys.stderr.write('bench: --total-particles must be a multiple of the rank count\n')
         sys.exit(2)
     m = build_map(a.map)
-    nblocks = max(1, int(math.ceil(MIN_TIMED_STEPS / float(a.steps))))
-    nblocks = min(nblocks, max(1, (4000 - a.warmup) // a.steps - 1))  # mcl_mean_history keeps 4096 results
-    total_steps = a.warmup + a.steps * (nblocks + 1)   # (+ one block at the end that carries the per-phase events)
+    if a.full:
+        nblocks = max(1, int(math.ceil(MIN_TIMED_STEPS / float(a.steps))))
+        nblocks = min(nblocks, max(1, (4000 - a.warmup) // a.steps - 1))  # mcl_mean_history keeps 4096 results
+        total_steps = a.warmup + a.steps * (nblocks + 1)   # (+ one block at the end that carries the per-phase events)
+    else:
+        nblocks, total_steps = 1, a.warmup + a.steps   # a plain run: the warm-up and the --steps timed steps, nothing else
     stream = synth.odom_stream(total_steps)
     ba = synth.beam_angles(B)
 
@@ -666,8 +706,11 @@ def worker(a, rank, world, local_rank):
     run(a.warmup, a.warmup + a.steps)
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
-    # ---- the same block repeated until >= MIN_TIMED_STEPS steps are timed: median and p95 per block
-    block_ms = [1e3 * dt / a.steps]
+    ms_per_step = 1e3 * dt / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, e, rank, min(a.steps, 4096))
+    # ---- --full: the same block repeated until >= MIN_TIMED_STEPS steps are timed: median and p95 per block
+    block_ms = [ms_per_step]
     for b in range(1, nblocks):
         k0 = a.warmup + b * a.steps
         t0 = time.perf_counter()
@@ -678,34 +721,55 @@ def worker(a, rank, world, local_rank):
     # region, so they stay out of every timed block; at the end of the run the filter is in its steady state, like
     # the median block and like the rocprofv3 average the roofline is checked against -- the first steps after the
     # warm-up still work on a wider cloud and a sweep launch takes 15 % longer there)
-    e.timing_enable(True)
-    k0 = a.warmup + nblocks * a.steps
-    run(k0, k0 + a.steps)
-    barrier()
-    tim = e.timing_get()
-    # every rank's share of the resample exchange (states sent to peers, lost slots), so that the first multi-GPU run
-    # explains itself: which rank fed which, and how far the traffic is from the (world - 1) / world worst case
-    ex_all = None
-    if world > 1 and dist is not None:
-        s_, l_ = e.exchange_stats()
-        tl = [torch.zeros(2, dtype=torch.float64) for _ in range(world)]
-        dist.all_gather(tl, torch.tensor([float(s_), float(l_)], dtype=torch.float64))
-        ex_all = [(float(x[0]), float(x[1])) for x in tl]
-    e.timing_enable(False)
+    tim, ex_all = None, None
+    if a.full:
+        e.timing_enable(True)
+        k0 = a.warmup + nblocks * a.steps
+        run(k0, k0 + a.steps)
+        barrier()
+        tim = e.timing_get()
+        # every rank's share of the resample exchange (states sent to peers, lost slots), so that the first multi-GPU run
+        # explains itself: which rank fed which, and how far the traffic is from the (world - 1) / world worst case
+        if world > 1 and dist is not None:
+            s_, l_ = e.exchange_stats()
+            tl = [torch.zeros(2, dtype=torch.float64) for _ in range(world)]
+            dist.all_gather(tl, torch.tensor([float(s_), float(l_)], dtype=torch.float64))
+            ex_all = [(float(x[0]), float(x[1])) for x in tl]
+        e.timing_enable(False)
     # pose RMSE of the filter's mean (x, y) against the synthetic ground truth over every timed step
-    n_timed = min(a.steps * (nblocks + 1), 4096)   # (the library keeps the last 4 096 results: mcl_mean_history)
+    n_timed = min(a.steps * (nblocks + 1 if a.full else 1), 4096)   # (the library keeps the last 4 096 results: mcl_mean_history)
     hist = e.mean_history(n_timed)
     truth = stream['truth'][total_steps - n_timed:total_steps]
     pose_rmse = float(np.sqrt(np.mean((hist[:, 0] - truth[:, 0]) ** 2 + (hist[:, 1] - truth[:, 1]) ** 2)))
 
     out = None
     if rank == 0:
-        first_block_ms = 1e3 * dt / a.steps
-        ms_per_step = pctl(block_ms, 50)   # the median block (the first block still holds the clock ramp)
-        n_timed = a.steps * nblocks
         total_particles = P * world
-        path_main = mbes_path(e, P)
         value = 1e3 / ms_per_step * (total_particles / 1048576.0)
+        out = {
+            'metric': METRIC,
+            'value': round(value, 3), 'unit': 'steps/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
+            'ms_per_step': round(ms_per_step, 4),
+            'value_definition': 'steps/s (x total particles / 2^20) of the timed block: exactly --steps steps right after the '
+                                '--warmup steps, between barrier + synchronize pairs, max over ranks; ms_per_step = its wall '
+                                'clock / --steps.  --full repeats the block until >= %d steps are timed (timed: median, p95)'
+                                % MIN_TIMED_STEPS,
+            'higher_is_better': True, 'scaling': a.scaling,
+            'vs_baseline': None, 'dtype': 'f64 state / f32 ray-cast', 'data': 'synthetic',
+            'steps_per_s': round(1e3 / ms_per_step, 3), 'particles_total': total_particles,
+            'rccl_ranks': rccl_ranks, 'overlapped_state_gather': bool(has_overlap), 'rccl_library': rccl_library(),
+            'launcher': 'bench.py' if os.environ.get('MCL_BENCH_SPAWNED') == '1' else ('external' if world > 1 else 'none'),
+            'config': {'workload': '%d particles/GPU x %d beams, %s%s, predict+MBES update+normalise+systematic '
+                                   'resample+mean/cov per step' % (P, B, m['desc'], (
+                                       ' -- RECOGNISED AS A LATTICE by mesh_build: swept on its 708 x 708 node heights, no triangle record '
+                                       'is read (an irregular TIN of the same size: value_tin / extra.mesh_tin)') if m['kind'] == 'mesh' else ''),
+                       'particles_per_gpu': P, 'beams': B, 'map': m['kind'], 'parallelism': 'particle-shard x%d' % world},
+            'pose_rmse_m': round(pose_rmse, 4),
+        }
+    if rank == 0 and a.full:
+        first_block_ms = ms_per_step
+        n_timed = a.steps * nblocks
+        path_main = mbes_path(e, P)
         alg = alg_bytes(P, B, m['bytes'], world)
         kernels = kernel_table(tim, alg, a.steps)
         dom = max((k for k in kernels if k in alg), key=lambda k: tim[k][0])
@@ -752,31 +816,18 @@ def worker(a, rank, world, local_rank):
                 traffic_source = 'none: %s is for kernel sources %s, this library is %s' % (rel, tj.get('source_hash'), src)
             break
         streaming = [k for k in ('predict', 'normalise', 'scan', 'resample', 'mean_cov') if k in kernels]
-        out = {
-            'metric': METRIC,
-            'value': round(value, 3), 'unit': 'steps/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
-            'ms_per_step': round(ms_per_step, 4), 'first_block_ms': round(first_block_ms, 4),
-            'value_definition': 'steps/s of the MEDIAN of the timed blocks (each exactly --steps steps between barrier + '
-                                'synchronize pairs, max over ranks; >= %d steps in all); first_block_value is the contract\'s '
-                                'single block right after the warm-up (rounds 1-2 reported that one)' % MIN_TIMED_STEPS,
+        out.update({
+            'first_block_ms': round(first_block_ms, 4),
             'first_block_value': round(1e3 / first_block_ms * (total_particles / 1048576.0), 3),
-            'higher_is_better': True, 'scaling': a.scaling,
-            'vs_baseline': None, 'dtype': 'f64 state / f32 ray-cast', 'data': 'synthetic',
-            'steps_per_s': round(1e3 / ms_per_step, 3), 'particles_total': total_particles, 'cloud': cloud,
-            'rccl_ranks': rccl_ranks, 'overlapped_state_gather': bool(has_overlap), 'rccl_library': rccl_library(),
-            'launcher': 'bench.py' if os.environ.get('MCL_BENCH_SPAWNED') == '1' else ('external' if world > 1 else 'none'),
+            'cloud': cloud,
             'timed': {'blocks': nblocks, 'steps_per_block': a.steps, 'steps_total': n_timed,
                       'ms_per_step_median': round(pctl(block_ms, 50), 4), 'ms_per_step_p95': round(pctl(block_ms, 95), 4),
                       'ms_per_step_min': round(min(block_ms), 4), 'ms_per_step_max': round(max(block_ms), 4),
                       'note': 'the timed block (exactly --steps steps between barrier+synchronize pairs, max over ranks) '
-                              'is repeated until >= %d steps are timed; value / ms_per_step are the MEDIAN block, '
-                              'first_block_ms the first one; the per-phase HIP events (kernels, roofline.launch_us) are '
+                              'is repeated until >= %d steps are timed; value / ms_per_step are the first block, '
+                              'ms_per_step_median the median one (the first block still holds the clock ramp and the cloud '
+                              'contracting after the warm-up); the per-phase HIP events (kernels, roofline.launch_us) are '
                               'recorded on one further block after them' % MIN_TIMED_STEPS},
-            'config': {'workload': '%d particles/GPU x %d beams, %s%s, predict+MBES update+normalise+systematic '
-                                   'resample+mean/cov per step' % (P, B, m['desc'], (
-                                       ' -- RECOGNISED AS A LATTICE by mesh_build: swept on its 708 x 708 node heights, no triangle record '
-                                       'is read (an irregular TIN of the same size: value_tin / extra.mesh_tin)') if m['kind'] == 'mesh' else ''),
-                       'particles_per_gpu': P, 'beams': B, 'map': m['kind'], 'parallelism': 'particle-shard x%d' % world},
             # (the dominant kernel is bound by vector issue -- `frac` stays the HBM figure SURVEY 8(d)
             #  defines, `frac_valu` is the share of the chip's vector-issue slots, from the offline PMC passes)
             'roofline': {'bound': 'valu_issue' if dom == 'update_mbes' else 'hbm', 'kernel': dom, 'achieved': round(achieved, 3), 'peak': HBM_PEAK_GBS,
@@ -809,8 +860,7 @@ def worker(a, rank, world, local_rank):
                                  'valu_insts_per_ray = wave instructions x 64 / (particles x beams); '
                                  'streaming kernels are listed in "kernels" with their own HBM fractions'},
             'kernels': kernels,
-            'pose_rmse_m': round(pose_rmse, 4),
-        }
+        })
         if world > 1:
             sent, lost = e.exchange_stats()
             ops, rounds = e.exchange_ops()
@@ -829,8 +879,8 @@ def worker(a, rank, world, local_rank):
                                        'moved 28 B x N_global per rank per step'}
     e.close()
 
-    # ---- N = 1: CPU baseline, trajectory RMSE against the oracle, extra workload legs
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    # ---- --full at N = 1: CPU baseline, trajectory RMSE against the oracle, extra workload legs
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         # all host cores (the oracle's particle loops are OpenMP-parallel) and, beside it, one thread
         ns = a.cpu_particles or (8192 if m['kind'] == 'grid' else 4096)
         cores = host_cores()
@@ -863,7 +913,7 @@ def worker(a, rank, world, local_rank):
         allc['pose_rmse_vs_oracle_m'] = rm
         allc['reference_python'] = REFERENCE_PYTHON
         out['cpu_baseline'] = allc
-    if rank == 0 and world == 1 and not a.no_extra:
+    if rank == 0 and world == 1 and a.full and not a.no_extra:
         extra = {}
         legs = []
         mesh = m if a.map == 'mesh' else build_map('mesh')

@@ -82,7 +82,7 @@ def verify(directory=GOLDEN, against=None):
 
 # (script, arguments, needs /root/reference)
 GENERATORS = (('gen_golden.py', (), True), ('gen_golden_dr.py', (), True), ('gen_golden_stats.py', (), True),
-              ('gen_launch_fixture.py', (), True), ('gen_golden_mbes.py', (), False))
+              ('gen_launch_fixture.py', (), True), ('gen_golden_munkres.py', (), True), ('gen_golden_mbes.py', (), False))
 
 
 def regenerate(out_dir, scripts=None, mbes_cases=None):

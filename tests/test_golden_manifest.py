@@ -41,7 +41,8 @@ def test_self_oracle_cases_regenerate_bit_for_bit(tmp_path):
 
 @pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='the reference only exists in the build container; the manifest check stands for these fixtures elsewhere')
 def test_reference_derived_fixtures_regenerate_bit_for_bit(tmp_path):
-    manifest.regenerate(str(tmp_path), scripts=['gen_golden.py', 'gen_golden_dr.py', 'gen_golden_stats.py', 'gen_launch_fixture.py'])
+    manifest.regenerate(str(tmp_path), scripts=['gen_golden.py', 'gen_golden_dr.py', 'gen_golden_stats.py', 'gen_launch_fixture.py',
+                                                'gen_golden_munkres.py'])
     made = manifest.fixtures(str(tmp_path))
     committed = manifest.load()
     assert made == sorted(n for n, e in committed.items() if e['needs_reference'])

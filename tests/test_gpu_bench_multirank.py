@@ -42,7 +42,7 @@ def _bench(lib, args, timeout=900, **env_extra):
 @pytest.mark.parametrize('exchange', ['p2p', 'allgather'])
 def test_two_real_ranks_of_the_bench_worker_on_one_gpu(fake_nccl, exchange):
     extra = {} if exchange == 'p2p' else {'MCL_EXCHANGE': 'allgather'}
-    rc, out, err, el = _bench(fake_nccl, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--only-main', '--particles', '262144'], **extra)
+    rc, out, err, el = _bench(fake_nccl, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--full', '--only-main', '--particles', '262144'], **extra)
     assert rc == 0, err[-4000:]
     lines = [l for l in out.strip().splitlines() if l.startswith('{')]
     assert len(lines) == 1, out[-2000:]   # ONE JSON line, rank 0's
@@ -67,7 +67,7 @@ def test_two_real_ranks_of_the_bench_worker_on_one_gpu(fake_nccl, exchange):
 def test_eight_real_ranks_of_the_bench_worker_on_one_gpu(fake_nccl):
     """The size of the driver's last SCALE run: `python bench.py --gpus 8`, eight real processes on the one GPU (65 536
     particles each), the point-to-point exchange among eight peers.  One line, rank 0's; every rank reports lost slots."""
-    rc, out, err, el = _bench(fake_nccl, ['--gpus', '8', '--steps', '5', '--warmup', '2', '--only-main', '--particles', '65536'], FAKE_NCCL_TIMEOUT_S='60')
+    rc, out, err, el = _bench(fake_nccl, ['--gpus', '8', '--steps', '5', '--warmup', '2', '--full', '--only-main', '--particles', '65536'], FAKE_NCCL_TIMEOUT_S='60')
     assert rc == 0, err[-4000:]
     lines = [l for l in out.strip().splitlines() if l.startswith('{')]
     assert len(lines) == 1, out[-2000:]
@@ -90,7 +90,7 @@ def test_external_launcher_form_with_two_real_ranks(fake_nccl):
     env.update(LD_PRELOAD=fake_nccl, FAKE_NCCL_SHM='1', FAKE_NCCL_TIMEOUT_S='20', MCL_BENCH_ONE_DEVICE='1')
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                         '--master-addr', '127.0.0.1', '--master-port', port, BENCH, '--gpus', '2', '--steps', '5', '--warmup', '2',
-                        '--only-main', '--particles', '131072'],
+                        '--full', '--only-main', '--particles', '131072'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, universal_newlines=True)
     assert p.returncode == 0, p.stderr[-4000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])

@@ -1,13 +1,30 @@
-"""The oracle's assignment solver against the REFERENCE's own Munkres (oracle/_ref, compiled from
-/root/reference/auv_ekf_slam/utils/munkres where it lies) on correspondence tables built the way
+"""The oracle's assignment solver against the REFERENCE's own Munkres (oracle/_ref, compiled from the reference's
+auv_ekf_slam/utils/munkres where it lies) on correspondence tables built the way
 auv_ekf_slam/src/ekf_slam_core.cpp:172-296 builds them, and the assignment-based landmark update's
-basic properties.  CPU only."""
+basic properties.  CPU only.  Where oracle/_ref is not built, the reference's answers on the same tables come from
+tests/golden/munkres_ref.npz (oracle/ref_harness/gen_golden_munkres.py)."""
 import itertools
+import os
 
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
+
+MUNKRES_REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'munkres_ref.npz')
+
+
+def ref_munkres(key, table):
+    """The reference's Munkres on `table` (row_of_col): live from oracle/_ref where it is built, else the answer it gave
+    on the same table, recorded under `key` (the recorded table must be this one)."""
+    live = orc.ref_munkres(table)
+    if live is not None:
+        return live
+    with np.load(MUNKRES_REF, allow_pickle=False) as z:
+        rec_table, rec = z[key + '_table'], z[key + '_row_of_col']
+    assert rec_table.shape == table.shape, key
+    np.testing.assert_allclose(table, rec_table, rtol=1e-12, atol=0)
+    return rec
 
 
 def _table(rs, n_lm, n_det, gate=11.34, new_mh=9.0, p_in=0.3):
@@ -32,22 +49,24 @@ def test_dense_solver_is_optimal_on_small_tables():
         assert total == pytest.approx(sum(c[r, col[r]] for r in range(n)), rel=1e-14)
 
 
-def test_dense_solver_matches_reference_munkres():
+def dense_cases():
+    """The correspondence tables of the dense-solver check, in order: (key, n_lm, n_det, rep, table)."""
     rs = np.random.RandomState(1)
-    probe = orc.ref_munkres(np.zeros((2, 2)))
-    if probe is None:
-        pytest.skip('oracle/_ref/libref_munkres.so not built (needs /root/reference)')
-    n_cases = 0
     for n_lm, n_det in [(3, 2), (8, 4), (20, 8), (40, 16), (64, 16), (5, 7)]:
         for rep in range(12):
-            t = _table(rs, n_lm, n_det, p_in=[0.1, 0.3, 0.7][rep % 3])
-            row_of_col = orc.ref_munkres(t)
-            assert (row_of_col >= 0).all() and len(set(row_of_col.tolist())) == n_det
-            ref_total = sum(t[row_of_col[c], c] for c in range(n_det))
-            col, total = orc.assign_dense(t.T.copy())      # oracle layout: rows = measurements
-            assert total == pytest.approx(ref_total, rel=1e-12), (n_lm, n_det, rep)
-            assert ref_total < 10000.0                       # never an "infinite" pair: each measurement owns a row
-            n_cases += 1
+            yield 'dense_%d_%d_%d' % (n_lm, n_det, rep), n_lm, n_det, rep, _table(rs, n_lm, n_det, p_in=[0.1, 0.3, 0.7][rep % 3])
+
+
+def test_dense_solver_matches_reference_munkres():
+    n_cases = 0
+    for key, n_lm, n_det, rep, t in dense_cases():
+        row_of_col = ref_munkres(key, t)
+        assert (row_of_col >= 0).all() and len(set(row_of_col.tolist())) == n_det
+        ref_total = sum(t[row_of_col[c], c] for c in range(n_det))
+        col, total = orc.assign_dense(t.T.copy())      # oracle layout: rows = measurements
+        assert total == pytest.approx(ref_total, rel=1e-12), (n_lm, n_det, rep)
+        assert ref_total < 10000.0                       # never an "infinite" pair: each measurement owns a row
+        n_cases += 1
     assert n_cases == 72
 
 
@@ -106,18 +125,25 @@ def _maha_scene(seed, n_lm=120, n_det=7, n=6):
     return soa, m2o, off, lm, cov, Q6, det
 
 
-@pytest.mark.parametrize('seed', [1, 2, 3, 4])
+MAHA_SEEDS = [1, 2, 3, 4]
+
+
+def maha_table(soa, m2o, off, lm, cov, Q6, det, gate, new_mh):
+    """The oracle's log-weight of the first particle and the dense correspondence table behind it."""
+    lw, asg, tab = orc.landmark_assign_update_maha(soa[:, :1].copy(), m2o, off, lm, det, 0.3, 8, gate, new_mh, lmcov=cov,
+                                                   Q6=Q6, want_assign=True, want_table=True)
+    return lw, tab
+
+
+@pytest.mark.parametrize('seed', MAHA_SEEDS)
 def test_mahalanobis_table_end_to_end_against_reference_munkres(seed):
     """The dense correspondence table built the reference's way (sensor-frame innovation, S = R^T Sigma_j R + Q,
     d_m if < gate else 10000, one new-landmark row per detection: ekf_slam_core.cpp:135-178,248-281) handed to
     the REFERENCE's own Munkres (oracle/_ref): its optimal total is the total behind the oracle's log-weight."""
     soa, m2o, off, lm, cov, Q6, det = _maha_scene(seed)
     gate, new_mh = 11.345, 9.0
-    lw, asg, tab = orc.landmark_assign_update_maha(soa[:, :1].copy(), m2o, off, lm, det, 0.3, 8, gate, new_mh, lmcov=cov,
-                                                   Q6=Q6, want_assign=True, want_table=True)
-    row_of_col = orc.ref_munkres(tab)
-    if row_of_col is None:
-        pytest.skip('oracle/_ref not built (reference sources absent)')
+    lw, tab = maha_table(soa, m2o, off, lm, cov, Q6, det, gate, new_mh)
+    row_of_col = ref_munkres('maha_%d' % seed, tab)
     total_ref = sum(tab[row_of_col[c], c] for c in range(tab.shape[1]))
     nv = tab.shape[1]
     Q = np.array([[Q6[0], Q6[1], Q6[2]], [Q6[1], Q6[3], Q6[4]], [Q6[2], Q6[4], Q6[5]]])

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=/tmp/kst; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 $R/bench.py "$@" --steps 50 --warmup 5 --only-main > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 $R/bench.py "$@" --steps 50 --warmup 5 --full --only-main > /dev/null 2>&1
 python3 - $O <<'PY'
 import csv, glob, sys
 for p in glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True):

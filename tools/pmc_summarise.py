@@ -42,7 +42,7 @@ def main():
     rnd = os.environ.get('ROUND', 'r06')
     out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, 'profiles', '%s_traffic.json' % rnd)
     res = {'_how': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* (three separate passes) on '
-                   '`python3 bench.py --map <m> --steps 4 --warmup 1 --only-main`, dominant kernel k_mbes_sweep<2,false,false> (mesh) / k_mbes_sweep<0,false,false> (grid): the fan sweep (one pass since round 4), '
+                   '`python3 bench.py --map <m> --steps 4 --warmup 1 --full --only-main`, dominant kernel k_mbes_sweep<2,false,false> (mesh) / k_mbes_sweep<0,false,false> (grid): the fan sweep (one pass since round 4), '
                    'mean over dispatches; KB -> bytes x1024; FETCH_SIZE doubled (gfx950 reports half of a wide streaming read)',
            '_round': int(rnd.lstrip('r')), 'source_hash': bench.source_hash()}
     # (round 6: the adjacency walk over an irregular TIN -- the path of any real survey mesh -- with its cache counters, and the

@@ -13,9 +13,9 @@ SQ2="SQ_WAIT_INST_ANY SQ_INSTS_SALU SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_INSTS_V
 pass() {  # pass <dir> <counters or --stats> <bench args...>
   local d=$1 c=$2; shift 2
   if [ "$c" = "--stats" ]; then
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/$d -- python3 $R/bench.py "$@" --steps 50 --warmup 5 --only-main > $O/bench_${d#stats_}.log 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/$d -- python3 $R/bench.py "$@" --steps 50 --warmup 5 --full --only-main > $O/bench_${d#stats_}.log 2>&1
   else
-    rocprofv3 --pmc $c --output-format csv -d $O/$d -- python3 $R/bench.py "$@" --steps 4 --warmup 1 --only-main > /dev/null 2>&1
+    rocprofv3 --pmc $c --output-format csv -d $O/$d -- python3 $R/bench.py "$@" --steps 4 --warmup 1 --full --only-main > /dev/null 2>&1
   fi
 }
 for m in mesh grid mesh-tin; do
@@ -28,17 +28,17 @@ pass pmc_mesh_sq2 "$SQ2" --map mesh
 # cache counters of the two sweeps (L2: TCC_HIT / TCC_MISS; vector L1: accesses and what went on to L2)
 for m in mesh mesh-tin; do
   pass pmc_${m}_cache "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" --map $m
-  rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum --output-format csv -d $O/pmc_${m}_cache -- python3 $R/bench.py --map $m --steps 4 --warmup 1 --only-main > /dev/null 2>&1
+  rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum --output-format csv -d $O/pmc_${m}_cache -- python3 $R/bench.py --map $m --steps 4 --warmup 1 --full --only-main > /dev/null 2>&1
 done
 # the filter that keeps a healthy spread (likelihood tempered by 1 / beams), lattice and TIN: stats + SQ + L2
 for m in mesh mesh-tin; do
   pass stats_${m}_tempered --stats --map $m --temper
-  rocprofv3 --pmc $SQ1 --output-format csv -d $O/pmc_${m}_tempered_sq -- python3 $R/bench.py --map $m --temper --steps 60 --warmup 30 --only-main > /dev/null 2>&1
-  rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $O/pmc_${m}_tempered_cache -- python3 $R/bench.py --map $m --temper --steps 60 --warmup 30 --only-main > /dev/null 2>&1
+  rocprofv3 --pmc $SQ1 --output-format csv -d $O/pmc_${m}_tempered_sq -- python3 $R/bench.py --map $m --temper --steps 60 --warmup 30 --full --only-main > /dev/null 2>&1
+  rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $O/pmc_${m}_tempered_cache -- python3 $R/bench.py --map $m --temper --steps 60 --warmup 30 --full --only-main > /dev/null 2>&1
 done
 # BASELINE config 5's shard (524 288 particles, fused landmark step) and the irregular soup: kernel tables only
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_config5 -- python3 $R/tools/experiments/leg.py config5 30 > $O/bench_config5.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_soup -- python3 $R/bench.py --map mesh-soup --steps 10 --warmup 2 --only-main > $O/bench_soup.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_soup -- python3 $R/bench.py --map mesh-soup --steps 10 --warmup 2 --full --only-main > $O/bench_soup.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_config4_rccl -- python3 $R/tools/experiments/leg.py config4_rccl 30 > $O/bench_config4_rccl.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_tin_hole -- python3 $R/tools/experiments/leg.py tin_hole 50 > $O/bench_tin_hole.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_tin_ragged -- python3 $R/tools/experiments/leg.py tin_ragged 50 > $O/bench_tin_ragged.log 2>&1

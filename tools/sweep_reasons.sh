@@ -11,4 +11,4 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 V=/tmp/libmcl_reasons.so
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -Wno-unused-function -Wno-bitwise-instead-of-logical \
   -fno-slp-vectorize -DSWEEP_REASONS=1 -o $V $R/smarc_navigation_amd/csrc/mcl_api.hip -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
-MCL_LIB=$V MCL_DEBUG_WORK=1 python3 $R/bench.py --only-main --steps 3 --warmup 1 "$@" 2>&1 >/dev/null | grep '^\[mbes\]' | tail -6
+MCL_LIB=$V MCL_DEBUG_WORK=1 python3 $R/bench.py --full --only-main --steps 3 --warmup 1 "$@" 2>&1 >/dev/null | grep '^\[mbes\]' | tail -6

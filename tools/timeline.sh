@@ -6,7 +6,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=/tmp/tl; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -- python3 $R/bench.py --map mesh --steps 20 --warmup 3 --only-main > /dev/null 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -- python3 $R/bench.py --map mesh --steps 20 --warmup 3 --full --only-main > /dev/null 2>&1
 python3 - $O <<'PY'
 import csv, glob, sys
 O = sys.argv[1]
