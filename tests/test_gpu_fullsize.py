@@ -316,3 +316,91 @@ def test_config2_exact_shape_step_parity():
         mean, yaw, c9 = e.mean_cov()
         m6, _, c_ref = orc.mean_cov(ref)
         np.testing.assert_allclose(mean, m6, rtol=0, atol=1e-9)
+
+
+def _dive_surface(kind):
+    """(omap, engine map attachment, m2o) of a surface of the bench's legs (bench.py: build_map and the leg's own map <- odom
+    transform; the round-6 legs through its punch_hole / synth.mesh_ragged)"""
+    from oracle import oracle as orc
+    import bench
+    m = bench.build_map('grid' if kind == 'grid' else ('mesh' if kind == 'mesh' else 'mesh-tin'))
+    m2o = None
+    if kind == 'mesh_tin_gaps':
+        m = bench.punch_gaps(m)
+    elif kind == 'mesh_tin_hole_under_swath':
+        m = bench.punch_hole(m, 1.0, 10.0)
+    elif kind in ('mesh_tin_ragged_outline', 'mesh_tin_vehicle_off_the_map'):
+        m = dict(m, tris=synth.mesh_ragged(m['verts'], m['tris']))
+        m2o = synth.rigid_matrix(100.0, -330.0 if kind == 'mesh_tin_ragged_outline' else -360.0, 0.0, 0.0, 0.0, 0.0)
+    omap = orc.Grid(m['z'], m['origin'], m['res']) if kind == 'grid' else orc.Mesh(m['verts'], m['tris'])
+    return m, omap, m2o
+
+
+_GAPS = ('mesh_tin_gaps', 'mesh_tin_hole_under_swath', 'mesh_tin_ragged_outline', 'mesh_tin_vehicle_off_the_map')
+
+
+@pytest.mark.parametrize('kind,attitude', [(k, 'dive') for k in ('mesh', 'grid', 'mesh_tin') + _GAPS] +
+                         [(k, 'level') for k in _GAPS[1:]])
+def test_full_size_diving_cloud_and_the_round6_surfaces(kind, attitude):
+    """1 M particles x 512 beams through the fan sweep with the whole cloud at one attitude far from level (pitch 0.26 rad =
+    15 degrees, roll 0.05: a diving AUV, every particle the odometry's pitch) on every sweep surface of the bench, and level
+    on the round-6 surfaces (a data gap under the swath, the ragged outline of a real survey, the vehicle off that map looking
+    back in) -- one lane per side, the at-size code the small-cloud tests never reach.  A random sample of 1 024 and up to
+    1 024 live particles against the oracle under the live-particle contract, at the metric's sigma and at the tempered
+    filter's (where a thousand particles are live); on the surfaces with gaps mesh_tin_gaps' rule: a particle beyond the
+    tolerance must own a ray that flips at a rim (an answer of the oracle under a 1 mm shift), at most one in 25."""
+    from smarc_navigation_amd import engine as eng
+    from oracle import oracle as orc
+    from tests.helpers import live_particle_contract, live_picks
+    bench_map, omap, m2o = _dive_surface(kind)
+    roll, pitch = (0.05, 0.26) if attitude == 'dive' else (0.015, -0.02)
+    ba = synth.beam_angles(B)
+    rs = np.random.RandomState(21)
+    soa = rs.randn(6, N) * np.array([1.5, 1.5, 0.0, 0.0, 0.0, 0.2])[:, None]
+    if m2o is None and kind != 'mesh_tin_hole_under_swath':
+        soa[0] += 30.0
+        soa[1] += -12.0
+    soa[2] = -2.2
+    soa[3] = roll
+    soa[4] = pitch
+    m2o = np.identity(4) if m2o is None else m2o
+    e = eng.Engine(N, m2o=m2o, rng_mode=eng.RNG_REPLAY)
+    e.set_particles(soa)
+    import bench
+    bench.attach_map(e, bench_map)
+    truth = np.array([[soa[0].mean()], [soa[1].mean()], [-2.2], [roll], [pitch], [0.0]])
+    _, ex = orc.mbes_update(truth, m2o, [0] * 6, omap, ba, None, 0.2, 100.0)
+    ranges = (ex[0] + 0.2 * np.random.RandomState(2).randn(B)).astype(np.float32)
+    ranges[ex[0] >= 100.0] = 0.0
+    label = '%s %s 1 M x 512' % (kind, attitude)
+    from tests.helpers import lw_outliers_explained
+    # sigma 0.2 (the metric's ping) and 0.2 sqrt(512) (bench.py's tempered filter: the cloud keeps a spread, so a thousand
+    # particles are live even where one gap under a beam puts the rest 30 below the best)
+    for sigma in (0.2, 0.2 * np.sqrt(B)):
+        e.update_mbes(ranges, ba, sigma, 100.0)
+        path, handed, _ = e.mbes_last_path()
+        lw = e.get_log_weights()
+        print('%s, sigma %.2f: path %d, the sweep handed over %d of %d (%d beams of the ping miss)' % (
+            label, sigma, path, handed, N, int((ex[0] >= 100.0).sum())))
+        assert path == 1, path
+        # a random sample under the rule of the level test (surfaces with gaps: rim flips, few and each an oracle answer)
+        pick = np.random.RandomState(3).choice(N, 1024, replace=False)
+        sub = np.ascontiguousarray(soa[:, pick])
+        lw_ref, _ = orc.mbes_update(sub, m2o, [0] * 6, omap, ba, ranges, sigma, 100.0)
+        d = np.abs(lw[pick] - lw_ref)
+        okm = (d <= 1e-2) | (d <= 2e-4 * np.abs(lw_ref))
+        print('%s, sigma %.2f: random sample max |dlw| %.3e, outside tolerance %d' % (label, sigma, d.max(), int((~okm).sum())))
+        if kind in _GAPS:
+            assert (~okm).sum() <= pick.size // 25, int((~okm).sum())
+            lw_outliers_explained(orc, omap, sub, ba, ranges, sigma, 100.0, lw[pick], lw_ref, m2o=m2o, label=label)
+        else:
+            assert np.all(okm)
+        live = live_picks(lw, 1024, seed=6)
+        lsub = np.ascontiguousarray(soa[:, live])
+        lw_live, _ = orc.mbes_update(lsub, m2o, [0] * 6, omap, ba, ranges, sigma, 100.0)
+        n_live, _, _ = live_particle_contract(orc, omap, lsub, ba, ranges, sigma, 100.0, lw[live], lw_live, float(lw.max()), m2o=m2o,
+                                              label='%s, sigma %.2f' % (label, sigma), allow=live.size // 25 if kind in _GAPS else None)
+        # (with a gap every 6 m a displaced particle's beams fall into gaps: even tempered, about ten particles of that cloud
+        #  are live -- the random sample above covers the rest of it)
+        assert n_live >= (16 if sigma > 1.0 and kind != 'mesh_tin_gaps' else 1)
+    e.close()

@@ -1,0 +1,529 @@
+"""The fan sweep (smarc_navigation_amd/csrc/mcl_sweep.h) at DIVING attitudes and across its tilt bound.  A fan is swept only
+while c2z = R_map_sensor[2][2] >= sweep_c2z_min, tan_lim = min(tan 35 deg, (grid 0.45 | mesh 0.8) / slope_max)
+(mcl_host_update.h); the margins inside the kernel -- the grid cell walk's arc bulge, sweep_border_final, the rim sweep's
+off_box branch, the fused step's proof that the clamp to r_max is idle -- are derived from that bound.  A real AUV dives at
+10 - 20 degrees of pitch and every particle takes the odometry's pitch: here the whole cloud shares one attitude, far from
+level, and particles sit just inside and just outside the bound on maps where the slope term (not the 35 degree cap) sets
+it.  Every ray against the fp64 brute-force oracle (oracle/mcl_oracle.c), whatever path cast the particle; the tolerances
+are the suite's (rays within 1e-3 m up to isolated grazing rays the oracle itself moves under a 1 mm shift, log-weights
+within |d| <= 1e-2 or 2e-4 |lw|)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from smarc_navigation_amd import synth
+from tests.helpers import live_particle_contract, live_picks, lw_outliers_explained, outliers_explained
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(autouse=True)
+def _force_sweep(monkeypatch):
+    """MCL_SWEEP=1 (read at mcl_create): the sweep takes the small clouds the oracle can check ray by ray."""
+    monkeypatch.setenv('MCL_SWEEP', '1')
+
+
+@pytest.fixture(scope='module')
+def orc():
+    from oracle import oracle
+    return oracle
+
+
+@pytest.fixture(scope='module')
+def eng():
+    from smarc_navigation_amd import engine
+    return engine
+
+
+# ------------------------------------------------------------------ the bound, computed in fp64 as the library does
+def _rot(roll, pitch, yaw):
+    """static-xyz Rz(yaw) Ry(pitch) Rx(roll), vectorised over arrays of angles: (..., 3, 3)"""
+    roll, pitch, yaw = np.broadcast_arrays(np.asarray(roll, float), np.asarray(pitch, float), np.asarray(yaw, float))
+    cr, sr, cp, sp, cy, sy = np.cos(roll), np.sin(roll), np.cos(pitch), np.sin(pitch), np.cos(yaw), np.sin(yaw)
+    return np.stack([np.stack([cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr], -1),
+                     np.stack([sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr], -1),
+                     np.stack([-sp, cp * sr, cp * cr], -1)], -2)
+
+
+def _sensor_frame(soa, m2o=None, off=None):
+    """R_map_sensor = R(m2o) R(particle) R(mount) per particle, fp64 (oracle/mcl_oracle.c: orc_mbes_update)"""
+    m2o = np.identity(4) if m2o is None else np.asarray(m2o)
+    off = [0.0] * 6 if off is None else off
+    return np.einsum('ij,njk,kl->nil', m2o[:3, :3], _rot(soa[3], soa[4], soa[5]), _rot(off[3], off[4], off[5]))
+
+
+def _c2z(soa, m2o=None, off=None):
+    return _sensor_frame(soa, m2o, off)[:, 2, 2]
+
+
+def _slope_grid(z, res):
+    """mcl_api.hip, mcl_set_map_grid: a bilinear patch's x slope lies between those of its two x edges, its y slope between
+    those of its two y edges"""
+    h = z.astype(np.float64)
+    ax = np.maximum(np.abs(h[1:, :-1] - h[:-1, :-1]), np.abs(h[1:, 1:] - h[:-1, 1:]))
+    ay = np.maximum(np.abs(h[:-1, 1:] - h[:-1, :-1]), np.abs(h[1:, 1:] - h[1:, :-1]))
+    return float(np.sqrt((ax * ax + ay * ay).max()) / res)
+
+
+def _slope_lattice(z, res):
+    """mcl_mesh.h (structured mesh): the four combinations of one x edge and one y edge of a cell -- the grid's rule"""
+    return _slope_grid(z, res)
+
+
+def _slope_tin(verts, tris):
+    """mcl_halfedge.h, adjacency: the steepest triangle's gradient |(nx, ny) / nz|"""
+    p = verts.astype(np.float64)[tris.astype(np.int64)]
+    a, b = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    nz = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+    nx = a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]
+    ny = a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2]
+    return float(np.sqrt(((nx * nx + ny * ny) / (nz * nz)).max()))
+
+
+def _c2z_min(slope, grid):
+    tan_lim = min(np.tan(np.radians(35.0)), (0.45 if grid else 0.8) / max(slope, 1e-9))
+    return 1.0 / np.sqrt(1.0 + tan_lim * tan_lim)
+
+
+def test_c2z_of_the_sensor_frame_is_the_oracles(orc):
+    """The fp64 c2z above against the oracle's own geometry: over a flat seabed the nadir beam travels depth / c2z -- any
+    roll, pitch, heading, mounting rotation and map-frame tilt."""
+    rs = np.random.RandomState(5)
+    origin, res = (-200.0, -200.0), 1.0
+    z = np.full((401, 401), -30.0, np.float32)
+    n = 256
+    soa = np.zeros((6, n))
+    soa[0], soa[1], soa[2] = rs.uniform(-5, 5, n), rs.uniform(-5, 5, n), rs.uniform(-4.0, -1.0, n)
+    soa[3], soa[4], soa[5] = rs.uniform(-0.4, 0.4, n), rs.uniform(-0.6, 0.6, n), rs.uniform(-np.pi, np.pi, n)
+    for m2o, off in ((None, None), (synth.rigid_matrix(0.0, 0.0, 0.0, 0.02, -0.015, 0.7), [0.0, 0.0, 0.0, 0.08, -0.1, 0.05])):
+        m = np.identity(4) if m2o is None else m2o
+        _, ex = orc.mbes_update(soa, m, [0.0] * 6 if off is None else off, orc.Grid(z, origin, res), np.zeros(1, np.float32), None, 0.2, 500.0)
+        oz = m[2, :3] @ soa[:3] + m[2, 3]
+        want = (oz + 30.0) / _c2z(soa, m2o, off)
+        assert np.abs(ex[:, 0] - want).max() <= 1e-9 * want.max(), np.abs(ex[:, 0] - want).max()
+
+
+# ------------------------------------------------------------------ a. diving fuzz
+_KINDS = ('grid', 'mesh', 'mesh2', 'tin', 'ragged', 'beyond')
+
+
+def _dive_scene(seed):
+    """map, cloud, sensor and ping of diving-fuzz scene `seed`: the surfaces in turn, one attitude for the whole cloud"""
+    rs = np.random.RandomState(4000 + seed)
+    kind = _KINDS[seed % len(_KINDS)]
+    res = float(rs.choice([0.5, 1.0, 2.0])) if kind in ('grid', 'mesh', 'mesh2') else 1.0
+    nx, ny = int(150 / res) + rs.randint(0, 30), int(150 / res) + rs.randint(0, 30)
+    origin = (-0.5 * nx * res + rs.uniform(-5, 5), -0.5 * ny * res + rs.uniform(-5, 5))
+    z = synth.bathymetry_grid(nx, ny, res, origin, seed=500 + seed, depth=-rs.uniform(12.0, 35.0),
+                              swell=rs.uniform(0.0, 4.0), fbm_amp=rs.uniform(0.1, 1.5))
+    verts = tris = None
+    centre = [rs.uniform(-8, 8), rs.uniform(-8, 8)]
+    if kind in ('mesh', 'mesh2'):
+        verts, tris = synth.mesh_from_grid(z, res, origin, diagonal='00-11' if kind == 'mesh' else '10-01')
+    elif kind != 'grid':
+        verts, tris = synth.mesh_tin(z, res, origin, seed=seed, jitter=float(rs.choice([0.1, 0.25])))
+        if kind in ('ragged', 'beyond'):
+            c = verts[tris.astype(np.int64)].mean(axis=1)
+            gone = np.zeros(len(tris), bool)
+            for _ in range(int(rs.choice([3, 12]))):
+                p = (rs.uniform(-40, 40), rs.uniform(-40, 40))
+                gone |= np.hypot(c[:, 0] - p[0], c[:, 1] - p[1]) < rs.uniform(0.6, 3.0)
+            tris = synth.mesh_ragged(verts, np.ascontiguousarray(tris[~gone]), seed=seed, band=3.0, bays=6,
+                                     bay_width=(2.0, 5.0), bay_depth=(8.0, 30.0))
+            # at the southern outline (the rim kernel walks across bays and off the outline) / beyond it, looking back in
+            centre = [rs.uniform(-30, 30), origin[1] + (rs.uniform(4.0, 14.0) if kind == 'ragged' else -rs.uniform(1.0, 5.0))]
+        verts, tris = synth.mesh_shuffle(verts, tris, seed=seed)
+    lattice = kind in ('mesh', 'mesh2')
+    n = 49152 if lattice and seed >= 12 else 256       # (49 152 on a lattice mesh: one lane per side, mcl_host_update.h sweep_lanes_per_side)
+    B = int(rs.choice([9, 64, 257, 512]))
+    pitch = float(rs.choice([-1, 1]) * rs.choice([0.17, 0.35, 0.52]))
+    roll = float(rs.choice([-1, 1]) * rs.choice([0.0, 0.15, 0.3]))
+    srs = np.random.RandomState(seed)
+    soa = np.empty((6, n))
+    soa[0] = centre[0] + 3.0 * srs.randn(n)
+    soa[1] = centre[1] + 3.0 * srs.randn(n)
+    soa[2] = -rs.uniform(0.5, 6.0) + 0.3 * srs.randn(n)
+    soa[3] = roll + 0.01 * srs.randn(n)
+    soa[4] = pitch + 0.01 * srs.randn(n)
+    soa[5] = srs.uniform(-np.pi, np.pi, n)
+    off = [0.0] * 6
+    if seed % 3 == 0:     # a sensor mounted at an angle
+        off = [rs.uniform(-0.5, 0.5), rs.uniform(-0.5, 0.5), rs.uniform(-0.3, 0.3)] + list(rs.uniform(-0.1, 0.1, 3))
+    m2o = synth.rigid_matrix(rs.uniform(-3, 3), rs.uniform(-3, 3), 0.0, 0.0, 0.0, rs.uniform(-3, 3))
+    if seed % 8 == 5:     # a tilted map frame
+        m2o = synth.rigid_matrix(rs.uniform(-3, 3), rs.uniform(-3, 3), 0.0, rs.uniform(-0.02, 0.02), rs.uniform(-0.02, 0.02), rs.uniform(-3, 3))
+    if kind in ('ragged', 'beyond'):   # (the outline is placed in map coordinates)
+        m2o = np.identity(4)
+    ba = synth.beam_angles(B, rs.uniform(0.6, 1.3))
+    r_max = float(rs.choice([40.0, 80.0, 150.0]))
+    return dict(kind=kind, res=res, z=z, origin=origin, verts=verts, tris=tris, soa=soa, off=off, m2o=m2o, ba=ba, B=B,
+                r_max=r_max, n=n, pitch=pitch, roll=roll, rs=rs)
+
+
+def _attach(e, orc, s):
+    if s['kind'] == 'grid':
+        e.set_map_grid(s['z'], s['origin'], s['res'])
+        return orc.Grid(s['z'], s['origin'], s['res'])
+    e.set_map_mesh(s['verts'], s['tris'])
+    return orc.Mesh(s['verts'], s['tris'])
+
+
+@pytest.mark.parametrize('seed', range(24))
+def test_diving_fuzz_against_the_oracle(seed, eng, orc):
+    """Random diving scenes on every sweep surface (height grid, lattice mesh of either diagonal, irregular TIN in random
+    order, TIN with holes and a ragged outline -- the rim kernel --, the vehicle beyond that outline looking back in): the
+    whole cloud at one pitch of +-10 / 20 / 30 degrees and one roll of 0 / +-9 / +-17 degrees (spread 0.01 rad), all headings,
+    mounting rotations and a tilted map frame in some scenes, 9 .. 512 beams.  Every ray and every log-weight against the
+    oracle; at 49 152 particles on a lattice mesh (one lane per side, the at-size code) a random sample of 512."""
+    s = _dive_scene(seed)
+    rs, soa, n, B, ba, r_max, m2o, off = s['rs'], s['soa'], s['n'], s['B'], s['ba'], s['r_max'], s['m2o'], s['off']
+    e = eng.Engine(n, m2o=m2o, rng_mode=eng.RNG_REPLAY)
+    e.set_particles(soa)
+    omap = _attach(e, orc, s)
+    pick = np.arange(n) if n <= 512 else np.sort(np.random.RandomState(seed).choice(n, 512, replace=False))
+    sub = np.ascontiguousarray(soa[:, pick])
+    got = e.mbes_expected(0, n, ba, r_max, off)[pick]
+    path, handed, _ = e.mbes_last_path()
+    assert path == 1
+    _, ref = orc.mbes_update(sub, m2o, off, omap, ba, None, 0.2, r_max)
+    err = np.abs(got - ref)
+    bad = int((err > 1e-3).sum())
+    label = 'dive %d %s pitch %+.2f roll %+.2f n %d B %d' % (seed, s['kind'], s['pitch'], s['roll'], n, B)
+    print('%s: handed over %d/%d, max err %.2e, rays off %d/%d, rays that miss %.0f %%' % (
+        label, handed, n, err.max(), bad, err.size, 100.0 * (ref >= r_max).mean()))
+    assert bad <= max(3, err.size // 4000)
+    outliers_explained(orc, omap, sub, ba, got, ref, r_max, m2o=m2o, off=off, label=label)
+    ranges = (ref[rs.randint(pick.size)] + 0.2 * rs.randn(B)).astype(np.float32)
+    ranges[ranges >= r_max] = 0.0
+    ranges[rs.randint(B)] = 0.0
+    e.update_mbes(ranges, ba, 0.2, r_max, off)
+    path, handed_u, _ = e.mbes_last_path()
+    assert path == 1
+    lw = e.get_log_weights()[pick]
+    lw_ref, _ = orc.mbes_update(sub, m2o, off, omap, ba, ranges, 0.2, r_max)
+    d = np.abs(lw - lw_ref)
+    okm = (d <= 1e-2) | (d <= 2e-4 * np.abs(lw_ref))
+    print('%s: update handed over %d/%d, max |dlw| %.3e, outside tolerance %d' % (label, handed_u, n, d.max(), int((~okm).sum())))
+    assert (~okm).sum() <= (2 if bad else 0) + pick.size // 100
+    lw_outliers_explained(orc, omap, sub, ba, ranges, 0.2, r_max, lw, lw_ref, m2o=m2o, off=off, label=label)
+    e.close()
+
+
+# ------------------------------------------------------------------ b. straddling the bound
+def _bound_map(case):
+    """(kind, z, origin, res, verts, tris, slope, c2z_min) of a map whose bound is set by `case`"""
+    origin, res = (-150.0, -150.0), 1.0
+    if case in ('grid_slope', 'mesh_slope'):
+        # one ridge of known steepness: a ramp in x of slope s, on gentle swell elsewhere -- the slope term binds
+        # (grid slope 1.0: 24.2 deg; mesh slope 2.0: 21.8 deg)
+        s = 1.0 if case == 'grid_slope' else 2.0
+        z = synth.bathymetry_grid(301, 301, res, origin, seed=61, depth=-25.0, swell=0.5, fbm_amp=0.1).astype(np.float64)
+        x = origin[0] + res * np.arange(301)[:, None]
+        z = z + np.clip(s * (x - 40.0), 0.0, 6.0)
+        z = z.astype(np.float32)
+    elif case == 'grid_twisted':
+        z = synth.bathymetry_grid(301, 301, res, origin, seed=62, depth=-25.0, swell=4.0, fbm_amp=3.0)
+    else:   # 'mesh_cap', 'tin_cap': gentle terrain, the 35 degree cap binds
+        z = synth.bathymetry_grid(301, 301, res, origin, seed=63, depth=-25.0, swell=1.0, fbm_amp=0.3)
+    verts = tris = None
+    if case.startswith('grid'):
+        slope = _slope_grid(z, res)
+        kind = 'grid'
+    elif case == 'tin_cap':
+        verts, tris = synth.mesh_tin(z, res, origin, seed=64)
+        slope = _slope_tin(verts, tris)
+        kind = 'tin'
+    else:
+        verts, tris = synth.mesh_from_grid(z, res, origin)
+        slope = _slope_lattice(z, res)
+        kind = 'mesh'
+    return kind, z, origin, res, verts, tris, slope, _c2z_min(slope, kind == 'grid')
+
+
+_EPS = (-1e-2, -1e-4, -1e-6, 0.0, 1e-6, 1e-4, 1e-2)
+
+
+@pytest.mark.parametrize('interior_only', [False, True])
+@pytest.mark.parametrize('case', ['grid_slope', 'mesh_slope', 'grid_cap_twisted', 'mesh_cap', 'tin_cap'])
+def test_particles_straddling_the_tilt_bound(case, interior_only, eng, orc):
+    """Particles whose fan leans from the vertical by just less or just more than the bound allows: c2z = c2z_min (1 + eps),
+    eps in {+-1e-2, +-1e-4, +-1e-6, 0}, the tilt split between roll and pitch at random, every heading; half of them in the
+    map's interior, half 2 m inside a border (unless `interior_only`).  Whatever path takes a particle, its rays are the
+    oracle's; every particle clearly past the bound (c2z more than 1e-5 below it) is handed over, and in the interior no
+    more are handed over than are not clearly inside it."""
+    if case == 'grid_cap_twisted':
+        case = 'grid_twisted'
+    kind, z, origin, res, verts, tris, slope, cmin = _bound_map(case)
+    tan_cap = np.tan(np.radians(35.0))
+    binds = 'slope' if (0.45 if kind == 'grid' else 0.8) / slope < tan_cap else 'cap'
+    print('%s: slope_max %.4f, c2z_min %.7f (tilt limit %.2f deg, set by the %s)' % (case, slope, cmin, np.degrees(np.arccos(cmin)), binds))
+    if case in ('grid_slope', 'mesh_slope'):
+        assert binds == 'slope' and abs(slope - (1.0 if kind == 'grid' else 2.0)) < 0.15
+    elif case in ('mesh_cap', 'tin_cap'):
+        assert binds == 'cap'
+    else:
+        assert binds == 'slope'   # (rough: the grid rule binds near 0.45 / slope)
+    per = 96
+    rs = np.random.RandomState(71)
+    eps = np.repeat(_EPS, per)
+    n = eps.size
+    target = cmin * (1.0 + eps)
+    # c2z = cos(pitch) cos(roll) for an untilted frame and no mount rotation: split the tilt between the two
+    tilt = np.arccos(np.minimum(target, 1.0))
+    share = rs.uniform(0.0, 1.0, n)
+    roll = rs.choice([-1.0, 1.0], n) * tilt * share
+    pitch = rs.choice([-1.0, 1.0], n) * np.arccos(np.minimum(target / np.cos(roll), 1.0))
+    soa = np.zeros((6, n))
+    soa[3], soa[4], soa[5] = roll, pitch, rs.uniform(-np.pi, np.pi, n)
+    soa[2] = -rs.uniform(1.0, 4.0, n)
+    border = np.zeros(n, bool) if interior_only else (np.arange(n) % 2 == 1)
+    soa[0] = rs.uniform(-30.0, 30.0, n)
+    soa[1] = rs.uniform(-30.0, 30.0, n)
+    lo, hi = np.array(origin), np.array(origin) + res * (np.array(z.shape) - 1)
+    side = rs.randint(0, 4, n)
+    for k in np.nonzero(border)[0]:
+        ax, end = side[k] // 2, side[k] % 2
+        soa[ax, k] = lo[ax] + 2.0 if end == 0 else hi[ax] - 2.0
+    c2z = _c2z(soa)
+    assert np.abs(c2z - target).max() <= 1e-12
+    past = c2z < cmin - 1e-5
+    not_inside = c2z < cmin + 1e-5
+    # the 0.01 rad beams of the lowest swath reach 60 m: the interior fans stay 90 m inside every border
+    ba = synth.beam_angles(128, 1.3 if case == 'grid_twisted' else 1.0)   # (twisted patches: beams out to 74 degrees)
+    r_max = 60.0
+    e = eng.Engine(n, rng_mode=eng.RNG_REPLAY)
+    e.set_particles(soa)
+    if kind == 'grid':
+        e.set_map_grid(z, origin, res)
+        omap = orc.Grid(z, origin, res)
+    else:
+        e.set_map_mesh(verts, tris)
+        omap = orc.Mesh(verts, tris)
+    got = e.mbes_expected(0, n, ba, r_max)
+    path, handed, _ = e.mbes_last_path()
+    assert path == 1
+    _, ref = orc.mbes_update(soa, np.identity(4), [0] * 6, omap, ba, None, 0.2, r_max)
+    err = np.abs(got - ref)
+    bad = int((err > 1e-3).sum())
+    print('%s%s: handed over %d of %d; clearly past the bound %d, not clearly inside %d; max err %.2e, rays off %d/%d' % (
+        case, ' (interior)' if interior_only else '', handed, n, int(past.sum()), int(not_inside.sum()), err.max(), bad, err.size))
+    assert bad <= max(3, err.size // 4000)
+    outliers_explained(orc, omap, soa, ba, got, ref, r_max, label='straddle ' + case)
+    assert handed >= past.sum()
+    if interior_only:
+        # besides the tilt test, an interior fan is declined only for rounding at a cell / triangle (mcl_sweep.h SWEEP_FAIL
+        # 6, 7, 8: the plane grazes a node or an edge) -- isolated particles; the slack is 1 %
+        assert handed <= not_inside.sum() + n // 100
+    # the same cloud through the update: log-weights against the oracle
+    ranges = (ref[np.argmax((ref < r_max).sum(axis=1))] + 0.1 * rs.randn(ba.size)).astype(np.float32)
+    ranges[ranges >= r_max] = 0.0
+    e.update_mbes(ranges, ba, 0.2, r_max)
+    assert e.mbes_last_path()[0] == 1
+    lw = e.get_log_weights()
+    lw_ref, _ = orc.mbes_update(soa, np.identity(4), [0] * 6, omap, ba, ranges, 0.2, r_max)
+    d = np.abs(lw - lw_ref)
+    okm = (d <= 1e-2) | (d <= 2e-4 * np.abs(lw_ref))
+    assert (~okm).sum() <= (2 if bad else 0) + n // 100
+    lw_outliers_explained(orc, omap, soa, ba, ranges, 0.2, r_max, lw, lw_ref, label='straddle ' + case)
+    e.close()
+
+
+# ------------------------------------------------------------------ c. one steep cell
+@pytest.mark.parametrize('kind', ['grid', 'mesh', 'tin', 'tin_holes'])
+def test_one_steep_cell_hands_the_whole_diving_cloud_over(kind, eng, orc):
+    """Gentle terrain with one spike of slope >= 5 anywhere on the map: the bound falls below 10 degrees, and a cloud diving
+    at 12 degrees is handed over whole -- every ray still the oracle's.  On a TIN with holes the hand-overs go to the fan
+    slice first, the rest to the ray traversal: the two account for every particle."""
+    origin, res = (-90.0, -80.0), 1.0
+    z = synth.bathymetry_grid(200, 180, res, origin, seed=81, depth=-22.0, swell=1.0, fbm_amp=0.2)
+    z[150, 40] += 12.0                       # far from the cloud: only the bound sees it
+    if kind == 'grid':
+        slope = _slope_grid(z, res)
+    elif kind == 'mesh':
+        verts, tris = synth.mesh_from_grid(z, res, origin)
+        slope = _slope_lattice(z, res)
+    else:
+        verts, tris = synth.mesh_tin(z, res, origin, seed=82)
+        if kind == 'tin_holes':
+            c = verts[tris.astype(np.int64)].mean(axis=1)
+            gone = np.zeros(len(tris), bool)
+            for p in ((-3.0, 8.0), (6.0, -9.0), (-20.0, -5.0)):
+                gone |= np.hypot(c[:, 0] - p[0], c[:, 1] - p[1]) < 1.5
+            tris = np.ascontiguousarray(tris[~gone])
+        slope = _slope_tin(verts, tris)
+    assert slope >= 5.0, slope
+    cmin = _c2z_min(slope, kind == 'grid')
+    n, B = 512, 128
+    rs = np.random.RandomState(83)
+    soa = np.zeros((6, n))
+    soa[0], soa[1], soa[2] = 3.0 * rs.randn(n), 3.0 * rs.randn(n), -2.0 + 0.2 * rs.randn(n)
+    soa[3], soa[4], soa[5] = 0.01 * rs.randn(n), np.radians(12.0) + 0.01 * rs.randn(n), rs.uniform(-np.pi, np.pi, n)
+    assert (_c2z(soa) < cmin - 1e-5).all()
+    ba = synth.beam_angles(B)
+    e = eng.Engine(n, rng_mode=eng.RNG_REPLAY)
+    e.set_particles(soa)
+    if kind == 'grid':
+        e.set_map_grid(z, origin, res)
+        omap = orc.Grid(z, origin, res)
+    else:
+        e.set_map_mesh(verts, tris)
+        omap = orc.Mesh(verts, tris)
+    got = e.mbes_expected(0, n, ba, 80.0)
+    path, handed, _ = e.mbes_last_path()
+    print('%s, one spike (slope_max %.2f, tilt limit %.2f deg): handed over %d of %d' % (kind, slope, np.degrees(np.arccos(cmin)), handed, n))
+    assert path == 1 and handed == n
+    _, ref = orc.mbes_update(soa, np.identity(4), [0] * 6, omap, ba, None, 0.2, 80.0)
+    err = np.abs(got - ref)
+    bad = int((err > 1e-3).sum())
+    assert bad <= max(3, err.size // 4000), (bad, err.max())
+    outliers_explained(orc, omap, soa, ba, got, ref, 80.0, label='spike ' + kind)
+    ranges = (ref[0] + 0.1 * rs.randn(B)).astype(np.float32)
+    ranges[ranges >= 80.0] = 0.0
+    e.update_mbes(ranges, ba, 0.2, 80.0)
+    path, handed, _ = e.mbes_last_path()
+    assert path == 1 and handed == n
+    if kind == 'tin_holes':
+        by_slice, by_trav = e.mbes_last_handover()
+        print('tin_holes: the fan slice cast %d, the ray traversal %d' % (by_slice, by_trav))
+        assert by_slice + by_trav == n
+    lw_ref, _ = orc.mbes_update(soa, np.identity(4), [0] * 6, omap, ba, ranges, 0.2, 80.0)
+    d = np.abs(e.get_log_weights() - lw_ref)
+    print('spike %s: max |dlw| %.3e' % (kind, d.max()))
+    okm = (d <= 1e-2) | (d <= 2e-4 * np.abs(lw_ref))
+    assert (~okm).sum() <= (2 if bad else 0) + n // 100
+    lw_outliers_explained(orc, omap, soa, ba, ranges, 0.2, 80.0, e.get_log_weights(), lw_ref, label='spike ' + kind)
+    e.close()
+
+
+# ------------------------------------------------------------------ d. the clamp proof under a dive (fused step)
+_CLAMP_CHILD = r'''
+import os, sys, numpy as np
+sys.path.insert(0, %(root)r)
+from smarc_navigation_amd import engine as eng
+from oracle import oracle as orc
+cases = np.load(sys.argv[1], allow_pickle=False)
+out = {}
+for k in range(int(cases['count'])):
+    c = {key[len('c%%d_' %% k):]: cases[key] for key in cases.files if key.startswith('c%%d_' %% k)}
+    n = 16384
+    cov = dict(seed=3, init_cov=[1.0, 1.0, 0, 0, 0, 0.01], process_cov=[1e-4, 1e-4, 0, 0, 0, 1e-6], resample_cov=[1e-3, 1e-3, 0, 0, 0, 1e-5])
+    soa = None
+    for fused in (True, False):
+        e = eng.Engine(n, **cov)
+        if c['grid_z'].size:
+            e.set_map_grid(c['grid_z'], tuple(c['origin']), 1.0)
+        else:
+            e.set_map_mesh(c['verts'], c['tris'])
+        e.init_particles()
+        if fused:
+            os.write(2, b'@@case %%d\n' %% k)
+            e.step_mbes([1.0, 0.0, 0.0], 0.05, c['q'], float(c['z']), 0.02, c['ranges'], c['ba'], 2.0, float(c['r_max']), c['off'])
+            e.sync()
+            os.write(2, b'@@end %%d\n' %% k)
+            out['lw_%%d' %% k] = e.get_log_weights()
+            out['path_%%d' %% k] = np.array(e.mbes_last_path())
+        else:   # the same predict through the plain call: the cloud the fused step weighed
+            e.predict([1.0, 0.0, 0.0], 0.05, c['q'], float(c['z']), 0.02)
+            out['soa_%%d' %% k] = e.get_particles()
+        e.close()
+np.savez(sys.argv[2], **out)
+'''
+
+
+def _clamp_flip(z_lowest, oz, R, ba, ranges):
+    """The distance at which the fused step's proof flips: a valid beam with downward direction dz travels at most
+    (z_lowest - oz) / dz before it is below every point of the map; the proof holds iff that is inside r_max (1 - 1e-3)
+    for every valid beam (and no valid beam is horizontal or rising)"""
+    a = ba.astype(np.float64)
+    dz = np.sin(a) * R[2, 1] - np.cos(a) * R[2, 2]
+    valid = ranges > 0
+    assert (dz[valid] < -1e-3).all()
+    return float(((z_lowest - oz) / dz[valid]).max())
+
+
+def test_clamp_proof_under_a_dive(orc, tmp_path):
+    """The fused step proves from the cloud's common roll and pitch (straight after the predict) that no beam can travel
+    beyond r_max, and the assembly merge loop then leaves the clamp out (mcl_host_update.h: sweep_noclamp).  Odometry at a
+    constant pitch of 15 degrees, with and without a mounting pitch, on a grid, a lattice mesh and a TIN; r_max 1 % above
+    and 1 % below the distance where the proof flips (from the fp64 geometry: the map's lowest point, the outermost valid
+    beam).  The verdict is the one the geometry predicts, the log-weights equal a run with the proof switched off
+    (MCL_SWEEP_NOCLAMP=0) bit for bit, and the live particles equal the oracle's."""
+    origin = (-90.0, -80.0)
+    z = synth.bathymetry_grid(200, 180, 1.0, origin, seed=41)
+    maps = {'grid': (z, None, None), 'mesh': (None,) + synth.mesh_from_grid(z, 1.0, origin),
+            'tin': (None,) + synth.mesh_tin(z, 1.0, origin, seed=42)}
+    B = 128
+    ba = synth.beam_angles(B)
+    pitch, yaw, zd = np.radians(15.0), 0.2, -2.0
+    q = orc.quat_from_euler(0.0, pitch, yaw)
+    ranges = (22.0 / np.cos(ba)).astype(np.float32)
+    ranges[::9] = 0.0
+    ranges[:2] = 0.0            # (the outermost port beams carry no range: the proof looks at the valid ones only)
+    cases, meta = {}, []
+    for name, (gz, verts, tris) in maps.items():
+        z_lowest = float(gz.min()) if gz is not None else float(verts[:, 2].min())
+        for mount in (0.0, 0.1):
+            off = np.array([0.2, 0.0, -0.1, 0.0, mount, 0.0])
+            R = _rot(0.0, pitch, yaw) @ _rot(*off[3:])
+            oz = zd + (_rot(0.0, pitch, yaw) @ off[:3])[2]
+            flip = _clamp_flip(z_lowest, oz, R, ba, ranges)
+            for above in (True, False):
+                k = len(meta)
+                r_max = flip / (1.0 - 1e-3) * (1.01 if above else 0.99)
+                meta.append((name, mount, above, r_max, flip))
+                pre = 'c%d_' % k
+                cases[pre + 'grid_z'] = gz if gz is not None else np.zeros(0, np.float32)
+                cases[pre + 'verts'] = verts if verts is not None else np.zeros((0, 3), np.float32)
+                cases[pre + 'tris'] = tris if tris is not None else np.zeros((0, 3), np.uint32)
+                cases[pre + 'origin'] = np.array(origin)
+                cases[pre + 'q'] = np.asarray(q, float)
+                cases[pre + 'z'] = np.array(zd)
+                cases[pre + 'ranges'] = ranges
+                cases[pre + 'ba'] = ba
+                cases[pre + 'r_max'] = np.array(r_max)
+                cases[pre + 'off'] = off
+    cases['count'] = np.array(len(meta))
+    cfile = str(tmp_path / 'cases.npz')
+    np.savez(cfile, **cases)
+    child = str(tmp_path / 'child.py')
+    with open(child, 'w') as f:
+        f.write(_CLAMP_CHILD % {'root': ROOT})
+    res, verdicts = {}, {}
+    for mode in ('default', 'noclamp0'):
+        env = dict(os.environ)
+        env['MCL_SWEEP'] = '1'
+        env['MCL_DEBUG_WORK'] = '1'
+        if mode == 'noclamp0':
+            env['MCL_SWEEP_NOCLAMP'] = '0'
+        out = str(tmp_path / (mode + '.npz'))
+        p = subprocess.run([sys.executable, child, cfile, out], env=env, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        res[mode] = np.load(out)
+        for k in range(len(meta)):
+            seg = p.stderr.split('@@case %d\n' % k)[1].split('@@end %d\n' % k)[0]
+            assert '[mbes] sweep handed over' in seg, seg
+            verdicts[mode, k] = 'proved idle: skipped' in seg
+            assert verdicts[mode, k] != ('r_max kept' in seg), seg
+    for k, (name, mount, above, r_max, flip) in enumerate(meta):
+        label = 'clamp proof %s, mount pitch %.1f, r_max %.2f (%s the flip at %.2f m)' % (name, mount, r_max, 'above' if above else 'below', flip)
+        print('%s: %s; handed over %d' % (label, 'proved idle' if verdicts['default', k] else 'kept', int(res['default']['path_%d' % k][1])))
+        assert verdicts['default', k] == above, label
+        assert not verdicts['noclamp0', k], label
+        assert int(res['default']['path_%d' % k][0]) == 1
+        lw, lw0 = res['default']['lw_%d' % k], res['noclamp0']['lw_%d' % k]
+        assert np.array_equal(lw, lw0), '%s: %d log-weights differ from the clamped run' % (label, int((lw != lw0).sum()))
+        soa = res['default']['soa_%d' % k]
+        assert np.allclose(soa[4], pitch, atol=1e-12) and np.allclose(soa[3], 0.0, atol=1e-12)
+        pick = live_picks(lw, 512, seed=k)
+        sub = np.ascontiguousarray(soa[:, pick])
+        gz, verts, tris = maps[name]
+        omap = orc.Grid(gz, origin, 1.0) if gz is not None else orc.Mesh(verts, tris)
+        off = list(cases['c%d_off' % k])
+        lw_ref, _ = orc.mbes_update(sub, np.identity(4), off, omap, ba, ranges, 2.0, r_max)
+        n_live, _, _ = live_particle_contract(orc, omap, sub, ba, ranges, 2.0, r_max, lw[pick], lw_ref, float(lw.max()), off=off, label=label)
+        assert n_live >= 16

@@ -25,6 +25,7 @@ _CHILD = r'''
 import sys, numpy as np
 sys.path.insert(0, %(root)r)
 from smarc_navigation_amd import engine as eng, synth
+from oracle import oracle as orc
 out = {}
 origin = (-64.0, -354.0)
 z = synth.bathymetry_grid(708, 708, 1.0, origin, seed=3)
@@ -53,6 +54,30 @@ for kind in ('mesh', 'tin', 'grid'):
         out['%%s_%%d_%%g_%%d' %% (kind, n, spread, B)] = e.get_log_weights()
         out['path_%%s_%%d' %% (kind, n)] = np.array(path)
         e.close()
+    # a diving vehicle: the whole cloud at one pitch of 0.35 rad and roll of 0.1 (every particle the odometry's attitude),
+    # collapsed (the lanes of a wave at the same beams) and wide
+    for n, spread, B in ((131072, 0.05, 512), (65536, 30.0, 301)):
+        rs = np.random.RandomState(4)
+        soa = rs.randn(6, n) * np.array([spread, spread, 0.3, 0.0, 0.0, 1.0])[:, None]
+        soa[0] += 100.0
+        soa[2] -= 5.0
+        soa[3] = 0.1
+        soa[4] = 0.35
+        e = eng.Engine(n, rng_mode=eng.RNG_REPLAY)
+        if kind == 'grid':
+            e.set_map_grid(z, origin, 1.0)
+        else:
+            e.set_map_mesh(verts, tris)
+        e.set_particles(soa)
+        ba = synth.beam_angles(B)
+        ranges = (25.0 / np.cos(ba) + 0.1 * rs.randn(B)).astype(np.float32)
+        ranges[::9] = 0.0
+        e.update_mbes(ranges, ba, 0.2, 100.0)
+        path = e.mbes_last_path()
+        assert path[0] == 1, path
+        out['dive_%%s_%%d_%%g_%%d' %% (kind, n, spread, B)] = e.get_log_weights()
+        out['path_dive_%%s_%%d' %% (kind, n)] = np.array(path)
+        e.close()
     # fused steps: straight after a predict the library can PROVE that no beam reaches the seabed beyond r_max and the
     # assembly loop leaves the clamp out (mcl_host_update.h: sweep_noclamp); the C++ loop always clamps
     # (r_max 100 m: every beam reaches the map's lowest point well inside it; 44 m: the outer beams do not -- the proof
@@ -77,6 +102,37 @@ for kind in ('mesh', 'tin', 'grid'):
         assert e.mbes_last_path()[0] == 1
         out['steps_%%s_%%g' %% (kind, r_max)] = e.get_particles()
         out['hist_%%s_%%g' %% (kind, r_max)] = e.mean_history(12)
+        e.close()
+    # ... and on an odometry stream at a constant pitch of 15 degrees, r_max 2 %% above the distance where the clamp proof
+    # flips on every step (skipped) and 2 %% below it on every step (kept): the lowest map point seen along the outermost
+    # valid beam of the pitched fan, from the odometry's depth
+    pitch = 0.2618
+    q = np.array([orc.quat_from_euler(stream['rpy'][k][0], pitch, stream['rpy'][k][2]) for k in range(12)])
+    ranges0 = np.minimum(20.0 / np.cos(ba), 1e3).astype(np.float32)
+    ranges0[5::17] = 0.0
+    a = ba[ranges0 > 0].astype(np.float64)
+    zlow = float(z.min() if kind != 'tin' else verts[:, 2].min())
+    flips = []
+    for k in range(12):
+        roll = stream['rpy'][k][0]
+        dz = np.cos(pitch) * (np.sin(a) * np.sin(roll) - np.cos(a) * np.cos(roll))
+        flips.append((zlow - stream['z'][k]) / dz.max() / (1.0 - 1e-3))
+    for tag, r_max in (('above', 1.02 * max(flips)), ('below', 0.98 * min(flips))):
+        e = eng.Engine(n, seed=5, init_cov=[0.5, 0.5, 0, 0, 0, 0.01], process_cov=[1e-3, 1e-3, 0, 0, 0, 1e-5],
+                       resample_cov=[1e-3, 1e-3, 0, 0, 0, 1e-5])
+        if kind == 'grid':
+            e.set_map_grid(z, origin, 1.0)
+        else:
+            e.set_map_mesh(verts, tris)
+        e.init_particles()
+        rs = np.random.RandomState(12)
+        for k in range(12):
+            ranges = np.where(ranges0 > 0, np.minimum(ranges0 + 0.3 * rs.randn(B), r_max - 0.5), 0.0).astype(np.float32)
+            e.step_mbes(stream['v'][k], stream['wz'][k], q[k], stream['z'][k], stream['dt'], ranges, ba, 0.2, r_max)
+        e.sync()
+        assert e.mbes_last_path()[0] == 1
+        out['steps_dive_%%s_%%s' %% (kind, tag)] = e.get_particles()
+        out['hist_dive_%%s_%%s' %% (kind, tag)] = e.mean_history(12)
         e.close()
 np.savez(sys.argv[1], **out)
 '''
@@ -106,7 +162,7 @@ def test_assembly_merge_loop_equals_the_compilers_bit_for_bit(tmp_path):
         # the fused steps really ran without the clamp (and the set_particles clouds, whose depths differ, with it)
         assert 'proved idle: skipped' in p.stderr and 'r_max kept' in p.stderr, p.stderr[-2000:]
     keys = [k for k in res['asm'].files if not k.startswith('path_')]
-    assert len(keys) == 30
+    assert len(keys) == 48
     handed = 0
     for k in res['asm'].files:
         a, c = res['asm'][k], res['cxx'][k]
