@@ -96,7 +96,7 @@ typedef struct mcl_odom {
 enum mcl_kernel_id {
   MCL_K_PREDICT = 0,
   MCL_K_UPDATE_GPS = 1,
-  MCL_K_UPDATE_MBES = 2,
+  MCL_K_UPDATE_MBES = 2, /* also the DVL / altimeter range update (mcl_update_ranges: one launch) */
   MCL_K_NORMALISE = 3, /* max-reduce + exp + fixed-point quantise */
   MCL_K_SCAN = 4,      /* u64 prefix scan + offspring counts */
   MCL_K_RESAMPLE = 5,  /* lost-slot scan + reassign gather + noise */
@@ -183,6 +183,20 @@ int mcl_update_mbes(mcl_handle* h, const float* ranges, const float* beam_angles
 /* expected ranges of particles [first, first+count) x n_beams (host floats); parity/diagnostics */
 int mcl_mbes_expected(mcl_handle* h, int64_t first, int64_t count, const float* beam_angles,
                       int32_t n_beams, double r_max, const double sensor_offset[6], float* out);
+
+/* ---- DVL / altimeter ranges: n_beams (1..16) rays in ANY direction against the map set by mcl_set_map_*.
+ * dirs: n_beams x 3 floats in the SENSOR frame (normalised by the library; a zero or non-finite direction is
+ * MCL_ERR_INVALID); ranges[b] <= 0 or NaN = invalid beam (skipped); a ray without a hit inside r_max has expected range
+ * r_max; sensor_offset as in mcl_update_mbes (NULL = zeros).  Geometry of mcl_update_mbes with the beam direction given:
+ * Rs = Rm R(roll, pitch, yaw) Ro, origin m2o [x y z 1] + (Rm Rp) t_off, ray direction Rs dir_b.
+ *     lw_i (+)= -1/2 sum_b ((r_b - e_ib)/sigma)^2 - n_valid log(sigma sqrt(2 pi));
+ * accumulate != 0 adds onto the log-likelihood an earlier update left (MBES ping, landmarks), in fp64.  Precision contract
+ * of mcl_update_mbes.  Timed under MCL_K_UPDATE_MBES. */
+int mcl_update_ranges(mcl_handle* h, const float* ranges, const float* dirs, int32_t n_beams, double sigma,
+                      double r_max, const double sensor_offset[6], int32_t accumulate);
+/* expected ranges of particles [first, first+count) x n_beams (host floats); parity/diagnostics */
+int mcl_ranges_expected(mcl_handle* h, int64_t first, int64_t count, const float* dirs, int32_t n_beams,
+                        double r_max, const double sensor_offset[6], float* out);
 
 /* ---- landmark update with k-nearest-neighbour data association (BASELINE config 5; nearest
  * reference analogues: auv_ekf_localization/src/ekf_localization.cpp:479-524 max-likelihood

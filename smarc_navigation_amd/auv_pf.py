@@ -66,6 +66,12 @@ DEFAULT_PARAMS = {
     'landmark_map_file': '', 'rocks_depth': float('inf'), 'lm_detect_topic': '/landmarks_detected',
     'landmark_std': 0.3, 'landmark_k': 1, 'landmark_gate': 11.345, 'landmark_sync_tol': 1e-3, 'landmark_max_age': 0.5,
     'landmark_late': 'update',
+    # DVL bottom range (terrain-aided navigation against the bathymetric map): smarc_msgs/DVL on `dvl_topic` (the
+    # reference's /sam/core/dvl, sam_dead_reckoning/scripts/dr_node.py:23,89; '' = not subscribed).  Its `altitude` is
+    # one range along the DVL frame's -z axis; the frame sits at `dvl_sensor_offset` in base_frame.  Each altitude is a
+    # measurement update of its own followed by the resampling, like a GPS fix.
+    'dvl_topic': '', 'dvl_altitude_std': 0.2, 'dvl_range_max': 60.0,
+    'dvl_sensor_offset': '[0.0, 0.0, 0.0, 0.0, 0.0, 0.0]',
 }
 
 
@@ -254,6 +260,8 @@ class auv_pf(object):
         self.has_map = False
         self.mbes_range_max = float(p['mbes_range_max'])
         self.mbes_points_frame = p['mbes_points_frame']
+        self.dvl_altitude_std, self.dvl_range_max = float(p['dvl_altitude_std']), float(p['dvl_range_max'])
+        self.dvl_sensor_offset = parse_cov_string(p['dvl_sensor_offset'])
         for key in ('map_grid_file', 'map_mesh_file'):   # the node's own map parameters
             if p[key]:
                 self.load_map(p[key])
@@ -432,6 +440,20 @@ class auv_pf(object):
             self.particles.update_mbes(np.asarray(scan.ranges, dtype=np.float32), angles.astype(np.float32),
                                        self.mbes_std, float(scan.range_max), self.mbes_sensor_offset)
             self._accumulate_pending_detections(self._stamp_of(scan))
+            self.resample(self.particles)
+
+    # ---- DVL bottom range
+    def dvl_cb(self, msg):
+        """smarc_msgs/DVL: the altitude as one range along the DVL frame's -z axis against the map, then the resampling.
+        An altitude that is not finite and positive (no bottom lock) is ignored."""
+        alt = float(msg.altitude)
+        if not (math.isfinite(alt) and alt > 0.0):
+            return
+        with self.lock:
+            if not (self.old_time and self.has_map):
+                return
+            self.particles.update_ranges([alt], [[0.0, 0.0, -1.0]], self.dvl_altitude_std, self.dvl_range_max,
+                                         self.dvl_sensor_offset)
             self.resample(self.particles)
 
     # ---- publishing, auv_pf.py:218-285

@@ -660,6 +660,133 @@ int mcl_update_landmarks_assign(mcl_handle* h, const double* det_xyz, int32_t n_
   return MCL_OK;
 }
 
+namespace {
+// DVL / altimeter ranges (mcl_ranges.h): the beam table -- directions normalised in fp64, then rounded -- and the map go
+// into the kernel's argument block; one launch over the particles [first, first + count).
+int ranges_launch(mcl_handle* h, const float* ranges, const float* dirs, int B, double sigma, double r_max,
+                  const double sensor_offset[6], bool accumulate, double* lw_out, float* exp_out, long long first,
+                  long long count) {
+  static const double zero6[6] = {0, 0, 0, 0, 0, 0};
+  const double* so = sensor_offset ? sensor_offset : zero6;
+  RangesArgs ra;
+  memset(&ra, 0, sizeof ra);
+  for (int b = 0; b < B; ++b) {
+    const double x = dirs[3 * b], y = dirs[3 * b + 1], z = dirs[3 * b + 2];
+    const double nrm = std::sqrt(x * x + y * y + z * z);
+    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(h, MCL_ERR_INVALID, "update_ranges: a beam direction is zero or not finite");
+    ra.beam[b] = make_float4((float)(x / nrm), (float)(y / nrm), (float)(z / nrm), ranges ? ranges[b] : 0.f);
+  }
+  RET_IF(materialise_uniform(h));
+  MbesArgs& a = ra.m;
+  for (int c = 0; c < 6; ++c) a.st[c] = h->state[h->cur] + (size_t)c * h->n;
+  a.n = h->n;
+  for (int k = 0; k < 12; ++k) a.m2o[k] = h->cfg.m2o[k];
+  for (int k = 0; k < 3; ++k) a.off_t[k] = so[k];
+  rot_rpy(so[3], so[4], so[5], a.off_R);
+  a.r_max = (float)r_max;
+  int map = 0;   // the map fields k_mbes_cast reads, as launch_mbes fills them
+  if (h->map_kind == 0) {
+    a.grid = h->grid;
+    a.grid_pad = h->grid_pad;
+    a.nyp = h->gny + 2;
+    a.nx = h->gnx;
+    a.ny = h->gny;
+    a.ox = h->gox;
+    a.oy = h->goy;
+    a.inv_res = 1.0 / h->gres;
+    a.res = (float)h->gres;
+    a.zmin_map = h->gzmin;
+    a.zmax_map = h->gzmax;
+  } else {
+    const MeshDev* m = h->mesh;
+    a.mesh = mesh_args(m);
+    a.grid = m->heights;
+    a.grid_pad = m->heights_pad;
+    a.nyp = m->gy + 3;
+    a.nx = m->gx + 1;
+    a.ny = m->gy + 1;
+    a.ox = m->x0;
+    a.oy = m->y0;
+    a.inv_res = 1.0 / m->cs;
+    a.res = (float)m->cs;
+    a.zmin_map = m->zmin;
+    a.zmax_map = m->zmax;
+    a.diag_mode = m->diag_mode;
+    map = (m->heights && m->heights_pad && !h->force_general_mesh) ? 2 : 1;   // a triangulated regular grid: its node heights
+  }
+  int lg = 0;
+  while ((1 << lg) < B) ++lg;
+  ra.i0 = first;
+  ra.i1 = first + count;
+  ra.n_beams = B;
+  ra.lg_bp = lg;
+  ra.accumulate = accumulate ? 1 : 0;
+  ra.sigma = sigma;
+  ra.lognorm = std::log(sigma * std::sqrt(2.0 * MCL_PI));
+  ra.lw = lw_out;
+  ra.exp_out = exp_out;
+  const long long per_block = RANGES_THREADS >> lg;
+  const unsigned grid = (unsigned)std::min<long long>((count + per_block - 1) / per_block, 1ll << 16);
+  const bool expect = exp_out != nullptr;
+  if (!expect) t_begin(h, MCL_K_UPDATE_MBES);
+#define LAUNCH_RANGES(MAPV)                                                              \
+  do {                                                                                   \
+    if (expect)                                                                          \
+      k_ranges_update<MAPV, true><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);           \
+    else                                                                                 \
+      k_ranges_update<MAPV, false><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);          \
+  } while (0)
+  if (map == 0)
+    LAUNCH_RANGES(0);
+  else if (map == 2)
+    LAUNCH_RANGES(2);
+  else
+    LAUNCH_RANGES(1);
+#undef LAUNCH_RANGES
+  if (!expect) t_end(h);
+  HIPCHK(h, hipGetLastError());
+  return MCL_OK;
+}
+}  // namespace
+
+int mcl_update_ranges(mcl_handle* h, const float* ranges, const float* dirs, int32_t n_beams, double sigma, double r_max,
+                      const double sensor_offset[6], int32_t accumulate) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!ranges || !dirs || n_beams < 1 || n_beams > RANGES_MAX_BEAMS || !(sigma > 0.0) || !(r_max > 0.0))
+    return fail(h, MCL_ERR_INVALID, "update_ranges: bad argument (1 <= n_beams <= 16, sigma > 0, r_max > 0)");
+  RET_IF(set_device(h));
+  if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "update_ranges: no map (call mcl_set_map_grid/mesh first)");
+  if (accumulate && !h->have_lw) return fail(h, MCL_ERR_STATE, "update_ranges: nothing to accumulate onto");
+  RET_IF(ranges_launch(h, ranges, dirs, n_beams, sigma, r_max, sensor_offset, accumulate != 0, h->lw, nullptr, 0, h->n));
+  if (!accumulate) h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
+  h->have_lw = true;
+  h->max_valid = false;
+  h->residual_k = -1;
+  return MCL_OK;
+}
+
+int mcl_ranges_expected(mcl_handle* h, int64_t first, int64_t count, const float* dirs, int32_t n_beams, double r_max,
+                        const double sensor_offset[6], float* out) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!dirs || !out || n_beams < 1 || n_beams > RANGES_MAX_BEAMS || !(r_max > 0.0) || first < 0 || count < 1 ||
+      first + count > h->n)
+    return fail(h, MCL_ERR_INVALID, "ranges_expected: bad argument");
+  RET_IF(set_device(h));
+  if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "ranges_expected: no map (call mcl_set_map_grid/mesh first)");
+  const size_t need = (size_t)count * (size_t)n_beams;
+  if (need > h->exp_cap) {
+    if (h->exp_dev) (void)hipFree(h->exp_dev);
+    h->exp_dev = nullptr;
+    h->exp_cap = 0;
+    HIPCHK(h, hipMalloc(&h->exp_dev, sizeof(float) * need));
+    h->exp_cap = need;
+  }
+  RET_IF(ranges_launch(h, nullptr, dirs, n_beams, 1.0, r_max, sensor_offset, false, nullptr, h->exp_dev, first, count));
+  HIPCHK(h, hipMemcpyAsync(out, h->exp_dev, sizeof(float) * need, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MCL_OK;
+}
+
 int mcl_resample(mcl_handle* h, const double* uniforms, int64_t n_uniforms, const double* replay_normals) {
   if (!h) return MCL_ERR_INVALID;
   if (h->world > 1 && !h->comm)

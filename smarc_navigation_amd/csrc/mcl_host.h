@@ -29,6 +29,7 @@
 #include "mcl_resample.h"
 #include "mcl_resample_alt.h"
 #include "mcl_landmarks.h"
+#include "mcl_ranges.h"
 
 #define MEAN_RING 4096
 #define RING_STRIDE 20  // doubles per mean/cov result: 16 payload + [16] format tag

@@ -109,6 +109,23 @@ class Engine(object):
                                             _ptr(so), _ptr(out)))
         return out
 
+    def update_ranges(self, ranges, dirs, sigma, r_max, sensor_offset=None, accumulate=False):
+        """DVL / altimeter ranges: beam b looks along dirs[b] (sensor frame, any length > 0); ranges <= 0 or NaN are
+        skipped; accumulate=True adds onto the log-likelihood an earlier update left (mcl_update_ranges)."""
+        r, d, so = _f32(ranges).reshape(-1), _f32(dirs).reshape(-1, 3), _f64(sensor_offset)
+        if r.size != d.shape[0]:
+            raise ValueError('update_ranges: %d ranges for %d directions' % (r.size, d.shape[0]))
+        self._ck(self.lib.mcl_update_ranges(self.h, _ptr(r), _ptr(d), d.shape[0], float(sigma), float(r_max), _ptr(so),
+                                            1 if accumulate else 0))
+
+    def ranges_expected(self, first, count, dirs, r_max, sensor_offset=None):
+        """expected ranges (count, n_beams) of particles [first, first + count) along dirs (mcl_ranges_expected)"""
+        d, so = _f32(dirs).reshape(-1, 3), _f64(sensor_offset)
+        out = np.zeros((int(count), d.shape[0]), np.float32)
+        self._ck(self.lib.mcl_ranges_expected(self.h, int(first), int(count), _ptr(d), d.shape[0], float(r_max), _ptr(so),
+                                              _ptr(out)))
+        return out
+
     def set_landmarks(self, xyz):
         a = _f64(xyz)
         self._ck(self.lib.mcl_set_landmarks(self.h, _ptr(a), a.shape[0]))

@@ -92,6 +92,16 @@ class LaserScan(object):
         self.range_max = range_max
 
 
+class DVL(object):
+    """smarc_msgs/DVL, the fields the filter reads: `altitude` (bottom range along the DVL's -z axis, m; <= 0 without
+    bottom lock) and the velocity the dead-reckoning integrator takes (sam_dead_reckoning/scripts/dr_node.py:89)."""
+
+    def __init__(self, altitude=0.0, velocity=None):
+        self.header = Header()
+        self.velocity = velocity if velocity is not None else Vector3()
+        self.altitude = altitude
+
+
 class PointField(object):
     """sensor_msgs/PointField: datatype 7 = FLOAT32, 8 = FLOAT64."""
     FLOAT32, FLOAT64 = 7, 8
