@@ -343,7 +343,9 @@ int mcl_update_mbes(mcl_handle* h, const float* ranges, const float* beam_angles
     return fail(h, MCL_ERR_INVALID, "update_mbes: bad argument");
   RET_IF(set_device(h));
   RET_IF(upload_beams(h, ranges, beam_angles, B));
-  RET_IF(launch_mbes(h, true, B, sigma, r_max, sensor_offset, h->lw, nullptr, 0, 0));
+  MbesPlan plan;
+  RET_IF(plan_mbes(h, B, sigma, r_max, sensor_offset, nullptr, plan));
+  RET_IF(run_mbes(h, plan, false));
   h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
   h->have_lw = true;
   h->residual_k = -1;
@@ -363,7 +365,10 @@ int mcl_mbes_expected(mcl_handle* h, int64_t first, int64_t count, const float* 
     HIPCHK(h, hipMalloc(&h->exp_dev, sizeof(float) * need));
     h->exp_cap = need;
   }
-  RET_IF(launch_mbes(h, false, B, 1.0, r_max, sensor_offset, nullptr, h->exp_dev, first, count));
+  const MbesExpect expect{h->exp_dev, first, count};
+  MbesPlan plan;
+  RET_IF(plan_mbes(h, B, 1.0, r_max, sensor_offset, &expect, plan));
+  RET_IF(run_mbes(h, plan, false));
   HIPCHK(h, hipMemcpyAsync(out, h->exp_dev, sizeof(float) * need, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MCL_OK;
@@ -666,8 +671,6 @@ namespace {
 int ranges_launch(mcl_handle* h, const float* ranges, const float* dirs, int B, double sigma, double r_max,
                   const double sensor_offset[6], bool accumulate, double* lw_out, float* exp_out, long long first,
                   long long count) {
-  static const double zero6[6] = {0, 0, 0, 0, 0, 0};
-  const double* so = sensor_offset ? sensor_offset : zero6;
   RangesArgs ra;
   memset(&ra, 0, sizeof ra);
   for (int b = 0; b < B; ++b) {
@@ -677,43 +680,9 @@ int ranges_launch(mcl_handle* h, const float* ranges, const float* dirs, int B, 
     ra.beam[b] = make_float4((float)(x / nrm), (float)(y / nrm), (float)(z / nrm), ranges ? ranges[b] : 0.f);
   }
   RET_IF(materialise_uniform(h));
-  MbesArgs& a = ra.m;
-  for (int c = 0; c < 6; ++c) a.st[c] = h->state[h->cur] + (size_t)c * h->n;
-  a.n = h->n;
-  for (int k = 0; k < 12; ++k) a.m2o[k] = h->cfg.m2o[k];
-  for (int k = 0; k < 3; ++k) a.off_t[k] = so[k];
-  rot_rpy(so[3], so[4], so[5], a.off_R);
-  a.r_max = (float)r_max;
-  int map = 0;   // the map fields k_mbes_cast reads, as launch_mbes fills them
-  if (h->map_kind == 0) {
-    a.grid = h->grid;
-    a.grid_pad = h->grid_pad;
-    a.nyp = h->gny + 2;
-    a.nx = h->gnx;
-    a.ny = h->gny;
-    a.ox = h->gox;
-    a.oy = h->goy;
-    a.inv_res = 1.0 / h->gres;
-    a.res = (float)h->gres;
-    a.zmin_map = h->gzmin;
-    a.zmax_map = h->gzmax;
-  } else {
-    const MeshDev* m = h->mesh;
-    a.mesh = mesh_args(m);
-    a.grid = m->heights;
-    a.grid_pad = m->heights_pad;
-    a.nyp = m->gy + 3;
-    a.nx = m->gx + 1;
-    a.ny = m->gy + 1;
-    a.ox = m->x0;
-    a.oy = m->y0;
-    a.inv_res = 1.0 / m->cs;
-    a.res = (float)m->cs;
-    a.zmin_map = m->zmin;
-    a.zmax_map = m->zmax;
-    a.diag_mode = m->diag_mode;
-    map = (m->heights && m->heights_pad && !h->force_general_mesh) ? 2 : 1;   // a triangulated regular grid: its node heights
-  }
+  fill_frames_and_map(h, sensor_offset, r_max, ra.m);
+  // the map walk: 0 the height grid, 2 the node heights of a triangulated regular grid, 1 triangle records
+  const int map = h->map_kind == 0 ? 0 : (structured_mesh(h) ? 2 : 1);
   int lg = 0;
   while ((1 << lg) < B) ++lg;
   ra.i0 = first;
@@ -983,14 +952,14 @@ int step_mbes_impl(mcl_handle* h, const mcl_odom* odom, double dt, const float* 
   // (the beam table first: the group classification in that kernel follows the two extreme beams)
   RET_IF(upload_beams(h, ranges, beam_angles, B));
   if (lm) RET_IF(landmarks_prepare(h, *lm, who, true));   // (after upload_beams: it forgets detections an earlier call left waiting)
-  MbesArgs pa;
-  RET_IF(launch_mbes(h, true, B, sigma, r_max, sensor_offset, h->lw, nullptr, 0, 0, false, &pa));
+  MbesPlan plan;
+  RET_IF(plan_mbes(h, B, sigma, r_max, sensor_offset, nullptr, plan));
   bool pose_done = false;
   const bool sys = h->cfg.resample_scheme == MCL_RESAMPLE_SYSTEMATIC || h->cfg.resample_scheme == MCL_RESAMPLE_NAIVE;
   // (systematic scheme: the gather of this call substitutes z, roll, pitch -- the predict kernel does not store them)
-  RET_IF(do_predict(h, odom, dt, nullptr, &pa, &pose_done, sys));
+  RET_IF(do_predict(h, odom, dt, nullptr, &plan.args, &pose_done, sys));
   int rc_u = h->fault_step ? fail(h, MCL_ERR_STATE, w + ": injected fault after predict") : start_state_gather(h);
-  if (rc_u == MCL_OK) rc_u = launch_mbes(h, true, B, sigma, r_max, sensor_offset, h->lw, nullptr, 0, 0, pose_done);
+  if (rc_u == MCL_OK) rc_u = run_mbes(h, plan, pose_done);
   if (rc_u == MCL_OK) {
     h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
     h->have_lw = true;
@@ -1050,12 +1019,12 @@ int group_step_mbes_impl(mcl_handle** shards, int32_t ns, const mcl_odom* odom, 
     mcl_handle* h = shards[s];
     // the same fused front half as mcl_step_mbes: predict writes the pose records, the sweep leaves max lw in the slots
     int rc = set_device(h);
-    MbesArgs pa;
-    if (rc == MCL_OK) rc = launch_mbes(h, true, B, sigma, r_max, sensor_offset, h->lw, nullptr, 0, 0, false, &pa);
+    MbesPlan plan;
+    if (rc == MCL_OK) rc = plan_mbes(h, B, sigma, r_max, sensor_offset, nullptr, plan);
     bool pose_done = false;
-    if (rc == MCL_OK) rc = do_predict(h, odom, dt, nullptr, &pa, &pose_done, true);
+    if (rc == MCL_OK) rc = do_predict(h, odom, dt, nullptr, &plan.args, &pose_done, true);
     if (rc == MCL_OK && h->fault_step) rc = fail(h, MCL_ERR_STATE, w + ": injected fault after predict");
-    if (rc == MCL_OK) rc = launch_mbes(h, true, B, sigma, r_max, sensor_offset, h->lw, nullptr, 0, 0, pose_done);
+    if (rc == MCL_OK) rc = run_mbes(h, plan, pose_done);
     if (rc == MCL_OK) {
       h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
       h->have_lw = true;

@@ -97,8 +97,6 @@ struct mcl_handle {
   // MBES
   float2* beam_sc = nullptr;
   float* ranges_dev = nullptr;
-  const float* ranges_ptr = nullptr;  // where the ranges of this update are on the device (ranges_dev, or beside the sweep's beam table)
-  bool ranges_pending = false;
   float* exp_dev = nullptr;
   MbesPose* pose_dev = nullptr;
   MbesGroup* mbes_groups = nullptr;  // one record per group of MBES_WAVES particles
@@ -133,8 +131,6 @@ struct mcl_handle {
   std::vector<float> ranges_host;   // last uploaded ranges (the sweep's beam table is built from them)
   bool sweep_angles_ok = false;     // ascending, finite, |a| <= 85 degrees
   int b_split = 0;
-  float4* sweep_beams = nullptr;   // the table of the CURRENT update: one of sweep_buf[2]
-  float* sweep_tail = nullptr;
   int sweep_cap = 0;
   // the table travels on its own stream into alternating device buffers, so the 12 KiB copy of ping k + 1 overlaps
   // the kernels of ping k instead of standing between two steps (4 us of copy + its launch gaps)
@@ -167,7 +163,7 @@ struct mcl_handle {
                                     // 524 288 x 512, -9 us at 65 536 x 256)
   int env_sweep = -1;               // MCL_SWEEP=0/1 forces the decision (tests, A/B)
   int env_nsub = 0;                 // MCL_SWEEP_NSUB=1/2/4 forces the lanes per particle side (A/B)
-  bool sweep_now = false;           // decided by the first launch_mbes call of an update
+  bool sweep_now = false;           // the fan sweep casts the current / last update (decided by plan_mbes)
   bool slice_now = false;           // ... the fan slice (mcl_slice.h) casts it
   bool handover_slice_now = false;  // the last update's sweep hand-overs went through the fan slice first (TIN with holes)
   int env_slice = -1;               // MCL_SLICE=0 keeps the ray traversal on triangle soups (tests, A/B)
@@ -176,7 +172,6 @@ struct mcl_handle {
   bool slice_attr_set = false;
   bool slice_group_ran = false;     // the last sliced update went through k_mbes_slice_group first
   size_t slice_attr_bytes = 0;
-  int sweep_nvalid = 0;
   float* grid = nullptr;
   float* grid_pad = nullptr;   // the same heights inside a one-node ring of NaNs (fan sweep: MbesArgs::grid_pad)
   int gnx = 0, gny = 0;

@@ -27,7 +27,7 @@
 #define RANGES_THREADS 256
 
 struct RangesArgs {
-  MbesArgs m;               // state (st, n), frames (m2o, off_t, off_R), the map (as launch_mbes fills it) and r_max
+  MbesArgs m;               // state (st, n), frames (m2o, off_t, off_R), the map (mcl_host_update.h: fill_frames_and_map) and r_max
   float4 beam[RANGES_MAX_BEAMS];  // x, y, z: unit direction in the sensor frame; w: measured range (<= 0 or NaN: invalid)
   long long i0, i1;         // the particles [i0, i1) this launch covers
   int n_beams, lg_bp;       // B, log2 of the lanes per particle (Bp >= B)

@@ -90,6 +90,11 @@ __device__ __forceinline__ void slice_beam(unsigned* slot, float T, float sec_b,
   __hip_atomic_fetch_min(slot, ok ? __float_as_uint(range) : 0x7f800000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// host: the dynamic LDS of k_mbes_slice for a ping of B beams (the layout at the top of the kernel)
+inline size_t slice_lds_bytes(int B) {
+  return ((size_t)B * (2 + SLICE_WAVES) + (size_t)SLICE_WAVES * (SLICE_LIST + 1)) * sizeof(float) + SLICE_LUT * sizeof(unsigned short);
+}
+
 template <bool EXPECT_ONLY>
 __global__ void __launch_bounds__(SLICE_THREADS, 4) k_mbes_slice(MbesArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char slice_lds[];
@@ -424,6 +429,16 @@ __global__ void __launch_bounds__(SLICE_THREADS, 4) k_mbes_slice(MbesArgs a) {
 #ifndef SLICE_G_DELTA
 #define SLICE_G_DELTA 1.5f    // a group is tight if its members' planes stay within this many cells of the reference's over the fan
 #endif
+// host: the dynamic LDS of k_mbes_slice_group for a ping of B beams (the layout at the top of the kernel)
+inline size_t slice_group_lds_bytes(int B) {
+  return (size_t)B * (3 + SLICE_G_WAVES) * sizeof(float) + (size_t)SLICE_G_TRIS * 9 * sizeof(float) +
+         SLICE_G_HASH * sizeof(unsigned) + SLICE_LUT * sizeof(unsigned short);
+}
+// does the group kernel's staging layout fit this ping's beam table?  The host decides BEFORE anything is asked of the
+// runtime (hipFuncSetAttribute itself fails beyond the device's limit, and the kernel's static
+// __shared__ -- member poses, reference plane, counters: a conservative 4 KiB -- counts against the same 160 KiB)
+inline bool slice_group_fits(int B) { return slice_group_lds_bytes(B) + 4096 <= (size_t)160 * 1024; }
+
 __global__ void __launch_bounds__(SLICE_G_THREADS, 6) k_mbes_slice_group(MbesArgs a) {   // (12 waves x 2 workgroups per CU = 6 waves per SIMD: <= 85 VGPRs, <= 80 KB of LDS)
   extern __shared__ __attribute__((aligned(16))) unsigned char slice_lds[];
   const int B = a.n_beams;

@@ -174,7 +174,7 @@ typedef float sweep_rec __attribute__((ext_vector_type(4)));   // {side-signed t
       "s_mov_b64 exec, %[sav]\n\t"                                                       \
       "s_waitcnt lgkmcnt(0)"
 // sel = side + 2 * noclamp (wave-uniform).  noclamp: the host has proved for this launch that no beam can reach the seabed
-// beyond r_max (mcl_host_update.h: launch_mbes -- depth, roll and pitch are the odometry's on every particle and the
+// beyond r_max (mcl_host_update.h: sweep_noclamp -- depth, roll and pitch are the odometry's on every particle and the
 // map has a lowest point), so max(residual, (z - r_max) w) is the residual: one instruction per beam less.
 #define SWEEP_MERGE_SIDE0(L1, L9, CLAMP) \
   SWEEP_MERGE_ASM_TEXT(" offset:48", " offset:64", " offset:80", " offset:96", "v_add_u32 %[bp], 32, %[bp]", "v_add_u32 %[bp], 16, %[bp]", L1, L9, CLAMP)
@@ -1405,6 +1405,10 @@ __device__ __forceinline__ double sweep_lane(const MbesArgs& a, long long j0, lo
 
 // (register budgets: the lattice walk 8 waves / SIMD (64 VGPRs), grids and TINs 6; the sub-fan kernel over a grid 5 -- it
 //  carries the conic AND the start ray's footprint test, and spilled 8 B per lane at 6: small clouds, latency-bound anyway)
+// host: the dynamic LDS of k_mbes_sweep for a ping of B beams (the table below: 4 spare records, two sentinels, one
+// record in front of either side; B tail sums and the 4 tangents)
+inline size_t sweep_lds_bytes(int B) { return (size_t)(B + 7) * sizeof(float4) + (size_t)(B + 4) * sizeof(float); }
+
 template <int SURF, bool EXPECT_ONLY, bool SUB = false>
 __global__ void __launch_bounds__(SUB ? 64 * SWEEP_MAX_WAVES : SWEEP_THREADS, SURF == 0 ? (SUB ? SWEEP_MIN_WAVES_GRID - 1 : SWEEP_MIN_WAVES_GRID) : (SURF == 6 && !SUB && !EXPECT_ONLY ? 8 : (SURF == 5 || SURF == 6 ? SWEEP_MIN_WAVES_TIN : SWEEP_MIN_WAVES))) k_mbes_sweep(MbesArgs a) {
 #ifdef SWEEP_TIMELINE
