@@ -257,10 +257,7 @@ int mcl_update_gps(mcl_handle* h, double gx_map, double gy_map) {
   k_gps_logw<<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, h->lw);
   t_end(h);
   HIPCHK(h, hipGetLastError());
-  h->weight_mode = MCL_WEIGHT_LINEAR_FLOOR;
-  h->have_lw = true;
-  h->max_valid = false;
-  h->residual_k = -1;
+  weights_written(h, MCL_WEIGHT_LINEAR_FLOOR, SLOTS_NONE);
   return MCL_OK;
 }
 
@@ -346,9 +343,7 @@ int mcl_update_mbes(mcl_handle* h, const float* ranges, const float* beam_angles
   MbesPlan plan;
   RET_IF(plan_mbes(h, B, sigma, r_max, sensor_offset, nullptr, plan));
   RET_IF(run_mbes(h, plan, false));
-  h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
-  h->have_lw = true;
-  h->residual_k = -1;
+  weights_written(h, MCL_WEIGHT_LOG_SHIFT, SLOTS_SET0);
   return MCL_OK;
 }
 
@@ -531,7 +526,7 @@ int landmarks_launch(mcl_handle* h, const LandmarkObs& o, bool accumulate, bool 
   a.k = o.k;
   a.accumulate = accumulate ? 1 : 0;
   a.lw = h->lw;
-  a.uni_mask = (fused && h->uni_deferred) ? 0x1cu : 0u;
+  a.uni_mask = (fused && h->uni_deferred) ? UNI_ZRP : 0u;
   for (int c = 0; c < 3; ++c) a.uni[c] = h->uni_val[c];
   a.max_slots = fused ? (u64*)(h->ctrl + CTRL_SLOTS2) : nullptr;   // (zeroed with the whole block by this step's predict / pose launch)
   t_begin(h, MCL_K_UPDATE_LANDMARKS);
@@ -543,11 +538,7 @@ int landmarks_launch(mcl_handle* h, const LandmarkObs& o, bool accumulate, bool 
     k_landmark_update<false><<<(unsigned)blocks, 256, 0, h->stream>>>(a);
   t_end(h);
   HIPCHK(h, hipGetLastError());
-  if (!accumulate) h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
-  h->have_lw = true;
-  h->max_valid = fused;
-  if (fused) h->slot_set = 1;
-  h->residual_k = -1;
+  weights_written(h, accumulate ? WEIGHT_MODE_KEEP : MCL_WEIGHT_LOG_SHIFT, fused ? SLOTS_SET1 : SLOTS_NONE);
   return MCL_OK;
 }
 }  // namespace
@@ -658,10 +649,7 @@ int mcl_update_landmarks_assign(mcl_handle* h, const double* det_xyz, int32_t n_
     le = hipMemcpyAsync(assign_out, asg_dev, sizeof(int) * (size_t)n_keep * n_det, hipMemcpyDeviceToHost, h->stream);
   if (le == hipSuccess && n_keep > 0) le = hipStreamSynchronize(h->stream);
   HIPCHK(h, le);
-  if (!accumulate) h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
-  h->have_lw = true;
-  h->max_valid = false;
-  h->residual_k = -1;
+  weights_written(h, accumulate ? WEIGHT_MODE_KEEP : MCL_WEIGHT_LOG_SHIFT, SLOTS_NONE);
   return MCL_OK;
 }
 
@@ -727,10 +715,7 @@ int mcl_update_ranges(mcl_handle* h, const float* ranges, const float* dirs, int
   if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "update_ranges: no map (call mcl_set_map_grid/mesh first)");
   if (accumulate && !h->have_lw) return fail(h, MCL_ERR_STATE, "update_ranges: nothing to accumulate onto");
   RET_IF(ranges_launch(h, ranges, dirs, n_beams, sigma, r_max, sensor_offset, accumulate != 0, h->lw, nullptr, 0, h->n));
-  if (!accumulate) h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
-  h->have_lw = true;
-  h->max_valid = false;
-  h->residual_k = -1;
+  weights_written(h, accumulate ? WEIGHT_MODE_KEEP : MCL_WEIGHT_LOG_SHIFT, SLOTS_NONE);
   return MCL_OK;
 }
 
@@ -885,10 +870,7 @@ int mcl_set_log_weights(mcl_handle* h, const double* lw, int32_t weight_mode) {
   RET_IF(set_device(h));
   HIPCHK(h, hipMemcpyAsync(h->lw, lw, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->weight_mode = weight_mode;
-  h->have_lw = true;
-  h->max_valid = false;
-  h->residual_k = -1;
+  weights_written(h, weight_mode, SLOTS_NONE);
   return MCL_OK;
 }
 
@@ -938,6 +920,14 @@ int mcl_get_fixed_weights(mcl_handle* h, uint64_t* q, uint64_t* total) {
 }
 
 namespace {
+// a fused step that ends between its predict and its gather: the z, roll, pitch stores that kernel left to the gather
+// are made now, on every shard it ran on; the error text `failed` holds survives that
+int abandon_step(mcl_handle* failed, mcl_handle** sh, int n, int rc) {
+  const std::string keep = failed->err;
+  for (int t = 0; t < n; ++t) (void)materialise_uniform(sh[t]);
+  failed->err = keep;
+  return rc;
+}
 // the fused step of one handle (mcl_step_mbes; with a landmark observation: mcl_step_mbes_landmarks)
 int step_mbes_impl(mcl_handle* h, const mcl_odom* odom, double dt, const float* ranges, const float* beam_angles, int32_t B,
                    double sigma, double r_max, const double sensor_offset[6], const LandmarkObs* lm, const char* who) {
@@ -961,9 +951,7 @@ int step_mbes_impl(mcl_handle* h, const mcl_odom* odom, double dt, const float* 
   int rc_u = h->fault_step ? fail(h, MCL_ERR_STATE, w + ": injected fault after predict") : start_state_gather(h);
   if (rc_u == MCL_OK) rc_u = run_mbes(h, plan, pose_done);
   if (rc_u == MCL_OK) {
-    h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
-    h->have_lw = true;
-    h->residual_k = -1;
+    weights_written(h, MCL_WEIGHT_LOG_SHIFT, SLOTS_SET0);
     // the landmark likelihood of the same ping on top (BASELINE config 5): reads the state the predict left (z, roll,
     // pitch from the odometry when that kernel did not store them), leaves max lw in the second slot set
     if (lm) rc_u = landmarks_launch(h, *lm, true, true);
@@ -977,12 +965,7 @@ int step_mbes_impl(mcl_handle* h, const mcl_odom* odom, double dt, const float* 
   }
   // resample; the gather pass also accumulates the sums of update_loc_pose of the new state
   rc_u = run_resample(&h, 1, nullptr, 0, nullptr, sys);
-  if (rc_u != MCL_OK) {
-    const std::string keep = h->err;
-    (void)materialise_uniform(h);
-    h->err = keep;
-    return rc_u;
-  }
+  if (rc_u != MCL_OK) return abandon_step(h, &h, 1, rc_u);
   if (sys)
     RET_IF(collect_fused_moments(&h, 1));
   else
@@ -1026,25 +1009,13 @@ int group_step_mbes_impl(mcl_handle** shards, int32_t ns, const mcl_odom* odom, 
     if (rc == MCL_OK && h->fault_step) rc = fail(h, MCL_ERR_STATE, w + ": injected fault after predict");
     if (rc == MCL_OK) rc = run_mbes(h, plan, pose_done);
     if (rc == MCL_OK) {
-      h->weight_mode = MCL_WEIGHT_LOG_SHIFT;
-      h->have_lw = true;
-      h->residual_k = -1;
+      weights_written(h, MCL_WEIGHT_LOG_SHIFT, SLOTS_SET0);
       if (lm) rc = landmarks_launch(h, *lm, true, true);
     }
-    if (rc != MCL_OK) {
-      const std::string keep = h->err;
-      for (int t = 0; t <= s; ++t) (void)materialise_uniform(shards[t]);
-      h->err = keep;
-      return rc;
-    }
+    if (rc != MCL_OK) return abandon_step(h, shards, s + 1, rc);
   }
   const int rc = run_resample(shards, ns, nullptr, 0, nullptr, true);
-  if (rc != MCL_OK) {
-    const std::string keep = shards[0]->err;
-    for (int t = 0; t < ns; ++t) (void)materialise_uniform(shards[t]);
-    shards[0]->err = keep;
-    return rc;
-  }
+  if (rc != MCL_OK) return abandon_step(shards[0], shards, ns, rc);
   return collect_fused_moments(shards, ns);
 }
 }  // namespace
@@ -1124,12 +1095,10 @@ int mcl_resample_indices(int32_t scheme, const double* weights, int64_t n, const
       if (rc == MCL_OK) rc = alt_indices(h, uniforms, n_uniforms);
       if (rc == MCL_OK) rc = mcl_get_last_indices(h, out);
       if (rc != MCL_OK) g_create_err = h->err;
-    } else if (!uniforms || n_uniforms < 1 || !(uniforms[0] >= 0.0 && uniforms[0] < 1.0)) {
+    } else if (uint64_t u53 = 0; sample_u53(h->cfg, 0u, uniforms, n_uniforms, &u53)) {
       g_create_err = "resample_indices: systematic needs one uniform in [0,1)";
       rc = MCL_ERR_INVALID;
     } else {
-      uint64_t u53 = (uint64_t)std::floor(uniforms[0] * 9007199254740992.0);
-      if (scheme == MCL_RESAMPLE_NAIVE) u53 |= MCL_U53_NAIVE;
       rc = phase_quantise(h, true);
       if (rc == MCL_OK) rc = phase_cdf(h, u53);
       if (rc == MCL_OK) {
@@ -1258,10 +1227,7 @@ int mcl_comm_selftest(mcl_handle* h, int32_t timeout_ms) {
       rc = MCL_ERR_COMM;
       break;
     }
-    if (h->gather_inflight) {
-      (void)hipStreamWaitEvent(h->stream, h->ev_gather_done, 0);
-      h->gather_inflight = false;
-    }
+    (void)cancel_state_gather(h);
     (void)hipEventRecord(done, h->stream);
     const int w = wait_event_ms(done, timeout_ms);
     if (w != 0) {

@@ -6,8 +6,6 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <cstring>
-
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <chrono>
@@ -56,6 +54,13 @@ struct TimedRegion {
   bool open;
 };
 
+// where the resample gather leaves the 13 moment sums of a fused step (decided by plan_gather, read by
+// collect_fused_moments)
+//   SCAL          scal[32..47]: reduced over the shards, then copied to the ring
+//   SHARD_RECORD  the shard's record: they ride with the NEXT step's all-gather
+//   RING_DIRECT   single shard: the kernel's last block writes the pinned ring entry itself
+enum MomentsDest { MOMENTS_SCAL, MOMENTS_SHARD_RECORD, MOMENTS_RING_DIRECT };
+
 }  // namespace
 
 struct mcl_handle {
@@ -91,7 +96,7 @@ struct mcl_handle {
   double* replay_dev = nullptr;
   double* pose7 = nullptr;
   double* host_pin_dev = nullptr;  // device-side address of host_pin (kernels write results into the ring directly)
-  bool moments_direct = false;
+  MomentsDest moments_dest = MOMENTS_SCAL;   // of the last gather
   double* host_pin = nullptr;  // pinned ring: MEAN_RING entries of 16 doubles (sums7, pad, cov-sums6, pad2)
   long long mean_count = 0;     // number of mean/cov results produced so far
   // MBES
@@ -209,7 +214,9 @@ struct mcl_handle {
   // z, roll, pitch of every particle are the odometry's right after motion_pred: the exchange leaves them out
   bool uni_valid = false;       // true from a predict until the state is written by anything else
   double uni_val[3] = {0, 0, 0};
-  unsigned gather_uni_mask = 0; // components the last state exchange skipped (phase_gather substitutes uni_val)
+  unsigned gather_uni_mask = 0; // components the state exchange of THIS resample skipped: written by start_state_gather,
+                                // exchange_cdf_state / exchange_cdf_state_group and launch_pack, read by plan_gather (which
+                                // substitutes uni_val), cleared by finish_resample
   bool fault_step = false;      // MCL_FAULT_INJECT=step_after_predict (tests): the fused step fails after its predict
   bool uni_deferred = false;    // fused step in flight: the predict kernel did NOT store z, roll, pitch (the gather of
                                 // the same call substitutes them; materialise_uniform() on any other way out)
@@ -222,7 +229,6 @@ struct mcl_handle {
   const u64* qshift_cur = nullptr;       // the shift the weights in `q` are read with (nullptr: none) -- set by every resample
   bool shrec_dirty = false;              // a launch that accumulates into the record is queued and k_shift_scan (which zeroes it) is not
   // the fused step's moments ride with the NEXT step's records instead of an all-reduce of their own:
-  bool moments_ride = false;             // this gather writes its 13 sums into the shard's record (set by phase_gather)
   bool mom_pending = false;              // a ring entry is reserved whose sums still lie, per shard, in the records
   long long mom_pending_entry = -1;      // ... which one (index into the result ring, before the modulo)
   u64* lsx = nullptr;            // device, world x 4 words
@@ -393,6 +399,33 @@ int upload_replay(mcl_handle* h, const double* normals) {
 int set_device(mcl_handle* h) {
   HIPCHK(h, hipSetDevice(h->device));
   return MCL_OK;
+}
+
+// z, roll, pitch (components 2, 3, 4) are the same three numbers on every particle of every shard: mcl_handle::uni_valid
+constexpr unsigned UNI_ZRP = 0x1cu;
+unsigned uni_mask(const mcl_handle* h) { return h->uni_valid ? UNI_ZRP : 0u; }
+// the components a state exchange that skips `mask` ships, ascending; returns how many
+int shipped_components(unsigned mask, int ship[6]) {
+  int nship = 0;
+  for (int c = 0; c < 6; ++c) {
+    ship[c] = 0;
+    if (!((mask >> c) & 1u)) ship[nship++] = c;
+  }
+  return nship;
+}
+
+// New log-weights were written (every update, mcl_set_log_weights): the ONE place that says what they are.
+// mode: the new weight_mode, or WEIGHT_MODE_KEEP when the update accumulated onto the weights that were there.
+// slots: which slot set the kernel that wrote them left max lw in -- SLOTS_NONE: neither, ensure_max_slots reduces.
+// (A stale max_valid would make the resample quantise against the wrong maximum, silently.)
+enum WeightSlots { SLOTS_NONE, SLOTS_SET0, SLOTS_SET1 };
+constexpr int WEIGHT_MODE_KEEP = -1;
+void weights_written(mcl_handle* h, int mode, WeightSlots slots) {
+  if (mode != WEIGHT_MODE_KEEP) h->weight_mode = mode;
+  h->have_lw = true;
+  h->max_valid = slots != SLOTS_NONE;
+  if (slots != SLOTS_NONE) h->slot_set = slots == SLOTS_SET1 ? 1 : 0;
+  h->residual_k = -1;
 }
 
 }  // namespace

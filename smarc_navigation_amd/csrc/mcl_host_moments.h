@@ -27,37 +27,31 @@ int phase_cov_partial(mcl_handle* h) {
   HIPCHK(h, hipGetLastError());
   return MCL_OK;
 }
-int exchange_sums(mcl_handle** sh, int ns, int off, int cnt) {
-  if (ns == 1) {
-    mcl_handle* h = sh[0];
-    if (h->comm) {
-      t_begin(h, MCL_K_COMM_MOMENTS);
-      NCCLCHK(h, ncclAllReduce(h->scal + off, h->scal + off, cnt, ncclDouble, ncclSum, h->comm, h->stream));
-      t_end(h);
-    }
-    return MCL_OK;
-  }
+int exchange_sums(mcl_handle* h, int off, int cnt) {
+  if (!h->comm) return MCL_OK;
+  t_begin(h, MCL_K_COMM_MOMENTS);
+  NCCLCHK(h, ncclAllReduce(h->scal + off, h->scal + off, cnt, ncclDouble, ncclSum, h->comm, h->stream));
+  t_end(h);
+  return MCL_OK;
+}
+int exchange_sums_group(mcl_handle** sh, int ns, int off, int cnt) {
   std::vector<double> acc(cnt, 0.0), tmp(cnt);
   for (int s = 0; s < ns; ++s) {
-    RET_IF(set_device(sh[s]));
-    HIPCHK(sh[s], hipMemcpyAsync(tmp.data(), sh[s]->scal + off, sizeof(double) * cnt, hipMemcpyDeviceToHost,
-                                 sh[s]->stream));
-    HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
+    RET_IF(pull_sync(sh[s], tmp.data(), sh[s]->scal + off, sizeof(double) * cnt));
     for (int k = 0; k < cnt; ++k) acc[k] += tmp[k];
   }
-  for (int s = 0; s < ns; ++s) {
-    RET_IF(set_device(sh[s]));
-    HIPCHK(sh[s], hipMemcpyAsync(sh[s]->scal + off, acc.data(), sizeof(double) * cnt, hipMemcpyHostToDevice,
-                                 sh[s]->stream));
-    HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
-  }
+  for (int s = 0; s < ns; ++s) RET_IF(push_sync(sh[s], sh[s]->scal + off, acc.data(), sizeof(double) * cnt));
   return MCL_OK;
+}
+// scal[off .. off + cnt) summed over the shards: the entry points below take (sh, ns) like run_resample does
+int sum_over_shards(mcl_handle** sh, int ns, int off, int cnt) {
+  return local_group(ns) ? exchange_sums_group(sh, ns, off, cnt) : exchange_sums(sh[0], off, cnt);
 }
 int run_mean_cov_async(mcl_handle** sh, int ns) {
   for (int s = 0; s < ns; ++s) RET_IF(phase_mean_partial(sh[s]));
-  RET_IF(exchange_sums(sh, ns, 8, 7));
+  RET_IF(sum_over_shards(sh, ns, 8, 7));
   for (int s = 0; s < ns; ++s) RET_IF(phase_cov_partial(sh[s]));
-  RET_IF(exchange_sums(sh, ns, 16, 6));
+  RET_IF(sum_over_shards(sh, ns, 16, 6));
   for (int s = 0; s < ns; ++s) {
     mcl_handle* h = sh[s];
     RET_IF(set_device(h));
@@ -92,27 +86,30 @@ int flush_pending_moments(mcl_handle* h) {
   return MCL_OK;
 }
 
-// the sums k_resample_gather<true> left in scal[32..47]: reduce over the shards, queue the copy to the ring
+// the sums of the fused step's gather, wherever plan_gather sent them (mcl_handle::moments_dest), become the next ring
+// entry.  A LOCAL group's lie in every shard's scal[32..47], like MOMENTS_SCAL
 int collect_fused_moments(mcl_handle** sh, int ns) {
-  if (ns == 1 && sh[0]->moments_direct) {
-    sh[0]->mean_count++;
-    sh[0]->have_meancov = true;
-    return MCL_OK;
+  mcl_handle* h0 = sh[0];
+  switch (local_group(ns) ? MOMENTS_SCAL : h0->moments_dest) {
+    case MOMENTS_RING_DIRECT:   // the kernel has written the entry
+      h0->mean_count++;
+      h0->have_meancov = true;
+      return MCL_OK;
+    case MOMENTS_SHARD_RECORD: {
+      // no collective now: the sums wait in the record; the ring entry is reserved, k_shift_scan of the next step (or a
+      // flush) fills it
+      RET_IF(flush_pending_moments(h0));   // (an older entry that no records exchange came for)
+      double* slot = h0->host_pin + RING_STRIDE * (h0->mean_count % MEAN_RING);
+      slot[16] = 1.0;
+      h0->mom_pending = true;
+      h0->mom_pending_entry = h0->mean_count;
+      h0->mean_count++;
+      h0->have_meancov = true;
+      return MCL_OK;
+    }
+    case MOMENTS_SCAL: break;   // reduce over the shards, queue the copy to the ring
   }
-  if (ns == 1 && sh[0]->moments_ride) {
-    // no collective now: the sums wait in the record; the ring entry is reserved, k_shift_scan of the next step (or a
-    // flush) fills it
-    mcl_handle* h = sh[0];
-    RET_IF(flush_pending_moments(h));   // (an older entry that no records exchange came for)
-    double* slot = h->host_pin + RING_STRIDE * (h->mean_count % MEAN_RING);
-    slot[16] = 1.0;
-    h->mom_pending = true;
-    h->mom_pending_entry = h->mean_count;
-    h->mean_count++;
-    h->have_meancov = true;
-    return MCL_OK;
-  }
-  RET_IF(exchange_sums(sh, ns, 32, MOM_COUNT));
+  RET_IF(sum_over_shards(sh, ns, 32, MOM_COUNT));
   for (int s = 0; s < ns; ++s) {
     mcl_handle* h = sh[s];
     RET_IF(set_device(h));

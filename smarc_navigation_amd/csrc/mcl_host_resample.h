@@ -33,52 +33,51 @@ int phase_local_max(mcl_handle* h) {
   return MCL_OK;
 }
 
-int exchange_max(mcl_handle** sh, int ns) {
-  if (ns == 1) {
-    mcl_handle* h = sh[0];
-    if (h->comm) {
-      t_begin(h, MCL_K_COMM);
-      NCCLCHK(h, ncclAllReduce(h->scal, h->scal, 1, ncclDouble, ncclMax, h->comm, h->stream));
-      t_end(h);
-    }
-    return MCL_OK;
-  }
-  double m = -INFINITY;
+// LOCAL group: a few words of a shard to the host and back, synchronously (the group is a test harness, not a fast path)
+int pull_sync(mcl_handle* h, void* host, const void* dev, size_t bytes) {
+  RET_IF(set_device(h));
+  HIPCHK(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MCL_OK;
+}
+int push_sync(mcl_handle* h, void* dev, const void* host, size_t bytes) {
+  RET_IF(set_device(h));
+  HIPCHK(h, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MCL_OK;
+}
+int exchange_max_group(mcl_handle** sh, int ns) {
+  double m = -INFINITY, v;
   for (int s = 0; s < ns; ++s) {
-    double v;
-    RET_IF(set_device(sh[s]));
-    HIPCHK(sh[s], hipMemcpyAsync(&v, sh[s]->scal, sizeof(double), hipMemcpyDeviceToHost, sh[s]->stream));
-    HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
+    RET_IF(pull_sync(sh[s], &v, sh[s]->scal, sizeof(double)));
     if (v > m) m = v;
   }
-  for (int s = 0; s < ns; ++s) {
-    RET_IF(set_device(sh[s]));
-    HIPCHK(sh[s], hipMemcpyAsync(sh[s]->scal, &m, sizeof(double), hipMemcpyHostToDevice, sh[s]->stream));
-    HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
-  }
+  for (int s = 0; s < ns; ++s) RET_IF(push_sync(sh[s], sh[s]->scal, &m, sizeof(double)));
   return MCL_OK;
 }
 
+// the argument block of both quantise kernels: what they share.  slots / rec / tile_bits are the caller's
+QuantArgs quant_args(const mcl_handle* h) {
+  QuantArgs a{};
+  a.lw = h->lw;
+  a.n = h->n;
+  a.m_lw = h->scal;
+  a.mode = h->weight_mode;
+  a.s = 63 - ceil_log2(h->ng);
+  a.scale = std::ldexp(1.0, a.s);
+  a.q = h->q;
+  a.tile_sum = h->tile64;
+  return a;
+}
 // fixed-point weights, tile sums, exclusive tile offsets and the shard total in ONE launch.
 // from_slots: single shard -- the kernel reads the maximum straight from the slots (no k_max_finish)
 // fused_next: k_cdf_expand<true> follows and adds the tile sums up itself (no tile scan launch)
 int phase_quantise(mcl_handle* h, bool from_slots, bool fused_next = false) {
   RET_IF(set_device(h));
-  const double scale = std::ldexp(1.0, 63 - ceil_log2(h->ng));
   t_begin(h, MCL_K_NORMALISE);
   if (from_slots) RET_IF(ensure_max_slots(h));
-  QuantArgs a;
-  a.lw = h->lw;
-  a.n = h->n;
+  QuantArgs a = quant_args(h);
   a.slots = from_slots ? ctrl_slots(h) : nullptr;
-  a.m_lw = h->scal;
-  a.mode = h->weight_mode;
-  a.scale = scale;
-  a.s = 63 - ceil_log2(h->ng);
-  a.q = h->q;
-  a.tile_sum = h->tile64;
-  a.rec = nullptr;
-  a.tile_bits = nullptr;
   h->qshift_cur = nullptr;
   k_quantise_tiles<<<(unsigned)h->ntiles_loc, MCL_BLOCK, 0, h->stream>>>(a);
   t_end(h);
@@ -114,16 +113,8 @@ int phase_quantise_shard(mcl_handle* h) {
     HIPCHK(h, hipMemsetAsync(mine, 0, sizeof(u64) * SHREC_WORDS, h->stream));
   t_begin(h, MCL_K_NORMALISE);
   RET_IF(ensure_max_slots(h));
-  QuantArgs a;
-  a.lw = h->lw;
-  a.n = h->n;
+  QuantArgs a = quant_args(h);
   a.slots = ctrl_slots(h);   // the SHARD's maximum
-  a.m_lw = h->scal;
-  a.mode = h->weight_mode;
-  a.scale = std::ldexp(1.0, 63 - ceil_log2(h->ng));
-  a.s = 63 - ceil_log2(h->ng);
-  a.q = h->q;
-  a.tile_sum = h->tile64;
   a.rec = mine;
   a.tile_bits = h->tile_bits;
   h->shrec_dirty = true;
@@ -161,27 +152,17 @@ int phase_shift_scan(mcl_handle* h) {
   return MCL_OK;
 }
 
-int exchange_totals(mcl_handle** sh, int ns) {
-  if (ns == 1) {
-    mcl_handle* h = sh[0];
-    if (h->comm) {
-      t_begin(h, MCL_K_COMM_RECORDS);
-      NCCLCHK(h, ncclAllGather(h->totals + h->rank, h->totals, 1, ncclUint64, h->comm, h->stream));
-      t_end(h);
-    }
-    return MCL_OK;
-  }
+int exchange_totals(mcl_handle* h) {
+  if (!h->comm) return MCL_OK;
+  t_begin(h, MCL_K_COMM_RECORDS);
+  NCCLCHK(h, ncclAllGather(h->totals + h->rank, h->totals, 1, ncclUint64, h->comm, h->stream));
+  t_end(h);
+  return MCL_OK;
+}
+int exchange_totals_group(mcl_handle** sh, int ns) {
   std::vector<u64> t(ns);
-  for (int s = 0; s < ns; ++s) {
-    RET_IF(set_device(sh[s]));
-    HIPCHK(sh[s], hipMemcpyAsync(&t[s], sh[s]->totals + s, sizeof(u64), hipMemcpyDeviceToHost, sh[s]->stream));
-    HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
-  }
-  for (int s = 0; s < ns; ++s) {
-    RET_IF(set_device(sh[s]));
-    HIPCHK(sh[s], hipMemcpyAsync(sh[s]->totals, t.data(), sizeof(u64) * ns, hipMemcpyHostToDevice, sh[s]->stream));
-    HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
-  }
+  for (int s = 0; s < ns; ++s) RET_IF(pull_sync(sh[s], &t[s], sh[s]->totals + s, sizeof(u64)));
+  for (int s = 0; s < ns; ++s) RET_IF(push_sync(sh[s], sh[s]->totals, t.data(), sizeof(u64) * ns));
   return MCL_OK;
 }
 
@@ -202,46 +183,52 @@ int phase_cdf(mcl_handle* h, uint64_t u53) {
   return MCL_OK;
 }
 
+// the pre-resample state to every rank, one all-gather per component (inside the caller's group) -- but z, roll, pitch
+// only when they are not the odometry's on every particle: 24 B instead of 48 B per particle of the GLOBAL cloud
+int allgather_state(mcl_handle* h, ncclComm_t comm, hipStream_t stream) {
+  h->gather_uni_mask = uni_mask(h);
+  int ship[6];
+  const int nship = shipped_components(h->gather_uni_mask, ship);
+  for (int j = 0; j < nship; ++j)
+    NCCLCHK(h, ncclAllGather(h->state[h->cur] + (size_t)ship[j] * h->n, h->state_glob + (size_t)ship[j] * h->ng,
+                             (size_t)h->n, ncclDouble, comm, stream));
+  return MCL_OK;
+}
 // all-gather of the offspring CDF slices and of the pre-resample state (north_star: "all-gather
 // before resampling"); shards are contiguous and equal-sized
-int exchange_cdf_state(mcl_handle** sh, int ns) {
-  if (ns == 1) {
-    mcl_handle* h = sh[0];
-    if (h->comm) {
-      t_begin(h, MCL_K_COMM);
-      if (h->gather_inflight) {
-        // the state went out right after predict and travelled under the measurement update
-        NCCLCHK(h, ncclAllGather(h->ncum + h->goff, h->ncum, (size_t)h->n, ncclUint32, h->comm, h->stream));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_gather_done, 0));
-        h->gather_inflight = false;
-      } else {
-        h->gather_uni_mask = h->uni_valid ? 0x1cu : 0u;  // z, roll, pitch: the same on every particle of every shard
-        NCCLCHK(h, ncclGroupStart());
-        NCCLCHK(h, ncclAllGather(h->ncum + h->goff, h->ncum, (size_t)h->n, ncclUint32, h->comm, h->stream));
-        for (int c = 0; c < 6; ++c)
-          if (!((h->gather_uni_mask >> c) & 1u))
-            NCCLCHK(h, ncclAllGather(h->state[h->cur] + (size_t)c * h->n, h->state_glob + (size_t)c * h->ng,
-                                     (size_t)h->n, ncclDouble, h->comm, h->stream));
-        NCCLCHK(h, ncclGroupEnd());
-      }
-      t_end(h);
-    }
-    return MCL_OK;
+int exchange_cdf_state(mcl_handle* h) {
+  if (!h->comm) return MCL_OK;
+  t_begin(h, MCL_K_COMM);
+  if (h->gather_inflight) {
+    // the state went out right after predict and travelled under the measurement update
+    NCCLCHK(h, ncclAllGather(h->ncum + h->goff, h->ncum, (size_t)h->n, ncclUint32, h->comm, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_gather_done, 0));
+    h->gather_inflight = false;
+  } else {
+    NCCLCHK(h, ncclGroupStart());
+    NCCLCHK(h, ncclAllGather(h->ncum + h->goff, h->ncum, (size_t)h->n, ncclUint32, h->comm, h->stream));
+    RET_IF(allgather_state(h, h->comm, h->stream));
+    NCCLCHK(h, ncclGroupEnd());
   }
+  t_end(h);
+  return MCL_OK;
+}
+int exchange_cdf_state_group(mcl_handle** sh, int ns) {
   for (int s = 0; s < ns; ++s) HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
   for (int d = 0; d < ns; ++d) {
     mcl_handle* D = sh[d];
-    D->gather_uni_mask = D->uni_valid ? 0x1cu : 0u;  // z, roll, pitch: the same on every particle of every shard
+    D->gather_uni_mask = uni_mask(D);
+    int ship[6];
+    const int nship = shipped_components(D->gather_uni_mask, ship);
     RET_IF(set_device(D));
     for (int s = 0; s < ns; ++s) {
       mcl_handle* S = sh[s];
       if (s != d)
         HIPCHK(D, hipMemcpyAsync(D->ncum + S->goff, S->ncum + S->goff, sizeof(u32) * (size_t)S->n,
                                  hipMemcpyDefault, D->stream));
-      for (int c = 0; c < 6; ++c)
-        if (!((D->gather_uni_mask >> c) & 1u))
-          HIPCHK(D, hipMemcpyAsync(D->state_glob + (size_t)c * D->ng + S->goff, S->state[S->cur] + (size_t)c * S->n,
-                                   sizeof(double) * (size_t)S->n, hipMemcpyDefault, D->stream));
+      for (int j = 0; j < nship; ++j)
+        HIPCHK(D, hipMemcpyAsync(D->state_glob + (size_t)ship[j] * D->ng + S->goff, S->state[S->cur] + (size_t)ship[j] * S->n,
+                                 sizeof(double) * (size_t)S->n, hipMemcpyDefault, D->stream));
     }
     HIPCHK(D, hipStreamSynchronize(D->stream));
   }
@@ -263,39 +250,38 @@ int start_state_gather(mcl_handle* h) {
   if (!h->comm2 || !h->state_glob) return MCL_OK;
   HIPCHK(h, hipEventRecord(h->ev_state_ready, h->stream));
   HIPCHK(h, hipStreamWaitEvent(h->comm_stream, h->ev_state_ready, 0));
-  // 24 B instead of 48 B per particle of the GLOBAL cloud when z, roll, pitch are the odometry's on every particle
-  h->gather_uni_mask = h->uni_valid ? 0x1cu : 0u;
   NCCLCHK(h, ncclGroupStart());
-  for (int c = 0; c < 6; ++c)
-    if (!((h->gather_uni_mask >> c) & 1u))
-      NCCLCHK(h, ncclAllGather(h->state[h->cur] + (size_t)c * h->n, h->state_glob + (size_t)c * h->ng, (size_t)h->n,
-                               ncclDouble, h->comm2, h->comm_stream));
+  RET_IF(allgather_state(h, h->comm2, h->comm_stream));
   NCCLCHK(h, ncclGroupEnd());
   HIPCHK(h, hipEventRecord(h->ev_gather_done, h->comm_stream));
   h->gather_inflight = true;
   return MCL_OK;
 }
 
-// lost-slot ranks + dupes list.  fused_cdf: single shard, the offspring CDF is computed in the same pass
-int phase_expand(mcl_handle* h, bool fused_cdf, uint64_t u53) {
-  RET_IF(set_device(h));
-  ExpandArgs a;
-  memset(&a, 0, sizeof a);
+// the argument block of k_cdf_expand: what the single-shard / all-gathered form and the shard-local form share
+ExpandArgs expand_args(mcl_handle* h, uint64_t u53) {
+  ExpandArgs a{};
   a.q = h->q;
-  a.tile_sum = h->tile64;
+  a.tile_sum = h->tile64;  // (shard-local form: the exclusive offsets k_scan_tile_sums left)
   a.n_fine = h->ntiles_loc;
   a.n_global_u = (u64)h->ng;
   a.u53 = u53;
-  a.total_out = h->totals + h->rank;
-  a.ncum = h->ncum;
-  a.n = h->ng;
-  a.own0 = h->goff;
   a.own_n = h->n;
   a.zr = h->zr;
   a.dupes = h->dupes32;
   a.desc = h->desc;
   a.ticket = ctrl_u32(h, CTRL_T_EXPAND);
   a.epoch = ++h->epoch;
+  return a;
+}
+// lost-slot ranks + dupes list.  fused_cdf: single shard, the offspring CDF is computed in the same pass
+int phase_expand(mcl_handle* h, bool fused_cdf, uint64_t u53) {
+  RET_IF(set_device(h));
+  ExpandArgs a = expand_args(h, u53);
+  a.total_out = h->totals + h->rank;
+  a.ncum = h->ncum;
+  a.n = h->ng;
+  a.own0 = h->goff;
   const unsigned grid = (unsigned)((h->ng + RS_TILE - 1) / RS_TILE);
   t_begin(h, fused_cdf ? MCL_K_SCAN : MCL_K_RESAMPLE);
   if (fused_cdf)
@@ -322,23 +308,11 @@ int launch_pack(mcl_handle* h, u64 publish_seq = 0);
 int phase_expand_local(mcl_handle* h, uint64_t u53) {
   RET_IF(set_device(h));
   RET_IF(alloc_lsx(h));
-  ExpandArgs a;
-  memset(&a, 0, sizeof a);
-  a.q = h->q;
-  a.tile_sum = h->tile64;  // exclusive offsets (k_scan_tile_sums)
-  a.n_fine = h->ntiles_loc;
-  a.n_global_u = (u64)h->ng;
-  a.u53 = u53;
+  ExpandArgs a = expand_args(h, u53);
   a.total_out = h->totals + h->world;  // (unused in this mode)
   a.ncum = h->ncum + h->goff;
   a.n = h->n;
   a.own0 = 0;
-  a.own_n = h->n;
-  a.zr = h->zr;
-  a.dupes = h->dupes32;
-  a.desc = h->desc;
-  a.ticket = ctrl_u32(h, CTRL_T_EXPAND);
-  a.epoch = ++h->epoch;
   a.totals = h->totals;
   a.rank = h->rank;
   a.world = h->world;
@@ -347,7 +321,7 @@ int phase_expand_local(mcl_handle* h, uint64_t u53) {
   for (int c = 0; c < 3; ++c) a.p0[c] = h->state[h->cur] + (size_t)c * h->n;
   // (after a fused predict the state's z words are not written yet -- the moments' shift takes the uniform
   //  depth itself, like the unsharded gather does, so sharded and unsharded means agree to the last bit)
-  a.p0_z_uniform = h->uni_valid ? 1 : 0;
+  a.p0_z_uniform = uni_mask(h) ? 1 : 0;
   a.p0_z = h->uni_val[0];
   const unsigned grid = (unsigned)((h->n + RS_TILE - 1) / RS_TILE);
   t_begin(h, MCL_K_SCAN);
@@ -358,68 +332,77 @@ int phase_expand_local(mcl_handle* h, uint64_t u53) {
   return MCL_OK;
 }
 
-// every shard learns {L, S} of every shard (and the position of global particle 0); the host needs them to size the
-// point-to-point transfers: ONE stream synchronisation per resample
-int exchange_ls(mcl_handle** sh, int ns) {
-  const int world = sh[0]->world;
-  if (ns == 1) {
-    mcl_handle* h = sh[0];
-    t_begin(h, MCL_K_COMM_RECORDS);
-    if (h->comm && world > 1)
-      NCCLCHK(h, ncclAllGather(h->lsx + 4 * (size_t)h->rank, h->lsx, 4, ncclUint64, h->comm, h->stream));
-    if (h->lsx_host_dev) {
-      // the records travel to pinned memory by a kernel that writes a sequence word last; the pack kernel (sized on
-      // the device from the same records) is queued behind it BEFORE the host starts to wait, so the GPU keeps
-      // working while the host wakes up; the host spins on the word instead of synchronising the stream
-      const u64 seq = ++h->ls_seq;
-      t_end(h);
-      RET_IF(launch_pack(h, seq));   // (its first workgroup publishes the records before it packs)
-      volatile u64* flag = h->lsx_host + 4 * (size_t)world;
-      const auto t0 = std::chrono::steady_clock::now();
-      unsigned spins = 0;
-      while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-        if ((++spins & 0xfffu) == 0u) {
-          if (hipStreamQuery(h->stream) == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
-            return fail(h, MCL_ERR_HIP, "resample exchange: the hand-over records never arrived");
-          if (std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count() > 60)
-            return fail(h, MCL_ERR_COMM, "resample exchange: timed out waiting for the hand-over records");
-        }
-        __builtin_ia32_pause();
-      }
-    } else {
-      HIPCHK(h, hipMemcpyAsync(h->lsx_host, h->lsx, sizeof(u64) * 4 * (size_t)world, hipMemcpyDeviceToHost, h->stream));
-      t_end(h);
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-  } else {
-    for (int s = 0; s < ns; ++s) {
-      mcl_handle* h = sh[s];
-      RET_IF(set_device(h));
-      HIPCHK(h, hipMemcpyAsync(h->lsx_host + 4 * (size_t)s, h->lsx + 4 * (size_t)s, sizeof(u64) * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    for (int s = 0; s < ns; ++s) HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
-    for (int d = 0; d < ns; ++d) {
-      for (int s = 0; s < ns; ++s)
-        if (s != d) memcpy(sh[d]->lsx_host + 4 * (size_t)s, sh[s]->lsx_host + 4 * (size_t)s, sizeof(u64) * 4);
-      RET_IF(set_device(sh[d]));
-      HIPCHK(sh[d], hipMemcpyAsync(sh[d]->lsx, sh[d]->lsx_host, sizeof(u64) * 4 * (size_t)ns, hipMemcpyHostToDevice, sh[d]->stream));
-    }
+// the hand-over records in lsx_host -> ex_L / ex_S and their prefix sums, which size the point-to-point transfers
+int read_ls_records(mcl_handle* h) {
+  const int world = h->world;
+  h->ex_L.assign(world, 0u);
+  h->ex_S.assign(world, 0u);
+  h->ex_Lpre.assign(world + 1, 0u);
+  h->ex_Spre.assign(world + 1, 0u);
+  for (int r = 0; r < world; ++r) {
+    h->ex_L[r] = (u32)(h->lsx_host[4 * (size_t)r] & 0xffffffffull);
+    h->ex_S[r] = (u32)(h->lsx_host[4 * (size_t)r] >> 32);
+    h->ex_Lpre[r + 1] = h->ex_Lpre[r] + h->ex_L[r];
+    h->ex_Spre[r + 1] = h->ex_Spre[r] + h->ex_S[r];
   }
+  if (h->ex_Lpre[world] != h->ex_Spre[world])
+    return fail(h, MCL_ERR_COMM, "resample exchange: lost slots and surplus copies of the shards do not add up (ranks fed different inputs?)");
+  return MCL_OK;
+}
+// the host's wait for the records k_pack_dupes' first workgroup publishes into pinned memory, sequence word last: it spins
+// on that word instead of synchronising the stream
+int wait_ls_records(mcl_handle* h, u64 seq) {
+  volatile u64* flag = h->lsx_host + 4 * (size_t)h->world;
+  const auto t0 = std::chrono::steady_clock::now();
+  unsigned spins = 0;
+  while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
+    if ((++spins & 0xfffu) == 0u) {
+      if (hipStreamQuery(h->stream) == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
+        return fail(h, MCL_ERR_HIP, "resample exchange: the hand-over records never arrived");
+      if (std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count() > 60)
+        return fail(h, MCL_ERR_COMM, "resample exchange: timed out waiting for the hand-over records");
+    }
+    __builtin_ia32_pause();
+  }
+  return MCL_OK;
+}
+
+// every shard learns {L, S} of every shard (and the position of global particle 0); the host needs them to size the
+// point-to-point transfers: ONE stream synchronisation per resample.  *packed: the pack kernel is queued already
+int exchange_ls(mcl_handle* h, bool* packed) {
+  t_begin(h, MCL_K_COMM_RECORDS);
+  if (h->comm && h->world > 1)
+    NCCLCHK(h, ncclAllGather(h->lsx + 4 * (size_t)h->rank, h->lsx, 4, ncclUint64, h->comm, h->stream));
+  *packed = h->lsx_host_dev != nullptr;
+  if (*packed) {
+    // the records travel to pinned memory by a kernel that writes a sequence word last; the pack kernel (sized on
+    // the device from the same records) is queued behind it BEFORE the host starts to wait, so the GPU keeps
+    // working while the host wakes up
+    const u64 seq = ++h->ls_seq;
+    t_end(h);
+    RET_IF(launch_pack(h, seq));   // (its first workgroup publishes the records before it packs)
+    RET_IF(wait_ls_records(h, seq));
+  } else {
+    HIPCHK(h, hipMemcpyAsync(h->lsx_host, h->lsx, sizeof(u64) * 4 * (size_t)h->world, hipMemcpyDeviceToHost, h->stream));
+    t_end(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return read_ls_records(h);
+}
+int exchange_ls_group(mcl_handle** sh, int ns) {
   for (int s = 0; s < ns; ++s) {
     mcl_handle* h = sh[s];
-    h->ex_L.assign(world, 0u);
-    h->ex_S.assign(world, 0u);
-    h->ex_Lpre.assign(world + 1, 0u);
-    h->ex_Spre.assign(world + 1, 0u);
-    for (int r = 0; r < world; ++r) {
-      h->ex_L[r] = (u32)(h->lsx_host[4 * (size_t)r] & 0xffffffffull);
-      h->ex_S[r] = (u32)(h->lsx_host[4 * (size_t)r] >> 32);
-      h->ex_Lpre[r + 1] = h->ex_Lpre[r] + h->ex_L[r];
-      h->ex_Spre[r + 1] = h->ex_Spre[r] + h->ex_S[r];
-    }
-    if (h->ex_Lpre[world] != h->ex_Spre[world])
-      return fail(h, MCL_ERR_COMM, "resample exchange: lost slots and surplus copies of the shards do not add up (ranks fed different inputs?)");
+    RET_IF(set_device(h));
+    HIPCHK(h, hipMemcpyAsync(h->lsx_host + 4 * (size_t)s, h->lsx + 4 * (size_t)s, sizeof(u64) * 4, hipMemcpyDeviceToHost, h->stream));
   }
+  for (int s = 0; s < ns; ++s) HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
+  for (int d = 0; d < ns; ++d) {
+    for (int s = 0; s < ns; ++s)
+      if (s != d) memcpy(sh[d]->lsx_host + 4 * (size_t)s, sh[s]->lsx_host + 4 * (size_t)s, sizeof(u64) * 4);
+    RET_IF(set_device(sh[d]));
+    HIPCHK(sh[d], hipMemcpyAsync(sh[d]->lsx, sh[d]->lsx_host, sizeof(u64) * 4 * (size_t)ns, hipMemcpyHostToDevice, sh[d]->stream));
+  }
+  for (int s = 0; s < ns; ++s) RET_IF(read_ls_records(sh[s]));
   return MCL_OK;
 }
 
@@ -434,7 +417,7 @@ int launch_pack(mcl_handle* h, u64 publish_seq) {
     HIPCHK(h, hipMalloc(&h->xsend, sizeof(double) * 6 * cap));
     h->xsend_cap = cap;
   }
-  h->gather_uni_mask = h->uni_valid ? 0x1cu : 0u;  // z, roll, pitch: the same on every particle of every shard
+  h->gather_uni_mask = uni_mask(h);
   PackArgs a;
   a.src = state_ptrs(h->state[h->cur], h->n);
   a.dupes = h->dupes32;
@@ -442,11 +425,7 @@ int launch_pack(mcl_handle* h, u64 publish_seq) {
   a.rank = h->rank;
   a.world = h->world;
   a.cap = (u32)std::min<size_t>(h->xsend_cap, 0xffffffffull);
-  a.nship = 0;
-  for (int c = 0; c < 6; ++c) {
-    a.ship[c] = 0;
-    if (!((h->gather_uni_mask >> c) & 1u)) a.ship[a.nship++] = c;
-  }
+  a.nship = shipped_components(h->gather_uni_mask, a.ship);
   h->ex_nship = a.nship;
   a.send = h->xsend;
   a.recv = h->xrecv;
@@ -482,37 +461,36 @@ void ex_range(const mcl_handle* h, int from, int to, u32& lo, u32& hi) {
   plan_range(h->ex_Lpre.data(), h->ex_Spre.data(), from, to, lo, hi);
 }
 
-int exchange_dupes(mcl_handle** sh, int ns) {
-  if (ns == 1) {
-    mcl_handle* h = sh[0];
-    h->ex_lost += h->ex_L[h->rank];
-    ++h->ex_rounds;
-    if (!h->comm || h->world == 1) return MCL_OK;
-    const int q = h->rank;
-    const size_t K = (size_t)h->ex_nship;
-    t_begin(h, MCL_K_COMM_P2P);
-    NCCLCHK(h, ncclGroupStart());
-    for (int r = 0; r < h->world; ++r) {
-      if (r == q) continue;
-      u32 lo, hi;
-      ex_range(h, q, r, lo, hi);  // what I hold and r needs
-      // (ONE send and ONE receive per peer: a copy is one record of K doubles, the range a peer needs is contiguous)
-      if (hi > lo) {
-        h->ex_sent += hi - lo;
-        NCCLCHK(h, ncclSend(h->xsend + (size_t)(lo - h->ex_Spre[q]) * K, (size_t)(hi - lo) * K, ncclDouble, r, h->comm, h->stream));
-        ++h->ex_ops;
-      }
-      ex_range(h, r, q, lo, hi);  // what r holds and I need
-      if (hi > lo) {
-        NCCLCHK(h, ncclRecv(h->xrecv + (size_t)(lo - h->ex_Lpre[q]) * K, (size_t)(hi - lo) * K, ncclDouble, r, h->comm, h->stream));
-        ++h->ex_ops;
-      }
+int exchange_dupes(mcl_handle* h) {
+  h->ex_lost += h->ex_L[h->rank];
+  ++h->ex_rounds;
+  if (!h->comm || h->world == 1) return MCL_OK;
+  const int q = h->rank;
+  const size_t K = (size_t)h->ex_nship;
+  t_begin(h, MCL_K_COMM_P2P);
+  NCCLCHK(h, ncclGroupStart());
+  for (int r = 0; r < h->world; ++r) {
+    if (r == q) continue;
+    u32 lo, hi;
+    ex_range(h, q, r, lo, hi);  // what I hold and r needs
+    // (ONE send and ONE receive per peer: a copy is one record of K doubles, the range a peer needs is contiguous)
+    if (hi > lo) {
+      h->ex_sent += hi - lo;
+      NCCLCHK(h, ncclSend(h->xsend + (size_t)(lo - h->ex_Spre[q]) * K, (size_t)(hi - lo) * K, ncclDouble, r, h->comm, h->stream));
+      ++h->ex_ops;
     }
-    NCCLCHK(h, ncclGroupEnd());
-    t_end(h);
-    return MCL_OK;
+    ex_range(h, r, q, lo, hi);  // what r holds and I need
+    if (hi > lo) {
+      NCCLCHK(h, ncclRecv(h->xrecv + (size_t)(lo - h->ex_Lpre[q]) * K, (size_t)(hi - lo) * K, ncclDouble, r, h->comm, h->stream));
+      ++h->ex_ops;
+    }
   }
-  // LOCAL group: the same ranges as device copies (after every shard has packed)
+  NCCLCHK(h, ncclGroupEnd());
+  t_end(h);
+  return MCL_OK;
+}
+// LOCAL group: the same ranges as device copies (after every shard has packed)
+int exchange_dupes_group(mcl_handle** sh, int ns) {
   for (int s = 0; s < ns; ++s) HIPCHK(sh[s], hipStreamSynchronize(sh[s]->stream));
   for (int d = 0; d < ns; ++d) {
     mcl_handle* D = sh[d];
@@ -558,23 +536,53 @@ int ensure_global_cdf(mcl_handle* h) {
   return MCL_OK;
 }
 
-// reassign gather + resampling noise (+ the sums of update_loc_pose of the new state when with_moments)
-int phase_gather(mcl_handle* h, const double* replay_normals, bool with_moments) {
-  RET_IF(set_device(h));
-  if (replay_normals) RET_IF(upload_replay(h, replay_normals));
-  GatherArgs a;
+// ------------------------------------------------------------------------------------------
+// the gather: reassign + resampling noise (+ the sums of update_loc_pose of the new state when with_moments), planned
+// (plan_gather), then launched (launch_gather), like an MBES update is (mcl_host_update.h: plan_mbes / run_mbes)
+// ------------------------------------------------------------------------------------------
+// the instantiations of k_resample_gather<MOMENTS, UNI, STASH> (mcl_resample.h)
+enum GatherVariant { GK_PLAIN, GK_UNI, GK_MOMENTS, GK_MOMENTS_UNI, GK_STASH };
+struct GatherPlan {
+  GatherArgs args;       // complete except args.visit, which visit_args() fills when `visit`
+  MomentsDest moments;   // where args.sums_out points
+  GatherVariant variant;
+  bool visit;            // the stash kernel also prepares the visiting order, k_visit_scan follows it
+};
+
+// Would the next update read a visiting order of this shard's slots (mcl_kernels.h: VisitArgs), and can the gather
+// prepare one?
+bool visit_order_wanted(const mcl_handle* h, bool replay) {
+  // only the fan sweep and the fan slice's group kernel visit in that order
+  if (replay || !(h->sweep_now || (h->slice_now && h->env_slice_group != 0)) || h->env_visit == 0) return false;
+  // (the sweep gains 17 % of 0.3 ms from it: shards of >= visit_min_n particles; the slice 30 - 45 % of milliseconds --
+  //  its group kernel needs the order --: from 8 192 particles)
+  const bool by_size = h->sweep_now ? h->n >= h->visit_min_n : h->n >= 8192;
+  // (16-bit counts per (workgroup, bin): a workgroup takes whole chunks of RS_BLOCK slots -- at most 63 of them, 64 512
+  //  particles, all of which land in ONE bin on a first gather -- ADVICE r5)
+  return (h->env_visit == 1 || by_size) && h->n <= 63ll * GATHER_MAX_GRID * RS_BLOCK;
+}
+
+// Phase 1: where the gather reads from, where its sums go, which kernel.  Reads the handle; allocates nothing, launches
+// nothing, and changes nothing but visit_ready (the order of the OLD slots is void whatever follows).
+GatherPlan plan_gather(mcl_handle* h, bool with_moments, bool replay) {
+  GatherPlan p{};
+  GatherArgs& a = p.args;
+  static const bool ride_env = !(getenv("MCL_MOMENTS_RIDE") && atoi(getenv("MCL_MOMENTS_RIDE")) == 0);   // (A/B switch, read at the first gather: include/mcl.h)
   const bool multi = h->world > 1 || h->comm;
   const bool p2p = multi && !h->exch_allgather;
+  // ---- source: own state (single shard; O(n) exchange) or the all-gathered one; lost slots of the O(n) exchange read
+  // the packed records they received
   a.src = (multi && !p2p) ? state_ptrs(h->state_glob, h->ng) : state_ptrs(h->state[h->cur], h->n);
   a.recv_mode = p2p ? 1 : 0;
   a.recv_stride = 1;
   a.recv = a.src;
   if (p2p) {   // records of ex_nship doubles (k_pack_dupes): component c is word j of its copy's record
+    int ship[6];
+    const int nship = shipped_components(h->gather_uni_mask, ship);
     a.recv_stride = h->ex_nship;
-    int j = 0;
-    for (int c = 0; c < 6; ++c) {
+    for (int c = 0, j = 0; c < 6; ++c) {
       a.recv.c[c] = h->xrecv + j;
-      if (!((h->gather_uni_mask >> c) & 1u)) ++j;
+      if (j < nship && ship[j] == c) ++j;
     }
   }
   a.shift_dev = p2p ? (const double*)(h->lsx + 1) : nullptr;
@@ -586,112 +594,133 @@ int phase_gather(mcl_handle* h, const double* replay_normals, bool with_moments)
   a.nz = noise_args(h, h->cfg.resample_cov, 2u, h->step_resample);
   a.add_noise = 1;
   a.part = h->part;
-  a.sums_out = h->scal + 32;
-  // one process per GPU, log-likelihood weights: the sums go into the shard's record and travel with the NEXT step's
-  // all-gather (collect_fused_moments reserves their ring entry; a reader that comes first flushes them by an all-reduce)
-  static const bool ride_env = !(getenv("MCL_MOMENTS_RIDE") && atoi(getenv("MCL_MOMENTS_RIDE")) == 0);   // (A/B switch)
-  h->moments_ride = with_moments && ride_env && one_collective(h) && h->shrec && h->host_pin_dev && h->qshift_cur != nullptr;
-  if (h->moments_ride) a.sums_out = (double*)(h->shrec + (size_t)h->rank * SHREC_WORDS + SHREC_MOM);
-  // (single shard: the gather reads straight from the pre-resample state; after a predict z, roll, pitch are the same
-  //  three numbers on every particle, so they are substituted instead of read -- bit-identical, 24 B x N less traffic)
-  a.uni_mask = multi ? h->gather_uni_mask : (h->uni_valid ? 0x1cu : 0u);
-  for (int c = 0; c < 6; ++c) a.uni[c] = (c >= 2 && c <= 4) ? h->uni_val[c - 2] : 0.0;
-  if (with_moments && !multi && h->host_pin_dev) {
-    // single shard: the last block writes the sums straight into the pinned ring entry (no copy command);
-    // the host reads it only after synchronising the stream
-    double* slot = h->host_pin + RING_STRIDE * (h->mean_count % MEAN_RING);
-    slot[16] = 1.0;
-    a.sums_out = h->host_pin_dev + RING_STRIDE * (h->mean_count % MEAN_RING);
-    h->moments_direct = true;
-  } else {
-    h->moments_direct = false;
-  }
   a.ticket = ctrl_u32(h, CTRL_T_GATHER);
-  const double* rp = replay_normals ? h->replay_dev : nullptr;
-  // the visiting order of the NEXT fan sweep / group slice (mcl_kernels.h: VisitArgs)
-  memset(&a.visit, 0, sizeof a.visit);
+  // (sharded: the mask the exchange of THIS resample skipped -- after an overlapped gather uni_valid may say otherwise.
+  //  single shard: the gather reads straight from the pre-resample state; after a predict z, roll, pitch are the same
+  //  three numbers on every particle, so they are substituted instead of read -- bit-identical, 24 B x N less traffic)
+  a.uni_mask = multi ? h->gather_uni_mask : uni_mask(h);
+  for (int c = 0; c < 6; ++c) a.uni[c] = (c >= 2 && c <= 4) ? h->uni_val[c - 2] : 0.0;
+  // ---- the 13 moment sums.  Single shard: the last block writes them straight into the pinned ring entry (no copy
+  // command; the host reads it only after synchronising the stream).  One process per GPU, log-likelihood weights: into
+  // the shard's record, to travel with the NEXT step's all-gather (collect_fused_moments reserves their ring entry; a
+  // reader that comes first flushes them by an all-reduce) -- one_collective() needs a communicator, so never both.
+  p.moments = !with_moments                      ? MOMENTS_SCAL
+              : (!multi && h->host_pin_dev)      ? MOMENTS_RING_DIRECT
+              : (ride_env && one_collective(h) && h->shrec && h->host_pin_dev && h->qshift_cur != nullptr) ? MOMENTS_SHARD_RECORD
+                                                 : MOMENTS_SCAL;
+  a.sums_out = p.moments == MOMENTS_RING_DIRECT    ? h->host_pin_dev + RING_STRIDE * (h->mean_count % MEAN_RING)
+               : p.moments == MOMENTS_SHARD_RECORD ? (double*)(h->shrec + (size_t)h->rank * SHREC_WORDS + SHREC_MOM)
+                                                   : h->scal + 32;
+  // ---- the kernel
   h->visit_ready = false;
+  const bool uni = a.uni_mask == UNI_ZRP;   // z, roll, pitch substituted: the lean kernel
+  const bool order_ok = visit_order_wanted(h, replay);
   // (the stash kernel -- mcl_resample.h -- takes the sums in a second pass: the fused step with resampling noise on
-  //  x, y, yaw only; it also prepares the visiting order)
-  const bool uni = a.uni_mask == 0x1cu;   // z, roll, pitch substituted: the lean kernel
-  // Is a visiting order wanted for the next update?  (the sweep gains 17 % of 0.3 ms from it: shards of >= visit_min_n
-  // particles; the slice 30 - 45 % of milliseconds -- its group kernel needs the order --: from 8 192 particles)
-  const bool by_size = h->sweep_now ? h->n >= h->visit_min_n : h->n >= 8192;
-  const bool order_ok = !rp && (h->sweep_now || (h->slice_now && h->env_slice_group != 0)) && h->env_visit != 0 &&
-                        (h->env_visit == 1 || by_size) && h->n <= 63ll * GATHER_MAX_GRID * RS_BLOCK;   // (16-bit counts per (workgroup, bin): a workgroup takes whole chunks of RS_BLOCK slots -- at most 63 of them, 64 512 particles, all of which land in ONE bin on a first gather -- ADVICE r5)
-  // (also for a plain mcl_resample right after predict + update -- the node's call sequence --: the sums are then a
-  //  by-product nobody reads, the visiting order is what the stash kernel is taken for)
-  const bool want_order = !with_moments && order_ok && h->world == 1 && !h->comm;
-  const bool stash = (with_moments || want_order) && uni && a.nz.sq[2] == 0.0 && a.nz.sq[3] == 0.0 && a.nz.sq[4] == 0.0;
-  const bool visit = stash && order_ok;
-  if (visit) {
-    const int nb = h->visit_nb[0] * h->visit_nb[1] * h->visit_nb[2];
-    if (!h->visit_okey) {
-      HIPCHK(h, hipMalloc(&h->visit_okey, sizeof(u32) * (size_t)h->n));
-      HIPCHK(h, hipMalloc(&h->visit_base, sizeof(u32) * (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS));
-      HIPCHK(h, hipMalloc(&h->visit_cnt, sizeof(unsigned short) * (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS));
-      HIPCHK(h, hipMalloc(&h->visit_desc, sizeof(u64) * (VISIT_MAX_BINS / 64)));
-      HIPCHK(h, hipMemsetAsync(h->visit_desc, 0, sizeof(u64) * (VISIT_MAX_BINS / 64), h->stream));
-      HIPCHK(h, hipMalloc(&h->visit_par, sizeof(VisitPar) * 2));
-      HIPCHK(h, hipMemsetAsync(h->visit_par, 0, sizeof(VisitPar) * 2, h->stream));
-    }
-    a.visit.okey = h->visit_okey;
-    a.visit.cnt = h->visit_cnt;
-    a.visit.base = h->visit_base;
-    a.visit.desc = h->visit_desc;
-    a.visit.epoch = ++h->visit_epoch;
-    a.visit.par_in = h->visit_par + (h->visit_flip & 1u);
-    a.visit.par_out = h->visit_par + ((h->visit_flip & 1u) ^ 1u);
-    h->visit_flip ^= 1u;
-    a.visit.nbx = h->visit_nb[0];
-    a.visit.nby = h->visit_nb[1];
-    a.visit.nbw = h->visit_nb[2];
-    a.visit.nb = nb;
-    a.visit.range = h->visit_range;
-    a.visit.psq[0] = (float)std::sqrt(h->cfg.process_cov[0]);
-    a.visit.psq[1] = (float)std::sqrt(h->cfg.process_cov[1]);
-    a.visit.psq[2] = (float)std::sqrt(h->cfg.process_cov[5]);
-    a.visit.pstep = h->step_predict;
-    {
-      static const bool preview = !(getenv("MCL_VISIT_NOISE") && atoi(getenv("MCL_VISIT_NOISE")) == 0);   // (A/B switch)
-      if (!preview) a.visit.psq[0] = a.visit.psq[1] = a.visit.psq[2] = 0.f;
-    }
-  }
+  //  x, y, yaw only; it also prepares the visiting order.  It is taken for a plain mcl_resample right after predict +
+  //  update too -- the node's call sequence --: the sums are then a by-product nobody reads, the visiting order is what
+  //  it is taken for)
+  const bool for_order_alone = order_ok && h->world == 1 && !h->comm;
+  const bool stash = (with_moments || for_order_alone) && uni && a.nz.sq[2] == 0.0 && a.nz.sq[3] == 0.0 && a.nz.sq[4] == 0.0;
+  p.visit = stash && order_ok;
+  p.variant = stash ? GK_STASH : with_moments ? (uni ? GK_MOMENTS_UNI : GK_MOMENTS) : (uni ? GK_UNI : GK_PLAIN);
+  return p;
+}
+
+int ensure_visit_buffers(mcl_handle* h) {
+  if (h->visit_okey) return MCL_OK;
+  HIPCHK(h, hipMalloc(&h->visit_okey, sizeof(u32) * (size_t)h->n));
+  HIPCHK(h, hipMalloc(&h->visit_base, sizeof(u32) * (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS));
+  HIPCHK(h, hipMalloc(&h->visit_cnt, sizeof(unsigned short) * (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS));
+  HIPCHK(h, hipMalloc(&h->visit_desc, sizeof(u64) * (VISIT_MAX_BINS / 64)));
+  HIPCHK(h, hipMemsetAsync(h->visit_desc, 0, sizeof(u64) * (VISIT_MAX_BINS / 64), h->stream));
+  HIPCHK(h, hipMalloc(&h->visit_par, sizeof(VisitPar) * 2));
+  HIPCHK(h, hipMemsetAsync(h->visit_par, 0, sizeof(VisitPar) * 2, h->stream));
+  return MCL_OK;
+}
+// the visiting order of the NEXT fan sweep / group slice: one epoch and one flip of the parameter pair per launch
+VisitArgs visit_args(mcl_handle* h) {
+  VisitArgs v{};
+  v.okey = h->visit_okey;
+  v.cnt = h->visit_cnt;
+  v.base = h->visit_base;
+  v.desc = h->visit_desc;
+  v.epoch = ++h->visit_epoch;
+  v.par_in = h->visit_par + (h->visit_flip & 1u);
+  v.par_out = h->visit_par + ((h->visit_flip & 1u) ^ 1u);
+  h->visit_flip ^= 1u;
+  v.nbx = h->visit_nb[0];
+  v.nby = h->visit_nb[1];
+  v.nbw = h->visit_nb[2];
+  v.nb = h->visit_nb[0] * h->visit_nb[1] * h->visit_nb[2];
+  v.range = h->visit_range;
+  static const bool preview = !(getenv("MCL_VISIT_NOISE") && atoi(getenv("MCL_VISIT_NOISE")) == 0);   // (A/B switch)
+  static const int xyw[3] = {0, 1, 5};   // x, y, yaw in process_cov
+  for (int k = 0; k < 3; ++k) v.psq[k] = preview ? (float)std::sqrt(h->cfg.process_cov[xyw[k]]) : 0.f;
+  v.pstep = h->step_predict;
+  return v;
+}
+
+// Phase 2: the kernel the plan names (and k_visit_scan behind the stash kernel that prepared an order)
+int launch_gather(mcl_handle* h, const GatherPlan& p, const double* rp) {
+  const GatherArgs& a = p.args;
   t_begin(h, MCL_K_RESAMPLE);
   // one particle per thread up to 256 blocks (= 256 tickets), grid-stride beyond
-  long long gg = (h->n + RS_BLOCK - 1) / RS_BLOCK;
-  gg = gg < 1 ? 1 : (gg > GATHER_MAX_GRID ? GATHER_MAX_GRID : gg);
-  if (stash) {
-    if (!h->gather_attr_set) {   // (more than 64 KiB of dynamic LDS has to be asked for, once per device)
-      HIPCHK(h, hipFuncSetAttribute((const void*)k_resample_gather<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GATHER_STASH_LDS));
-      h->gather_attr_set = true;
-    }
-    k_resample_gather<true, true, true><<<(unsigned)gg, RS_BLOCK, GATHER_STASH_LDS, h->stream>>>(a, rp);
-  } else if (with_moments && uni)
-    k_resample_gather<true, true><<<(unsigned)gg, RS_BLOCK, 0, h->stream>>>(a, rp);
-  else if (with_moments)
-    k_resample_gather<true><<<(unsigned)gg, RS_BLOCK, 0, h->stream>>>(a, rp);
-  else if (uni)
-    k_resample_gather<false, true><<<(unsigned)gg, RS_BLOCK, 0, h->stream>>>(a, rp);
-  else
-    k_resample_gather<false><<<(unsigned)gg, RS_BLOCK, 0, h->stream>>>(a, rp);
-  if (visit) {
+  const unsigned gg = (unsigned)std::min<long long>(std::max<long long>((h->n + RS_BLOCK - 1) / RS_BLOCK, 1), GATHER_MAX_GRID);
+  switch (p.variant) {
+    case GK_STASH:
+      if (!h->gather_attr_set) {   // (more than 64 KiB of dynamic LDS has to be asked for, once per device)
+        HIPCHK(h, hipFuncSetAttribute((const void*)k_resample_gather<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GATHER_STASH_LDS));
+        h->gather_attr_set = true;
+      }
+      k_resample_gather<true, true, true><<<gg, RS_BLOCK, GATHER_STASH_LDS, h->stream>>>(a, rp);
+      break;
+    case GK_MOMENTS_UNI: k_resample_gather<true, true><<<gg, RS_BLOCK, 0, h->stream>>>(a, rp); break;
+    case GK_MOMENTS: k_resample_gather<true><<<gg, RS_BLOCK, 0, h->stream>>>(a, rp); break;
+    case GK_UNI: k_resample_gather<false, true><<<gg, RS_BLOCK, 0, h->stream>>>(a, rp); break;
+    case GK_PLAIN: k_resample_gather<false><<<gg, RS_BLOCK, 0, h->stream>>>(a, rp); break;
+  }
+  if (p.visit) {
     k_visit_scan<<<(unsigned)(a.visit.nb / 64), 1024, 0, h->stream>>>(a.visit, (int)gg, ctrl_u32(h, CTRL_T_VISIT));
     h->visit_ready = true;
   }
   t_end(h);
   HIPCHK(h, hipGetLastError());
-  h->cur ^= 1;
-  h->uni_valid = false;  // (the new state carries resampling noise)
-  h->uni_deferred = false;
-  h->gather_uni_mask = 0u;
-  h->step_resample++;
-  h->have_cdf = true;
-  h->have_lw = false;
-  h->pose_ready = false;
   return MCL_OK;
 }
 
+// Every resample ends here: the other state buffer is the current one, the weights are spent.
+// via_cdf: the systematic pipeline (offspring CDF + gather); else an explicit ancestor vector (run_resample_alt: single
+// shard, separate calls only -- no exchange mask, no deferred stores, no fused pose records to void)
+void finish_resample(mcl_handle* h, bool via_cdf) {
+  h->cur ^= 1;
+  h->step_resample++;
+  h->have_lw = false;
+  h->have_cdf = via_cdf;
+  if (!via_cdf) {
+    h->idx_explicit = true;
+    h->residual_k = -1;
+    return;
+  }
+  h->uni_valid = false;  // (the new state carries resampling noise; run_resample_alt says so before its first launch)
+  h->uni_deferred = false;
+  h->gather_uni_mask = 0u;
+  h->pose_ready = false;
+}
+
+int phase_gather(mcl_handle* h, const double* replay_normals, bool with_moments) {
+  RET_IF(set_device(h));
+  if (replay_normals) RET_IF(upload_replay(h, replay_normals));
+  GatherPlan p = plan_gather(h, with_moments, replay_normals != nullptr);
+  h->moments_dest = p.moments;
+  if (p.moments == MOMENTS_RING_DIRECT) h->host_pin[RING_STRIDE * (h->mean_count % MEAN_RING) + 16] = 1.0;   // (format 1)
+  if (p.visit) {
+    RET_IF(ensure_visit_buffers(h));
+    p.args.visit = visit_args(h);
+  }
+  RET_IF(launch_gather(h, p, replay_normals ? h->replay_dev : nullptr));
+  finish_resample(h, true);
+  return MCL_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // stratified / multinomial / residual (single shard): explicit ancestor vector + generic reassign
@@ -836,12 +865,99 @@ int run_resample_alt(mcl_handle* h, const double* uniforms, long long nu, const 
                                                              replay_normals ? h->replay_dev : nullptr);
   t_end(h);
   HIPCHK(h, hipGetLastError());
-  h->cur ^= 1;
-  h->step_resample++;
-  h->have_cdf = false;
-  h->idx_explicit = true;
-  h->have_lw = false;
-  h->residual_k = -1;
+  finish_resample(h, false);
+  return MCL_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the systematic resample over a set of shards: planned once, then front half -> exchange + expansion -> gather
+// ------------------------------------------------------------------------------------------
+// the u53 of the systematic / naive scheme: the caller's uniform (REPLAY) or the handle's own draw; nullptr or what is
+// wrong with the uniform
+const char* sample_u53(const mcl_config& cfg, uint32_t step, const double* uniforms, long long nu, uint64_t* u53) {
+  if (cfg.rng_mode == MCL_RNG_REPLAY) {
+    if (!uniforms || nu < 1) return "resample: REPLAY mode needs 1 uniform";
+    if (!(uniforms[0] >= 0.0 && uniforms[0] < 1.0)) return "resample: u not in [0,1)";
+    *u53 = (uint64_t)std::floor(uniforms[0] * 9007199254740992.0);
+  } else {
+    *u53 = native_u53(cfg.seed, step);
+  }
+  if (cfg.resample_scheme == MCL_RESAMPLE_NAIVE) *u53 |= MCL_U53_NAIVE;  // ">=" at the CDF edges (mcl_device.h)
+  return nullptr;
+}
+const double* replay_normals_of(const mcl_handle* h, const double* const* replay_normals, int s) {
+  return (replay_normals && h->cfg.rng_mode == MCL_RNG_REPLAY) ? replay_normals[s] : nullptr;
+}
+
+// several handles in one process (the LOCAL test group), or one: alone or one process per GPU
+bool local_group(int ns) { return ns > 1; }
+
+// The front half -- every shard's fixed-point weights, tile offsets and the totals of all shards:
+//   SINGLE                one shard (and few enough tiles for every k_cdf_expand block to add their sums up itself):
+//                         max from the slots -> quantise -> CDF + expansion -> gather, three launches
+//   RANK_ONE_COLLECTIVE   one process per GPU, log-likelihood weights: quantise at the shard's own exponent, ONE
+//                         all-gather of the shards' records, shift (rounds 1-5: all-reduce of the maximum, quantise,
+//                         all-gather of the totals -- two dependent collectives)
+//   RANK_TWO_COLLECTIVES  one process per GPU: the 64 max-lw slots the update kernel filled are all-reduced as they are
+//                         (ordered u64 keys: the maximum of the keys is the key of the maximum) and the quantise kernel
+//                         reads them -- no k_max_finish; then the all-gather of the totals
+//   LOCAL_GROUP           several handles in one process: the same two steps as host copies
+enum ResampleFront { FRONT_SINGLE, FRONT_RANK_ONE_COLLECTIVE, FRONT_RANK_TWO_COLLECTIVES, FRONT_LOCAL_GROUP };
+// The exchange that brings every lost slot its copy:
+//   NONE       single shard: CDF + expansion in one launch, the gather reads the shard's own state
+//   P2P        O(n) per rank: every shard expands its OWN slice, the shards exchange two integers each, and
+//              only the surplus copies whose global positions fall into a peer's lost ranks cross a link
+//   ALLGATHER  MCL_EXCHANGE=allgather: offspring CDF slices and pre-resample state to every shard
+enum ResampleExchange { EXCHANGE_NONE, EXCHANGE_P2P, EXCHANGE_ALLGATHER };
+struct ResamplePlan {
+  ResampleFront front;
+  ResampleExchange exchange;
+  uint64_t u53;
+  bool with_moments;
+};
+ResamplePlan plan_resample(mcl_handle* const* sh, int ns, uint64_t u53, bool with_moments) {
+  const mcl_handle* h0 = sh[0];
+  const ResampleFront front = local_group(ns)                                            ? FRONT_LOCAL_GROUP
+                              : (h0->world == 1 && !h0->comm && h0->ntiles_loc <= 8192) ? FRONT_SINGLE
+                              : one_collective(h0)                                      ? FRONT_RANK_ONE_COLLECTIVE
+                                                                                        : FRONT_RANK_TWO_COLLECTIVES;
+  const ResampleExchange exchange =
+      front == FRONT_SINGLE ? EXCHANGE_NONE : (h0->exch_allgather ? EXCHANGE_ALLGATHER : EXCHANGE_P2P);
+  return ResamplePlan{front, exchange, u53, with_moments};
+}
+
+int front_two_collectives(mcl_handle* h) {
+  RET_IF(set_device(h));
+  t_begin(h, MCL_K_NORMALISE);
+  RET_IF(ensure_max_slots(h));
+  t_end(h);
+  if (h->comm && h->world > 1) {
+    t_begin(h, MCL_K_COMM_RECORDS);
+    NCCLCHK(h, ncclAllReduce(ctrl_slots(h), ctrl_slots(h), MCL_MAX_SLOTS, ncclUint64, ncclMax, h->comm, h->stream));
+    t_end(h);
+  }
+  RET_IF(phase_quantise(h, true));
+  return exchange_totals(h);
+}
+int front_local_group(mcl_handle** sh, int ns) {
+  for (int s = 0; s < ns; ++s) RET_IF(phase_local_max(sh[s]));
+  RET_IF(exchange_max_group(sh, ns));
+  for (int s = 0; s < ns; ++s) RET_IF(phase_quantise(sh[s], false));
+  return exchange_totals_group(sh, ns);
+}
+int exchange_p2p(mcl_handle** sh, int ns, const ResamplePlan& p) {
+  const bool group = p.front == FRONT_LOCAL_GROUP;
+  bool packed = false;   // (exchange_ls queued the pack behind the publish; LOCAL groups pack after it)
+  for (int s = 0; s < ns; ++s) RET_IF(phase_expand_local(sh[s], p.u53));
+  RET_IF(group ? exchange_ls_group(sh, ns) : exchange_ls(sh[0], &packed));
+  for (int s = 0; s < ns; ++s) RET_IF(phase_pack(sh[s], packed));
+  return group ? exchange_dupes_group(sh, ns) : exchange_dupes(sh[0]);
+}
+int exchange_allgather(mcl_handle** sh, int ns, const ResamplePlan& p) {
+  for (int s = 0; s < ns; ++s) RET_IF(phase_cdf(sh[s], p.u53));
+  RET_IF(p.front == FRONT_LOCAL_GROUP ? exchange_cdf_state_group(sh, ns) : exchange_cdf_state(sh[0]));
+  for (int s = 0; s < ns; ++s) sh[s]->cdf_global = true;
+  for (int s = 0; s < ns; ++s) RET_IF(phase_expand(sh[s], false, 0));
   return MCL_OK;
 }
 
@@ -857,75 +973,29 @@ int run_resample(mcl_handle** sh, int ns, const double* uniforms, long long nu,
     }
   }
   uint64_t u53;
-  if (h0->cfg.rng_mode == MCL_RNG_REPLAY) {
-    if (!uniforms || nu < 1) return fail(h0, MCL_ERR_INVALID, "resample: REPLAY mode needs 1 uniform");
-    if (!(uniforms[0] >= 0.0 && uniforms[0] < 1.0)) return fail(h0, MCL_ERR_INVALID, "resample: u not in [0,1)");
-    u53 = (uint64_t)std::floor(uniforms[0] * 9007199254740992.0);
-  } else {
-    u53 = native_u53(h0->cfg.seed, h0->step_resample);
+  if (const char* bad = sample_u53(h0->cfg, h0->step_resample, uniforms, nu, &u53)) return fail(h0, MCL_ERR_INVALID, bad);
+  const ResamplePlan p = plan_resample(sh, ns, u53, with_moments);
+  // (the peers a lazy global CDF reads its slices from -- ensure_global_cdf --: none unless this is a LOCAL group)
+  for (int s = 0; s < ns; ++s) sh[s]->group.assign(sh, sh + (p.front == FRONT_LOCAL_GROUP ? ns : 0));
+  switch (p.front) {
+    case FRONT_SINGLE:
+      h0->cdf_global = true;
+      RET_IF(phase_quantise(h0, true, true));
+      break;
+    case FRONT_RANK_ONE_COLLECTIVE:
+      RET_IF(phase_quantise_shard(h0));
+      RET_IF(exchange_shard_records(h0));
+      RET_IF(phase_shift_scan(h0));   // (also delivers the moments the LAST fused step left in the records: mom_pending)
+      break;
+    case FRONT_RANK_TWO_COLLECTIVES: RET_IF(front_two_collectives(h0)); break;
+    case FRONT_LOCAL_GROUP: RET_IF(front_local_group(sh, ns)); break;
   }
-  if (h0->cfg.resample_scheme == MCL_RESAMPLE_NAIVE) u53 |= MCL_U53_NAIVE;  // ">=" at the CDF edges (mcl_device.h)
-  // one shard (and few enough tiles for every k_cdf_expand block to add their sums up itself):
-  // max from the slots -> quantise -> CDF + expansion -> gather, three launches
-  const bool single = ns == 1 && h0->world == 1 && !h0->comm && h0->ntiles_loc <= 8192;
-  if (single) {
-    h0->cdf_global = true;
-    h0->group.clear();
-    RET_IF(phase_quantise(h0, true, true));
-    RET_IF(phase_expand(h0, true, u53));
-    return phase_gather(h0, (replay_normals && h0->cfg.rng_mode == MCL_RNG_REPLAY) ? replay_normals[0] : nullptr,
-                        with_moments);
+  switch (p.exchange) {
+    case EXCHANGE_NONE: RET_IF(phase_expand(h0, true, p.u53)); break;
+    case EXCHANGE_P2P: RET_IF(exchange_p2p(sh, ns, p)); break;
+    case EXCHANGE_ALLGATHER: RET_IF(exchange_allgather(sh, ns, p)); break;
   }
-  if (ns == 1 && one_collective(h0)) {
-    // one process per GPU, log-likelihood weights: quantise at the shard's own exponent, ONE all-gather of the shards'
-    // records, shift (rounds 1-5: all-reduce of the maximum, quantise, all-gather of the totals -- two dependent
-    // collectives)
-    h0->group.clear();
-    RET_IF(phase_quantise_shard(h0));
-    RET_IF(exchange_shard_records(h0));
-    RET_IF(phase_shift_scan(h0));
-  } else if (ns == 1) {
-    // one process per GPU: the 64 max-lw slots the update kernel filled are all-reduced as they are (ordered u64
-    // keys: the maximum of the keys is the key of the maximum) and the quantise kernel reads them -- no k_max_finish
-    h0->group.clear();
-    RET_IF(set_device(h0));
-    t_begin(h0, MCL_K_NORMALISE);
-    RET_IF(ensure_max_slots(h0));
-    t_end(h0);
-    if (h0->comm && h0->world > 1) {
-      t_begin(h0, MCL_K_COMM_RECORDS);
-      NCCLCHK(h0, ncclAllReduce(ctrl_slots(h0), ctrl_slots(h0), MCL_MAX_SLOTS, ncclUint64, ncclMax, h0->comm, h0->stream));
-      t_end(h0);
-    }
-    RET_IF(phase_quantise(h0, true));
-  } else {
-    for (int s = 0; s < ns; ++s) {
-      sh[s]->group.assign(sh, sh + ns);
-      RET_IF(phase_local_max(sh[s]));
-    }
-    RET_IF(exchange_max(sh, ns));
-    for (int s = 0; s < ns; ++s) RET_IF(phase_quantise(sh[s], false));
-  }
-  if (!(ns == 1 && one_collective(h0))) RET_IF(exchange_totals(sh, ns));
-  if (!h0->exch_allgather) {
-    // O(n) per rank: every shard expands its OWN slice, the shards exchange two integers each, and only
-    // the surplus copies whose global positions fall into a peer's lost ranks cross a link
-    for (int s = 0; s < ns; ++s) RET_IF(phase_expand_local(sh[s], u53));
-    RET_IF(exchange_ls(sh, ns));
-    for (int s = 0; s < ns; ++s) RET_IF(phase_pack(sh[s], ns == 1 && sh[s]->lsx_host_dev != nullptr));
-    RET_IF(exchange_dupes(sh, ns));
-    for (int s = 0; s < ns; ++s)
-      RET_IF(phase_gather(sh[s], (replay_normals && sh[s]->cfg.rng_mode == MCL_RNG_REPLAY) ? replay_normals[s] : nullptr,
-                          with_moments));
-    return MCL_OK;
-  }
-  for (int s = 0; s < ns; ++s) RET_IF(phase_cdf(sh[s], u53));
-  RET_IF(exchange_cdf_state(sh, ns));
-  for (int s = 0; s < ns; ++s) sh[s]->cdf_global = true;
-  for (int s = 0; s < ns; ++s) RET_IF(phase_expand(sh[s], false, 0));
-  for (int s = 0; s < ns; ++s)
-    RET_IF(phase_gather(sh[s], (replay_normals && sh[s]->cfg.rng_mode == MCL_RNG_REPLAY) ? replay_normals[s] : nullptr,
-                        with_moments));
+  for (int s = 0; s < ns; ++s) RET_IF(phase_gather(sh[s], replay_normals_of(sh[s], replay_normals, s), p.with_moments));
   return MCL_OK;
 }
 

@@ -769,6 +769,9 @@ int run_mbes(mcl_handle* h, const MbesPlan& p, bool pose_done) {
   } seq_guard{h};
   t_begin(h, MCL_K_UPDATE_MBES);
   if (!pose_done) RET_IF(run_pose(h, p, a));
+  // (the cast kernels leave max lw in slot set 0.  Said here, before they are queued, and again by the caller's
+  //  weights_written once they all are: an error return in between leaves max_valid set beside the weights of the
+  //  update before -- as it always has; a caller that goes on after such an error writes new weights first)
   if (a.max_slots) {
     h->max_valid = true;
     h->slot_set = 0;
