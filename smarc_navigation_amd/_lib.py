@@ -1,4 +1,4 @@
-"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h and mcl_map.h).
+"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h and mcl_recovery.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -44,6 +44,19 @@ class DrOdom(C.Structure):
 
 class Timing(C.Structure):
     _fields_ = [('ms', C.c_double * len(MCL_K_NAMES)), ('launches', C.c_int64 * len(MCL_K_NAMES))]
+
+
+class Box(C.Structure):
+    """mcl_box (include/mcl_recovery.h); frame: 0 = odom, 1 = map"""
+    _fields_ = [('x_min', C.c_double), ('x_max', C.c_double), ('y_min', C.c_double), ('y_max', C.c_double),
+                ('yaw_min', C.c_double), ('yaw_max', C.c_double), ('frame', C.c_int32)]
+
+
+class WStats(C.Structure):
+    """mcl_wstats (include/mcl_recovery.h)"""
+    _fields_ = [('n', C.c_int64), ('n_live', C.c_int64), ('argmax_gid', C.c_int64), ('max_lw', C.c_double),
+                ('sum_w', C.c_double), ('sum_w2', C.c_double), ('n_eff', C.c_double), ('log_mean_lik', C.c_double),
+                ('map_pose', C.c_double * 6)]
 
 
 # every symbol include/mcl.h, mcl_dr.h and mcl_map.h declare: name -> (restype, argtypes)
@@ -128,6 +141,16 @@ SYMBOLS = {
     'mcl_gridmap_finalize': (C.c_int, [_vp, _i32, _vp, C.POINTER(C.c_int64), _vp]),
 }
 
+# include/mcl_recovery.h: global localisation and kidnap recovery (a table of its own: SYMBOLS is exactly what the three
+# headers above declare)
+RECOVERY_SYMBOLS = {
+    'mcl_map_bounds': (C.c_int, [_vp, _vp]),
+    'mcl_init_particles_uniform': (C.c_int, [_vp, C.POINTER(Box), _vp]),
+    'mcl_weight_stats': (C.c_int, [_vp, C.POINTER(WStats)]),
+    'mcl_weight_stats_merge': (C.c_int, [C.POINTER(WStats), _i32, C.POINTER(WStats)]),
+    'mcl_inject_uniform': (C.c_int, [_vp, _d, C.POINTER(Box), _vp, C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -140,7 +163,7 @@ def load():
         raise ImportError('libmcl_hip.so not built (%s): the MCL hot path has no fallback; run '
                           '__graft_entry__.build()' % SO_PATH)
     lib = C.CDLL(SO_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

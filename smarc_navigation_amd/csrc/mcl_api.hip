@@ -6,6 +6,8 @@
 #include "mcl_host_resample.h"
 #include "mcl_host_moments.h"
 #include "mcl_host_update.h"
+// global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
+#include "mcl_recovery.h"
 
 
 // dead-reckoning integrator (host only; uses euler_from_quat above)
@@ -180,7 +182,8 @@ int mcl_destroy(mcl_handle* h) {
   void* bufs[] = {h->state[0], h->state[1], h->state_glob, h->lw, h->wnorm, h->q, h->ncum, h->zcum, h->zr, h->dupes32, h->desc, h->ctrl,
                   h->tile64, h->tile32, h->part, h->scal, h->totals, h->idx, h->replay_dev, h->pose7,
                   h->beam_sc, h->ranges_dev, h->exp_dev, h->grid, h->pose_dev, h->mbes_worklist, h->mbes_groups, h->sort_keys, h->sort_keys_out, h->sort_idx, h->mbes_perm, h->sort_tmp, h->sweep_buf[0], h->sweep_buf[1], h->defer_idx, h->defer2_idx, h->visit_okey, h->visit_base, h->visit_cnt, h->visit_desc, h->visit_par, h->slice_loose, h->reasons_dev, h->grid_pad, h->lm_worklist, h->cq, h->u53, h->cnt, h->first,
-                  h->flags, h->fcum, h->copies, h->ccum, h->dupes, h->cs, h->chunk, h->uni_dev, h->lsx, h->xsend, h->xrecv, h->shrec, h->tile_bits};
+                  h->flags, h->fcum, h->copies, h->ccum, h->dupes, h->cs, h->chunk, h->uni_dev, h->lsx, h->xsend, h->xrecv, h->shrec, h->tile_bits,
+                  h->wstats_dev, h->inject_cnt};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (h->mesh) mesh_free(h->mesh);
@@ -228,6 +231,7 @@ int mcl_init_particles(mcl_handle* h, const double* replay_normals) {
   HIPCHK(h, hipGetLastError());
   h->step_predict = 0;
   h->step_resample = 0;
+  h->step_inject = 0;
   h->have_lw = h->have_cdf = false;
   return MCL_OK;
 }
@@ -301,6 +305,10 @@ int mcl_set_map_grid(mcl_handle* h, const float* z, int32_t nx, int32_t ny, doub
     h->gslope_max = std::sqrt(g2) / res;
   }
   h->map_kind = 0;
+  h->map_xy[0] = ox;
+  h->map_xy[1] = ox + (nx - 1) * res;
+  h->map_xy[2] = oy;
+  h->map_xy[3] = oy + (ny - 1) * res;
   return MCL_OK;
 }
 
@@ -323,6 +331,18 @@ int mcl_set_map_mesh_ex(mcl_handle* h, const float* verts, int64_t nv, const uin
     return rc;
   }
   h->map_kind = 1;
+  {
+    double lo[2] = {verts[0], verts[1]}, hi[2] = {verts[0], verts[1]};
+    for (int64_t i = 1; i < nv; ++i)
+      for (int c = 0; c < 2; ++c) {
+        lo[c] = std::min(lo[c], (double)verts[3 * i + c]);
+        hi[c] = std::max(hi[c], (double)verts[3 * i + c]);
+      }
+    h->map_xy[0] = lo[0];
+    h->map_xy[1] = hi[0];
+    h->map_xy[2] = lo[1];
+    h->map_xy[3] = hi[1];
+  }
   h->mesh_heightfield = (flags & MCL_MESH_HEIGHTFIELD) != 0;
   h->force_general_mesh = (flags & (MCL_MESH_GENERAL | MCL_MESH_UNSTRUCTURED)) != 0;
   h->mesh_no_sweep = (flags & MCL_MESH_GENERAL) != 0;
@@ -1300,6 +1320,158 @@ int mcl_mbes_visit_order(mcl_handle* h, uint32_t* slots, int32_t* sorted) {
   std::vector<MbesPose> rec((size_t)h->n);
   HIPCHK(h, hipMemcpy(rec.data(), h->pose_dev, sizeof(MbesPose) * (size_t)h->n, hipMemcpyDeviceToHost));
   for (long long i = 0; i < h->n; ++i) slots[i] = rec[(size_t)i].slot;
+  return MCL_OK;
+}
+
+// ---- global localisation and kidnap recovery (include/mcl_recovery.h)
+namespace {
+// the argument block of k_uniform_state from a caller's box: bounds checked, the MAP frame resolved against cfg.m2o
+int uniform_args(mcl_handle* h, const mcl_box* box, uint32_t purpose, uint32_t step, const char* who, UniformArgs& a) {
+  const std::string w(who);
+  const double b[6] = {box->x_min, box->x_max, box->y_min, box->y_max, box->yaw_min, box->yaw_max};
+  for (int c = 0; c < 3; ++c) {
+    if (!std::isfinite(b[2 * c]) || !std::isfinite(b[2 * c + 1])) return fail(h, MCL_ERR_INVALID, w + ": a bound of the box is not finite");
+    if (b[2 * c + 1] < b[2 * c]) return fail(h, MCL_ERR_INVALID, w + ": a maximum of the box lies below its minimum");
+  }
+  if (box->yaw_max - box->yaw_min > 2.0 * MCL_PI) return fail(h, MCL_ERR_INVALID, w + ": the yaw interval is longer than 2 pi");
+  if (box->frame != MCL_FRAME_ODOM && box->frame != MCL_FRAME_MAP) return fail(h, MCL_ERR_INVALID, w + ": unknown frame");
+  memset(&a, 0, sizeof a);
+  for (int c = 0; c < 3; ++c) {
+    a.lo[c] = b[2 * c];
+    a.hi[c] = b[2 * c + 1];
+    a.w[c] = b[2 * c + 1] - b[2 * c];
+  }
+  if (box->frame == MCL_FRAME_MAP) {
+    const double* m = h->cfg.m2o;
+    if (std::fabs(m[2]) > 1e-12 || std::fabs(m[6]) > 1e-12 || std::fabs(m[8]) > 1e-12 || std::fabs(m[9]) > 1e-12 ||
+        std::fabs(m[10] - 1.0) > 1e-12)
+      return fail(h, MCL_ERR_UNSUPPORTED, w + ": a box in the map frame needs an m2o that turns about z alone");
+    a.r00 = m[0];
+    a.r01 = m[1];
+    a.r10 = m[4];
+    a.r11 = m[5];
+    a.tx = m[3];
+    a.ty = m[7];
+    a.theta = std::atan2(m[4], m[0]);
+    a.xform = !(m[0] == 1.0 && m[1] == 0.0 && m[4] == 0.0 && m[5] == 1.0 && m[3] == 0.0 && m[7] == 0.0);
+  }
+  a.k0 = (uint32_t)h->cfg.seed;
+  a.k1 = (uint32_t)(h->cfg.seed >> 32);
+  a.step = step;
+  a.purpose = purpose;
+  a.gid0 = h->goff;
+  return MCL_OK;
+}
+// REPLAY uniforms (n x per doubles, per <= 6) into the replay buffer
+int upload_replay_uniforms(mcl_handle* h, const double* u, int per) {
+  if (!h->replay_dev) HIPCHK(h, hipMalloc(&h->replay_dev, sizeof(double) * 6 * (size_t)h->n));
+  return upload(h, h->replay_dev, u, sizeof(double) * (size_t)per * (size_t)h->n);
+}
+}  // namespace
+
+int mcl_map_bounds(mcl_handle* h, double xy_min_max[4]) {
+  if (!h || !xy_min_max) return MCL_ERR_INVALID;
+  if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "map_bounds: no map (call mcl_set_map_grid/mesh first)");
+  for (int k = 0; k < 4; ++k) xy_min_max[k] = h->map_xy[k];
+  return MCL_OK;
+}
+
+int mcl_init_particles_uniform(mcl_handle* h, const mcl_box* box, const double* replay_uniforms) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!box) return fail(h, MCL_ERR_INVALID, "init_particles_uniform: null box");
+  RET_IF(set_device(h));
+  UniformArgs a;
+  RET_IF(uniform_args(h, box, 5u, 0u, "init_particles_uniform", a));
+  const double* rp = nullptr;
+  if (h->cfg.rng_mode == MCL_RNG_REPLAY) {
+    if (!replay_uniforms) return fail(h, MCL_ERR_INVALID, "init_particles_uniform: REPLAY mode needs n x 3 uniforms");
+    RET_IF(upload_replay_uniforms(h, replay_uniforms, 3));
+    rp = h->replay_dev;
+  }
+  RET_IF(cancel_state_gather(h));
+  h->uni_valid = false;
+  h->visit_ready = false;
+  t_begin(h, MCL_K_NOISE);
+  k_uniform_state<false><<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, rp, nullptr);
+  t_end(h);
+  HIPCHK(h, hipGetLastError());
+  h->step_predict = 0;
+  h->step_resample = 0;
+  h->step_inject = 0;
+  h->have_lw = h->have_cdf = false;
+  return MCL_OK;
+}
+
+int mcl_weight_stats(mcl_handle* h, mcl_wstats* out) {
+  if (!h || !out) return MCL_ERR_INVALID;
+  if (!h->have_lw) return fail(h, MCL_ERR_STATE, "weight_stats: no log-weights (call an update first)");
+  RET_IF(set_device(h));
+  const long long ntiles = (h->n + WS_TILE - 1) / WS_TILE;
+  if (!h->wstats_dev) HIPCHK(h, hipMalloc(&h->wstats_dev, sizeof(double) * WS_OUT_WORDS + sizeof(WsPartial) * (size_t)ntiles));
+  WsPartial* part = reinterpret_cast<WsPartial*>(h->wstats_dev + WS_OUT_WORDS);
+  t_begin(h, MCL_K_NORMALISE);
+  k_wstats_partial<<<(unsigned)ntiles, MCL_BLOCK, 0, h->stream>>>(h->lw, h->n, h->goff, part);
+  k_wstats_final<<<1, MCL_BLOCK, 0, h->stream>>>(part, ntiles, state_ptrs(h->state[h->cur], h->n), h->goff, h->wstats_dev);
+  t_end(h);
+  HIPCHK(h, hipGetLastError());
+  double r[11];
+  HIPCHK(h, hipMemcpyAsync(r, h->wstats_dev, sizeof r, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int64_t words[2];
+  memcpy(words, r + 3, sizeof words);
+  out->n = h->n;
+  out->n_live = words[1];
+  out->argmax_gid = words[0];
+  out->max_lw = r[0];
+  out->sum_w = r[1];
+  out->sum_w2 = r[2];
+  for (int c = 0; c < 6; ++c) out->map_pose[c] = r[5 + c];
+  wstats_finish(out);
+  return MCL_OK;
+}
+
+int mcl_weight_stats_merge(const mcl_wstats* parts, int32_t n_parts, mcl_wstats* out) {
+  return weight_stats_merge_impl(parts, n_parts, out);
+}
+
+int mcl_inject_uniform(mcl_handle* h, double fraction, const mcl_box* box, const double* replay_uniforms,
+                       int64_t* n_injected) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!box) return fail(h, MCL_ERR_INVALID, "inject_uniform: null box");
+  if (!(fraction >= 0.0 && fraction <= 1.0)) return fail(h, MCL_ERR_INVALID, "inject_uniform: fraction outside [0, 1]");
+  if (h->have_lw) return fail(h, MCL_ERR_STATE, "inject_uniform: log-weights pending (resample first: they describe the particles as they are)");
+  RET_IF(set_device(h));
+  UniformArgs a;
+  RET_IF(uniform_args(h, box, 6u, h->step_inject, "inject_uniform", a));
+  a.fraction = fraction;
+  if (h->cfg.rng_mode == MCL_RNG_REPLAY && !replay_uniforms)
+    return fail(h, MCL_ERR_INVALID, "inject_uniform: REPLAY mode needs n x 4 uniforms");
+  if (fraction == 0.0) {
+    if (n_injected) *n_injected = 0;
+    return MCL_OK;
+  }
+  const double* rp = nullptr;
+  if (h->cfg.rng_mode == MCL_RNG_REPLAY) {
+    RET_IF(upload_replay_uniforms(h, replay_uniforms, 4));
+    rp = h->replay_dev;
+  }
+  if (!h->inject_cnt) HIPCHK(h, hipMalloc(&h->inject_cnt, sizeof(u64) * (1 + MCL_MAX_GRID)));
+  RET_IF(cancel_state_gather(h));
+  h->uni_valid = false;
+  h->visit_ready = false;
+  const int grid = grid_for(h->n);
+  t_begin(h, MCL_K_NOISE);
+  k_uniform_state<true><<<grid, MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, rp, h->inject_cnt + 1);
+  if (n_injected) k_count_final<<<1, MCL_BLOCK, 0, h->stream>>>(h->inject_cnt + 1, grid, h->inject_cnt);
+  t_end(h);
+  HIPCHK(h, hipGetLastError());
+  h->step_inject++;
+  if (n_injected) {
+    u64 cnt = 0;
+    HIPCHK(h, hipMemcpyAsync(&cnt, h->inject_cnt, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_injected = (int64_t)cnt;
+  }
   return MCL_OK;
 }
 

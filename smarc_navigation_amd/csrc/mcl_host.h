@@ -200,6 +200,11 @@ struct mcl_handle {
   int weight_mode = 0;
   bool have_lw = false, have_cdf = false, have_meancov = false;
   uint32_t step_predict = 0, step_resample = 0;
+  // global localisation / recovery (include/mcl_recovery.h)
+  uint32_t step_inject = 0;       // Philox step of the next mcl_inject_uniform; reset by both init calls
+  double map_xy[4] = {0, 0, 0, 0};  // footprint of the map (x_min, x_max, y_min, y_max; MAP frame), valid while map_kind >= 0
+  double* wstats_dev = nullptr;   // weight statistics: WS_OUT_WORDS result words, then one 32-byte record per tile (lazily)
+  u64* inject_cnt = nullptr;      // injection: the replaced-particle total, then one count per workgroup (lazily)
   bool timing = false;
   std::vector<TimedRegion> regions;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

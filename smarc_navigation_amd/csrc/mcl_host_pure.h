@@ -1,5 +1,6 @@
 // mcl_host_pure.h -- the host arithmetic of libmcl_hip.so that touches no device: tf.transformations' Euler /
-// quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf.  No HIP header: the
+// quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
+// weight statistics.  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mcl.h"
+#include "../../include/mcl_recovery.h"
 
 namespace {
 
@@ -110,6 +112,48 @@ int exchange_plan_impl(int32_t world, const uint32_t* lost, const uint32_t* surp
     recv_off[r] = lo - Lpre[rank];
     recv_cnt[r] = hi - lo;
   }
+  return MCL_OK;
+}
+
+// n_eff and log_mean_lik of mcl_wstats from its sums: the ONE place that forms them (mcl_weight_stats and the merge)
+void wstats_finish(mcl_wstats* s) {
+  const bool any = s->argmax_gid >= 0 && s->sum_w2 > 0.0;
+  s->n_eff = any ? (s->sum_w * s->sum_w) / s->sum_w2 : 0.0;
+  s->log_mean_lik = any && s->n > 0 ? s->max_lw + std::log(s->sum_w / (double)s->n) : -INFINITY;
+}
+
+// mcl_weight_stats_merge (include/mcl_recovery.h): statistics of the union of the parts, in the order given
+int weight_stats_merge_impl(const mcl_wstats* parts, int32_t n_parts, mcl_wstats* out) {
+  if (!parts || !out || n_parts < 1) return MCL_ERR_INVALID;
+  int win = -1;   // the part that holds the maximum: the largest max_lw, the lowest id among equal ones
+  for (int p = 0; p < n_parts; ++p) {
+    if (parts[p].n < 0 || parts[p].n_live < 0 || parts[p].n_live > parts[p].n) return MCL_ERR_INVALID;
+    if (parts[p].argmax_gid < 0) continue;   // nothing finite in this part
+    if (win < 0 || parts[p].max_lw > parts[win].max_lw ||
+        (parts[p].max_lw == parts[win].max_lw && parts[p].argmax_gid < parts[win].argmax_gid))
+      win = p;
+  }
+  mcl_wstats r;
+  r.n = r.n_live = 0;
+  r.argmax_gid = -1;
+  r.max_lw = -INFINITY;
+  r.sum_w = r.sum_w2 = 0.0;
+  for (int c = 0; c < 6; ++c) r.map_pose[c] = 0.0;
+  if (win >= 0) {
+    r.argmax_gid = parts[win].argmax_gid;
+    r.max_lw = parts[win].max_lw;
+    for (int c = 0; c < 6; ++c) r.map_pose[c] = parts[win].map_pose[c];
+  }
+  for (int p = 0; p < n_parts; ++p) {
+    r.n += parts[p].n;
+    r.n_live += parts[p].n_live;
+    if (parts[p].argmax_gid < 0) continue;
+    const double f = std::exp(parts[p].max_lw - r.max_lw);   // (exactly 1 for the winning part)
+    r.sum_w += parts[p].sum_w * f;
+    r.sum_w2 += parts[p].sum_w2 * (f * f);
+  }
+  wstats_finish(&r);
+  *out = r;
   return MCL_OK;
 }
 

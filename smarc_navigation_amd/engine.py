@@ -1,6 +1,7 @@
 """Thin Python wrapper over the C ABI handle (include/mcl.h).  numpy in / numpy out; all compute
 runs in libmcl_hip.so on the GPU."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -10,6 +11,7 @@ from ._lib import Config, Odom, Timing, MclError  # noqa: F401
 SYSTEMATIC, RESIDUAL, STRATIFIED, MULTINOMIAL, NAIVE = 0, 1, 2, 3, 4
 RNG_NATIVE, RNG_REPLAY = 0, 1
 WEIGHT_LINEAR_FLOOR, WEIGHT_LOG_SHIFT, WEIGHT_LINEAR = 0, 1, 2
+FRAME_ODOM, FRAME_MAP = 0, 1
 
 
 def _ptr(a):
@@ -22,6 +24,40 @@ def _f64(a):
 
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+class WeightStats(object):
+    """mcl_wstats as a Python object: n, n_live, argmax_gid, max_lw, sum_w, sum_w2, n_eff, log_mean_lik, map_pose (6)."""
+    FIELDS = ('n', 'n_live', 'argmax_gid', 'max_lw', 'sum_w', 'sum_w2', 'n_eff', 'log_mean_lik')
+
+    def __init__(self, c):
+        for f in self.FIELDS:
+            setattr(self, f, getattr(c, f))
+        self.map_pose = np.array(c.map_pose[:], dtype=np.float64)
+
+    def as_c(self):
+        c = _lib.WStats()
+        for f in self.FIELDS:
+            setattr(c, f, getattr(self, f))
+        c.map_pose[:] = [float(x) for x in self.map_pose]
+        return c
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f in self.FIELDS}
+        d['map_pose'] = self.map_pose.tolist()
+        return d
+
+    def __repr__(self):
+        return 'WeightStats(%r)' % (self.as_dict(),)
+
+
+def make_box(xy, yaw=(-math.pi, math.pi), frame='map'):
+    """mcl_box from (x_min, x_max, y_min, y_max), a yaw interval and 'map' / 'odom' (or FRAME_MAP / FRAME_ODOM)"""
+    b = _lib.Box()
+    b.x_min, b.x_max, b.y_min, b.y_max = [float(v) for v in xy]
+    b.yaw_min, b.yaw_max = float(yaw[0]), float(yaw[1])
+    b.frame = {'odom': FRAME_ODOM, 'map': FRAME_MAP}.get(frame, frame)
+    return b
 
 
 def make_odom(v, wz, q, z, stamp=0.0):
@@ -77,6 +113,41 @@ class Engine(object):
     def init_particles(self, normals=None):
         nz = _f64(normals)
         self._ck(self.lib.mcl_init_particles(self.h, _ptr(nz)))
+
+    # ---- global localisation and kidnap recovery (include/mcl_recovery.h)
+    def map_bounds(self):
+        """(x_min, x_max, y_min, y_max) of the map set by set_map_grid / set_map_mesh, map frame"""
+        b = np.zeros(4)
+        self._ck(self.lib.mcl_map_bounds(self.h, _ptr(b)))
+        return tuple(float(v) for v in b)
+
+    def _box(self, box, frame, yaw):
+        if isinstance(box, _lib.Box):
+            return box
+        if box is None:   # the map's footprint: map-frame numbers whatever `frame` says
+            return make_box(self.map_bounds(), yaw, 'map')
+        return make_box(box, yaw, frame)
+
+    def init_particles_uniform(self, box=None, frame='map', yaw=(-math.pi, math.pi), uniforms=None):
+        """x, y, yaw uniform in the box (x_min, x_max, y_min, y_max) x yaw; box=None: the map's footprint.
+        uniforms: n x 3 in [0, 1) (REPLAY mode)."""
+        b, u = self._box(box, frame, yaw), _f64(uniforms)
+        self._ck(self.lib.mcl_init_particles_uniform(self.h, C.byref(b), _ptr(u)))
+
+    def weight_stats(self):
+        """statistics of the log-weights the last update left (before they are resampled away): a WeightStats"""
+        c = _lib.WStats()
+        self._ck(self.lib.mcl_weight_stats(self.h, C.byref(c)))
+        return WeightStats(c)
+
+    def inject_uniform(self, fraction, box=None, frame='map', yaw=(-math.pi, math.pi), uniforms=None, count=True):
+        """replace the particles whose selection draw is < fraction by uniform draws from the box (box=None: the map's
+        footprint); returns the number replaced, or None with count=False (the call then does not wait for the GPU).
+        uniforms: n x 4 in [0, 1) (REPLAY mode)."""
+        b, u = self._box(box, frame, yaw), _f64(uniforms)
+        k = C.c_int64(0)
+        self._ck(self.lib.mcl_inject_uniform(self.h, float(fraction), C.byref(b), _ptr(u), C.byref(k) if count else None))
+        return int(k.value) if count else None
 
     def predict(self, v, wz, q, z, dt, normals=None, stamp=0.0):
         nz = _f64(normals)
@@ -306,6 +377,15 @@ def comm_unique_id():
     buf = C.create_string_buffer(128)
     _lib.check(lib.mcl_comm_unique_id(buf))
     return buf.raw
+
+
+def merge_weight_stats(parts):
+    """statistics of the union of several shards' WeightStats, in the order given (mcl_weight_stats_merge: host only)"""
+    lib = _lib.load()
+    arr = (_lib.WStats * len(parts))(*[p.as_c() if isinstance(p, WeightStats) else p for p in parts])
+    out = _lib.WStats()
+    _lib.check(lib.mcl_weight_stats_merge(arr, len(parts), C.byref(out)))
+    return WeightStats(out)
 
 
 def group_resample(engines, uniforms=None, normals_per_shard=None):

@@ -291,6 +291,62 @@ def replay_bag(path, params=None, m2o=None, utm2map=None, grid=None, mesh=None, 
     return dict(pf_xyz=pf_xyz, pf_stamp=np.array(pf_stamp), counts=counts, summary=summary, node=pf)
 
 
+def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=1.0, m2o=None, yaw=(-np.pi, np.pi),
+                   process_cov=(0.01, 0.01, 0, 0, 0, 1e-4), resample_cov=(0.04, 0.04, 0, 0, 0, 1e-3), alpha_slow=0.001,
+                   alpha_fast=0.1, max_fraction=0.1, inject=True):
+    """Global localisation with kidnap recovery on a recorded stream (--recover): the cloud starts uniform over the map's
+    footprint, and every ping runs the separate calls  predict ... -> update_mbes -> weight_stats -> resample ->
+    inject_uniform(fraction)  with the fraction of recovery.AugmentedMCL (the likelihood per valid beam, a short-term
+    against a long-term average).  The node class is not involved.  Returns dict(pf_xyz[m,3] mean pose after every ping,
+    pub_idx, fractions[m], injected[m], log_lik_per_beam[m], n_eff[m], summary)."""
+    from . import engine as eng
+    from . import recovery
+    if 'mbes_idx' not in stream or (grid is None and mesh is None):
+        raise ValueError('replay_recover: needs a stream with MBES pings and a map')
+    e = eng.Engine(int(particles), process_cov=process_cov, resample_cov=resample_cov, m2o=m2o, seed=seed)
+    if grid is not None:
+        e.set_map_grid(grid['z'], grid['origin'], float(grid['res']))
+    else:
+        e.set_map_mesh(mesh['verts'], mesh['tris'])
+    e.init_particles_uniform(yaw=yaw)
+    aug = recovery.AugmentedMCL(alpha_slow, alpha_fast, max_fraction)
+    mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])}
+    ang = np.asarray(stream['mbes_angles'], dtype=np.float32)
+    r_max = float(stream['mbes_range_max']) if 'mbes_range_max' in stream else 100.0
+    t_prev = float(stream['t0']) if 't0' in stream else float(stream['stamp'][0]) - 0.02
+    out = dict(pf_xyz=[], pub_idx=[], fractions=[], injected=[], log_lik_per_beam=[], n_eff=[])
+    for k in range(len(stream['stamp'])):
+        t = float(stream['stamp'][k])
+        e.predict(stream['v'][k], float(stream['wz'][k]), stream['q'][k], float(stream['z'][k]), t - t_prev, stamp=t)
+        t_prev = t
+        if k not in mbes_at:
+            continue
+        ranges = np.asarray(stream['mbes_ranges'][mbes_at[k]], dtype=np.float32)
+        e.update_mbes(ranges, ang, sigma, r_max)
+        st = e.weight_stats()
+        out['log_lik_per_beam'].append(aug.observe(st, int(np.count_nonzero(ranges > 0))))
+        out['n_eff'].append(st.n_eff)
+        e.resample()
+        frac = aug.fraction() if inject else 0.0
+        out['fractions'].append(frac)
+        out['injected'].append(e.inject_uniform(frac, yaw=yaw) if frac > 0.0 else 0)
+        if frac > 0.0:
+            aug.injected()
+        out['pf_xyz'].append(e.mean_cov()[0][:3])
+        out['pub_idx'].append(k)
+    e.close()
+    for name in out:
+        out[name] = np.array(out[name])
+    summary = dict(pings=len(out['pub_idx']), injected_total=int(out['injected'].sum()) if len(out['injected']) else 0)
+    if len(out['pf_xyz']):
+        summary['pf_distance'], summary['pf_final'] = track_metrics(out['pf_xyz'].T)
+        if 'truth_xyz' in stream:
+            ref = np.asarray(stream['truth_xyz'])[out['pub_idx']]
+            summary['final_error_vs_truth'] = float(np.linalg.norm(out['pf_xyz'][-1, :2] - ref[-1, :2]))
+    out['summary'] = summary
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('stream')
@@ -304,6 +360,10 @@ def main(argv=None):
     ap.add_argument('--gps-topic', default='/sam/dr/gps')
     ap.add_argument('--mbes-topic', default='/sam/mbes_scan')
     ap.add_argument('--dive-topic', default='/dive')
+    ap.add_argument('--recover', action='store_true',
+                    help='global localisation with kidnap recovery (replay_recover): uniform start over the map, '
+                         'augmented-MCL injection; needs --map-grid and MBES pings in the stream')
+    ap.add_argument('--sigma', type=float, default=1.0, help='--recover: MBES range sigma')
     a = ap.parse_args(argv)
     if a.bag:
         grid = dict(np.load(a.map_grid)) if a.map_grid else None
@@ -322,6 +382,13 @@ def main(argv=None):
         stream, m2o = odom_stream_from_raw(stream['ev_t'], stream['ev_kind'], stream['ev_data'],
                                            gps_map=stream.get('gps_map'), pressure_tf=ptf)
     grid = dict(np.load(a.map_grid)) if a.map_grid else None
+    if a.recover:
+        res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=a.sigma, m2o=m2o)
+        if a.out:
+            np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz'], res['fractions']]), delimiter=',',
+                       header='step,x,y,z,injected_fraction')
+        print(json.dumps(res['summary']))
+        return
     res = replay(stream, dict(particle_count=a.particles, seed=a.seed), m2o=m2o, grid=grid)
     if a.out:
         np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz']]), delimiter=',', header='step,x,y,z')
