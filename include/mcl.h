@@ -147,6 +147,8 @@ int mcl_update_gps(mcl_handle* h, double gx_map, double gy_map);
 /* ---- a15: MBES measurement update (no reference symbol; north_star).  Map in the MAP frame. */
 int mcl_set_map_grid(mcl_handle* h, const float* z, int32_t nx, int32_t ny, double origin_x,
                      double origin_y, double res); /* z[ix*ny + iy] at (ox + ix*res, oy + iy*res) */
+/* A setter that fails once its arguments have passed (an allocation, the upload) leaves NO map: the old one is gone and
+ * every update and mcl_map_bounds return MCL_ERR_STATE until a setter succeeds. */
 int mcl_set_map_mesh(mcl_handle* h, const float* verts, int64_t nv, const uint32_t* tris, int64_t nt);
 /* flags: MCL_MESH_HEIGHTFIELD = the caller declares the mesh single-valued in z over (x,y) (what a
  * bathymetric surface is).  It enables neighbour-chained ray starts; a mesh with
@@ -161,6 +163,8 @@ int mcl_set_map_mesh(mcl_handle* h, const float* verts, int64_t nv, const uint32
 #define MCL_MESH_UNSTRUCTURED 4u
 int mcl_set_map_mesh_ex(mcl_handle* h, const float* verts, int64_t nv, const uint32_t* tris, int64_t nt,
                         uint32_t flags);
+/* A mesh the build refuses (an index out of range, too many records, MCL_MESH_HEIGHTFIELD on vertical faces) or cannot
+ * allocate leaves NO map, as above: the old one is released before the new one is built. */
 /* ranges[b] <= 0 or NaN marks an invalid beam; beam b looks along (0, sin a_b, -cos a_b) in the
  * sensor frame; sensor_offset = x,y,z,roll,pitch,yaw of the sensor in base_link (NULL = zeros).
  * Precision contract (state in fp64, ray-cast in fp32 -- SURVEY 8(d) allows it with a stated tolerance): against the

@@ -120,45 +120,46 @@ int mcl_create(const mcl_config* cfg, mcl_handle** out) {
     delete h;
     return MCL_ERR_INVALID;
   }
-#define CREATE_CHK(call)                                                   \
+  // (on a failure mcl_destroy releases the stream; the buffers free themselves with the handle)
+#define CREATE_CHK(status)                                                 \
   do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      g_create_err = std::string(#call " failed: ") + hipGetErrorString(e_); \
+    const int rc_ = (status);                                              \
+    if (rc_ != MCL_OK) {                                                   \
+      g_create_err = std::string(#status " failed: ") + hipGetErrorString(hipGetLastError()); \
       mcl_destroy(h);                                                      \
-      return e_ == hipErrorOutOfMemory ? MCL_ERR_ALLOC : MCL_ERR_HIP;      \
+      return rc_;                                                          \
     }                                                                      \
   } while (0)
-  CREATE_CHK(hipSetDevice(h->device));
-  CREATE_CHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  CREATE_CHK(hip_status(hipSetDevice(h->device)));
+  CREATE_CHK(hip_status(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)));
   const size_t n = (size_t)h->n, ng = (size_t)h->ng;
-  CREATE_CHK(hipMalloc(&h->state[0], sizeof(double) * 6 * n));
-  CREATE_CHK(hipMalloc(&h->state[1], sizeof(double) * 6 * n));
-  CREATE_CHK(hipMemsetAsync(h->state[0], 0, sizeof(double) * 6 * n, h->stream));
-  CREATE_CHK(hipMemsetAsync(h->state[1], 0, sizeof(double) * 6 * n, h->stream));
-  if (h->world > 1 && h->exch_allgather) CREATE_CHK(hipMalloc(&h->state_glob, sizeof(double) * 6 * ng));
-  CREATE_CHK(hipMalloc(&h->lw, sizeof(double) * n));
-  CREATE_CHK(hipMalloc(&h->q, sizeof(u64) * n));
-  CREATE_CHK(hipMalloc(&h->ncum, sizeof(u32) * ng));
-  CREATE_CHK(hipMalloc(&h->zcum, sizeof(u32) * ng));
   h->ntiles_loc = (h->n + MCL_SCAN_TILE - 1) / MCL_SCAN_TILE;
   h->ntiles_glob = (h->ng + MCL_SCAN_TILE - 1) / MCL_SCAN_TILE;
-  CREATE_CHK(hipMalloc(&h->tile64, sizeof(u64) * (size_t)(h->ntiles_loc + 1)));
-  CREATE_CHK(hipMalloc(&h->tile32, sizeof(u32) * (size_t)(h->ntiles_glob + 1)));
-  CREATE_CHK(hipMalloc(&h->part, sizeof(double) * MOM_COUNT * MCL_MAX_GRID));
-  CREATE_CHK(hipMalloc(&h->scal, sizeof(double) * 64));
-  CREATE_CHK(hipMemsetAsync(h->scal, 0, sizeof(double) * 64, h->stream));
-  CREATE_CHK(hipMalloc(&h->zr, sizeof(u32) * n));
-  CREATE_CHK(hipMalloc(&h->dupes32, sizeof(u32) * ng));
-  CREATE_CHK(hipMalloc(&h->desc, sizeof(u64) * (size_t)(h->ntiles_glob + 1)));
-  CREATE_CHK(hipMemsetAsync(h->desc, 0, sizeof(u64) * (size_t)(h->ntiles_glob + 1), h->stream));
-  CREATE_CHK(hipMalloc(&h->ctrl, CTRL_BYTES));
-  CREATE_CHK(hipMemsetAsync(h->ctrl, 0, CTRL_BYTES, h->stream));
-  CREATE_CHK(hipMalloc(&h->totals, sizeof(u64) * (size_t)(h->world + 1)));
-  CREATE_CHK(hipMemsetAsync(h->totals, 0, sizeof(u64) * (size_t)(h->world + 1), h->stream));
-  CREATE_CHK(hipHostMalloc(&h->host_pin, sizeof(double) * RING_STRIDE * MEAN_RING, hipHostMallocDefault));
+  CREATE_CHK(h->state[0].reserve(6 * n));
+  CREATE_CHK(h->state[1].reserve(6 * n));
+  if (h->world > 1 && h->exch_allgather) CREATE_CHK(h->state_glob.reserve(6 * ng));
+  CREATE_CHK(h->lw.reserve(n));
+  CREATE_CHK(h->q.reserve(n));
+  CREATE_CHK(h->ncum.reserve(ng));
+  CREATE_CHK(h->zcum.reserve(ng));
+  CREATE_CHK(h->tile64.reserve((size_t)(h->ntiles_loc + 1)));
+  CREATE_CHK(h->tile32.reserve((size_t)(h->ntiles_glob + 1)));
+  CREATE_CHK(h->part.reserve(MOM_COUNT * MCL_MAX_GRID));
+  CREATE_CHK(h->scal.reserve(64));
+  CREATE_CHK(h->zr.reserve(n));
+  CREATE_CHK(h->dupes32.reserve(ng));
+  CREATE_CHK(h->desc.reserve((size_t)(h->ntiles_glob + 1)));
+  CREATE_CHK(h->ctrl.reserve(CTRL_BYTES));
+  CREATE_CHK(h->totals.reserve((size_t)(h->world + 1)));
+  CREATE_CHK(h->host_pin.reserve(RING_STRIDE * MEAN_RING));
   if (hipHostGetDevicePointer((void**)&h->host_pin_dev, h->host_pin, 0) != hipSuccess) h->host_pin_dev = nullptr;
-  CREATE_CHK(hipStreamSynchronize(h->stream));
+  CREATE_CHK(hip_status(hipMemsetAsync(h->state[0], 0, sizeof(double) * 6 * n, h->stream)));
+  CREATE_CHK(hip_status(hipMemsetAsync(h->state[1], 0, sizeof(double) * 6 * n, h->stream)));
+  CREATE_CHK(hip_status(hipMemsetAsync(h->scal, 0, sizeof(double) * 64, h->stream)));
+  CREATE_CHK(hip_status(hipMemsetAsync(h->desc, 0, sizeof(u64) * h->desc.cap, h->stream)));
+  CREATE_CHK(hip_status(hipMemsetAsync(h->ctrl, 0, CTRL_BYTES, h->stream)));
+  CREATE_CHK(hip_status(hipMemsetAsync(h->totals, 0, sizeof(u64) * h->totals.cap, h->stream)));
+  CREATE_CHK(hip_status(hipStreamSynchronize(h->stream)));
 #undef CREATE_CHK
   *out = h;
   return MCL_OK;
@@ -179,36 +180,20 @@ int mcl_destroy(mcl_handle* h) {
   if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
   if (h->ev_state_ready) (void)hipEventDestroy(h->ev_state_ready);
   if (h->ev_gather_done) (void)hipEventDestroy(h->ev_gather_done);
-  void* bufs[] = {h->state[0], h->state[1], h->state_glob, h->lw, h->wnorm, h->q, h->ncum, h->zcum, h->zr, h->dupes32, h->desc, h->ctrl,
-                  h->tile64, h->tile32, h->part, h->scal, h->totals, h->idx, h->replay_dev, h->pose7,
-                  h->beam_sc, h->ranges_dev, h->exp_dev, h->grid, h->pose_dev, h->mbes_worklist, h->mbes_groups, h->sort_keys, h->sort_keys_out, h->sort_idx, h->mbes_perm, h->sort_tmp, h->sweep_buf[0], h->sweep_buf[1], h->defer_idx, h->defer2_idx, h->visit_okey, h->visit_base, h->visit_cnt, h->visit_desc, h->visit_par, h->slice_loose, h->reasons_dev, h->grid_pad, h->lm_worklist, h->cq, h->u53, h->cnt, h->first,
-                  h->flags, h->fcum, h->copies, h->ccum, h->dupes, h->cs, h->chunk, h->uni_dev, h->lsx, h->xsend, h->xrecv, h->shrec, h->tile_bits,
-                  h->wstats_dev, h->inject_cnt};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (h->mesh) mesh_free(h->mesh);
-  if (h->landmarks) landmarks_free(h->landmarks);
-  if (h->det_dev) (void)hipFree(h->det_dev);
-  if (h->host_pin) (void)hipHostFree(h->host_pin);
-  if (h->lsx_host) (void)hipHostFree(h->lsx_host);
-  if (h->work_host) (void)hipHostFree(h->work_host);
   if (h->copy_stream) {
     (void)hipStreamSynchronize(h->copy_stream);
     (void)hipStreamDestroy(h->copy_stream);
   }
-  for (int k = 0; k < 2; ++k) {
-    if (h->sweep_stage[k]) (void)hipHostFree(h->sweep_stage[k]);
-    if (h->ev_stage[k]) (void)hipEventDestroy(h->ev_stage[k]);
-  }
+  for (auto& e : h->ev_stage)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : h->ev_upd)
     if (e) (void)hipEventDestroy(e);
-  for (auto& sl : h->pin_ring) {
+  for (auto& sl : h->pin_ring)
     if (sl.ev) (void)hipEventDestroy(sl.ev);
-    if (sl.p) (void)hipHostFree(sl.p);
-  }
-  if (h->asg_dev) (void)hipFree(h->asg_dev);
+  mesh_free(h->mesh);
+  landmarks_free(h->landmarks);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // (its buffers free themselves: here, with the handle's device current)
   return MCL_OK;
 }
 
@@ -270,14 +255,14 @@ int mcl_set_map_grid(mcl_handle* h, const float* z, int32_t nx, int32_t ny, doub
   RET_IF(set_device(h));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (nx > (1 << 21) || ny > (1 << 21)) return fail(h, MCL_ERR_UNSUPPORTED, "set_map_grid: more than 2^21 nodes a side");
-  if (h->grid) (void)hipFree(h->grid);
-  if (h->grid_pad) (void)hipFree(h->grid_pad);
-  h->grid = nullptr;
-  h->grid_pad = nullptr;
+  h->map_kind = -1;   // (no map until everything below has succeeded: include/mcl.h)
+  h->grid.reset();
+  h->grid_pad.reset();
   const size_t cnt = (size_t)nx * (size_t)ny;
-  HIPCHK(h, hipMalloc(&h->grid, sizeof(float) * cnt));
+  RESERVE(h, h->grid, cnt);
   HIPCHK(h, hipMemcpy(h->grid, z, sizeof(float) * cnt, hipMemcpyHostToDevice));
-  HIPCHK(h, upload_padded_heights(z, nx, ny, &h->grid_pad));
+  RESERVE(h, h->grid_pad, padded_heights_count(nx, ny));
+  HIPCHK(h, upload_padded_heights(z, nx, ny, h->grid_pad));
   float mn = z[0], mx = z[0];
   for (size_t k = 1; k < cnt; ++k) {
     if (z[k] < mn) mn = z[k];
@@ -321,7 +306,8 @@ int mcl_set_map_mesh_ex(mcl_handle* h, const float* verts, int64_t nv, const uin
   if (!h || !verts || !tris || nv < 3 || nt < 1) return fail(h, MCL_ERR_INVALID, "set_map_mesh: bad argument");
   RET_IF(set_device(h));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->mesh) mesh_free(h->mesh);
+  h->map_kind = -1;   // (no map until everything below has succeeded: include/mcl.h)
+  mesh_free(h->mesh);
   h->mesh = nullptr;
   std::string err;
   // (a structured mesh is cast as a soup only on request: the slice's vertex records are built then)
@@ -330,7 +316,6 @@ int mcl_set_map_mesh_ex(mcl_handle* h, const float* verts, int64_t nv, const uin
     h->err = err;
     return rc;
   }
-  h->map_kind = 1;
   {
     double lo[2] = {verts[0], verts[1]}, hi[2] = {verts[0], verts[1]};
     for (int64_t i = 1; i < nv; ++i)
@@ -351,6 +336,7 @@ int mcl_set_map_mesh_ex(mcl_handle* h, const float* verts, int64_t nv, const uin
     h->mesh_heightfield = false;
     return MCL_ERR_INVALID;
   }
+  h->map_kind = 1;
   return MCL_OK;
 }
 
@@ -374,12 +360,7 @@ int mcl_mbes_expected(mcl_handle* h, int64_t first, int64_t count, const float* 
   RET_IF(set_device(h));
   RET_IF(upload_beams(h, nullptr, beam_angles, B));
   const size_t need = (size_t)count * (size_t)B;
-  if (need > h->exp_cap) {
-    if (h->exp_dev) (void)hipFree(h->exp_dev);
-    h->exp_dev = nullptr;
-    HIPCHK(h, hipMalloc(&h->exp_dev, sizeof(float) * need));
-    h->exp_cap = need;
-  }
+  RESERVE(h, h->exp_dev, need);
   const MbesExpect expect{h->exp_dev, first, count};
   MbesPlan plan;
   RET_IF(plan_mbes(h, B, 1.0, r_max, sensor_offset, &expect, plan));
@@ -393,7 +374,7 @@ int mcl_set_landmarks(mcl_handle* h, const double* xyz, int64_t n_landmarks) {
   if (!h || !xyz || n_landmarks < 1) return fail(h, MCL_ERR_INVALID, "set_landmarks: bad argument");
   RET_IF(set_device(h));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->landmarks) landmarks_free(h->landmarks);
+  landmarks_free(h->landmarks);
   h->landmarks = new LandmarkDev();
   h->landmarks->host_xyz.assign(xyz, xyz + 3 * n_landmarks);
   return MCL_OK;
@@ -473,12 +454,7 @@ struct LandmarkObs {
   const double* so;
 };
 int landmarks_upload(mcl_handle* h, const LandmarkObs& o) {
-  if (o.n_det > h->det_cap) {
-    if (h->det_dev) (void)hipFree(h->det_dev);
-    h->det_dev = nullptr;
-    HIPCHK(h, hipMalloc(&h->det_dev, sizeof(double) * 3 * (size_t)o.n_det));
-    h->det_cap = o.n_det;
-  }
+  RESERVE(h, h->det_dev, 3 * (size_t)o.n_det);
   return upload(h, h->det_dev, o.det, sizeof(double) * 3 * (size_t)o.n_det);
 }
 // argument checks and the cell grid for this gate radius.  (A grid rebuild drains the
@@ -595,24 +571,11 @@ int mcl_update_landmarks_assign(mcl_handle* h, const double* det_xyz, int32_t n_
       }
     }
   }
-  if (n_det > h->det_cap) {
-    if (h->det_dev) (void)hipFree(h->det_dev);
-    h->det_dev = nullptr;
-    HIPCHK(h, hipMalloc(&h->det_dev, sizeof(double) * 3 * (size_t)n_det));
-    h->det_cap = n_det;
-  }
-  RET_IF(upload(h, h->det_dev, det_xyz, sizeof(double) * 3 * (size_t)n_det));
+  RET_IF(landmarks_upload(h, LandmarkObs{det_xyz, n_det, sigma, k_cand, gate, sensor_offset}));
   if (n_keep > h->n) n_keep = h->n;
   int* asg_dev = nullptr;
   if (n_keep > 0) {
-    const size_t need = (size_t)n_keep * (size_t)n_det;
-    if (need > h->asg_cap) {
-      if (h->asg_dev) (void)hipFree(h->asg_dev);
-      h->asg_dev = nullptr;
-      h->asg_cap = 0;
-      HIPCHK(h, hipMalloc(&h->asg_dev, sizeof(int) * need));
-      h->asg_cap = need;
-    }
+    RESERVE(h, h->asg_dev, (size_t)n_keep * (size_t)n_det);
     asg_dev = h->asg_dev;
   }
   static const double zero6[6] = {0, 0, 0, 0, 0, 0};
@@ -647,13 +610,10 @@ int mcl_update_landmarks_assign(mcl_handle* h, const double* det_xyz, int32_t n_
   aa.k_cand = k_cand;
   aa.assign_out = asg_dev;
   aa.n_keep = n_keep;
-  hipError_t le = hipSuccess;
-  if (!h->lm_worklist) le = hipMalloc(&h->lm_worklist, sizeof(int) * ((size_t)h->n + 1));
-  if (le == hipSuccess) {
-    aa.worklist = h->lm_worklist;
-    aa.work_count = h->lm_worklist + h->n;
-    le = hipMemsetAsync(aa.work_count, 0, sizeof(int), h->stream);
-  }
+  RESERVE(h, h->lm_worklist, (size_t)h->n + 1);
+  aa.worklist = h->lm_worklist;
+  aa.work_count = h->lm_worklist + h->n;
+  hipError_t le = hipMemsetAsync(aa.work_count, 0, sizeof(int), h->stream);
   if (le == hipSuccess) {
     t_begin(h, MCL_K_UPDATE_LANDMARKS);
     long long blocks = (h->n + LA_PER_BLOCK - 1) / LA_PER_BLOCK;
@@ -748,13 +708,7 @@ int mcl_ranges_expected(mcl_handle* h, int64_t first, int64_t count, const float
   RET_IF(set_device(h));
   if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "ranges_expected: no map (call mcl_set_map_grid/mesh first)");
   const size_t need = (size_t)count * (size_t)n_beams;
-  if (need > h->exp_cap) {
-    if (h->exp_dev) (void)hipFree(h->exp_dev);
-    h->exp_dev = nullptr;
-    h->exp_cap = 0;
-    HIPCHK(h, hipMalloc(&h->exp_dev, sizeof(float) * need));
-    h->exp_cap = need;
-  }
+  RESERVE(h, h->exp_dev, need);
   RET_IF(ranges_launch(h, nullptr, dirs, n_beams, 1.0, r_max, sensor_offset, false, nullptr, h->exp_dev, first, count));
   HIPCHK(h, hipMemcpyAsync(out, h->exp_dev, sizeof(float) * need, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -841,7 +795,7 @@ int mcl_mean_history(mcl_handle* h, int64_t last_k, double* mean6_out) {
 int mcl_get_poses(mcl_handle* h, double* pose7) {
   if (!h || !pose7) return MCL_ERR_INVALID;
   RET_IF(set_device(h));
-  if (!h->pose7) HIPCHK(h, hipMalloc(&h->pose7, sizeof(double) * 7 * (size_t)h->n));
+  RESERVE(h, h->pose7, 7 * (size_t)h->n);
   k_poses<<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, h->pose7);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(pose7, h->pose7, sizeof(double) * 7 * (size_t)h->n, hipMemcpyDeviceToHost, h->stream));
@@ -856,7 +810,7 @@ int mcl_get_particles(mcl_handle* h, double* soa, double* w) {
                            h->stream));
   if (w) {
     if (!h->have_cdf) return fail(h, MCL_ERR_STATE, "get_particles: weights exist only after a resample");
-    if (!h->wnorm) HIPCHK(h, hipMalloc(&h->wnorm, sizeof(double) * (size_t)h->n));
+    RESERVE(h, h->wnorm, (size_t)h->n);
     k_normalised_weights<<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(h->q, h->n, h->totals, h->world, h->qshift_cur, h->wnorm);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(w, h->wnorm, sizeof(double) * (size_t)h->n, hipMemcpyDeviceToHost, h->stream));
@@ -898,7 +852,7 @@ int mcl_get_last_indices(mcl_handle* h, int32_t* idx) {
   if (!h || !idx) return MCL_ERR_INVALID;
   if (!h->have_cdf && !h->idx_explicit) return fail(h, MCL_ERR_STATE, "get_last_indices: no resample yet");
   RET_IF(set_device(h));
-  if (!h->idx) HIPCHK(h, hipMalloc(&h->idx, sizeof(int) * (size_t)h->n));
+  RESERVE(h, h->idx, (size_t)h->n);
   if (!h->idx_explicit) RET_IF(ensure_global_cdf(h));
   if (!h->idx_explicit) {
     k_indices<<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(h->ncum, h->ng, h->goff, h->n, h->idx);
@@ -1178,7 +1132,7 @@ int mcl_comm_init_ex(mcl_handle* h, const char id[128], uint32_t flags) {
   ncclUniqueId uid;
   memcpy(&uid, id, sizeof uid);
   NCCLCHK(h, ncclCommInitRank(&h->comm, h->world, uid, h->rank));
-  if (h->exch_allgather && !h->state_glob) HIPCHK(h, hipMalloc(&h->state_glob, sizeof(double) * 6 * (size_t)h->ng));
+  if (h->exch_allgather) RESERVE(h, h->state_glob, 6 * (size_t)h->ng);
   // second communicator + stream for the overlapped state all-gather (MCL_EXCHANGE=allgather only: the O(n)
   // exchange ships a few per cent of a shard and has nothing worth hiding); optional
   const bool overlap = h->exch_allgather && !(flags & MCL_COMM_NO_OVERLAP) && !h->env_no_overlap;
@@ -1364,7 +1318,7 @@ int uniform_args(mcl_handle* h, const mcl_box* box, uint32_t purpose, uint32_t s
 }
 // REPLAY uniforms (n x per doubles, per <= 6) into the replay buffer
 int upload_replay_uniforms(mcl_handle* h, const double* u, int per) {
-  if (!h->replay_dev) HIPCHK(h, hipMalloc(&h->replay_dev, sizeof(double) * 6 * (size_t)h->n));
+  RESERVE(h, h->replay_dev, 6 * (size_t)h->n);
   return upload(h, h->replay_dev, u, sizeof(double) * (size_t)per * (size_t)h->n);
 }
 }  // namespace
@@ -1407,7 +1361,8 @@ int mcl_weight_stats(mcl_handle* h, mcl_wstats* out) {
   if (!h->have_lw) return fail(h, MCL_ERR_STATE, "weight_stats: no log-weights (call an update first)");
   RET_IF(set_device(h));
   const long long ntiles = (h->n + WS_TILE - 1) / WS_TILE;
-  if (!h->wstats_dev) HIPCHK(h, hipMalloc(&h->wstats_dev, sizeof(double) * WS_OUT_WORDS + sizeof(WsPartial) * (size_t)ntiles));
+  static_assert(sizeof(WsPartial) % sizeof(double) == 0, "the tile records lie behind the result words of one double array");
+  RESERVE(h, h->wstats_dev, WS_OUT_WORDS + sizeof(WsPartial) / sizeof(double) * (size_t)ntiles);
   WsPartial* part = reinterpret_cast<WsPartial*>(h->wstats_dev + WS_OUT_WORDS);
   t_begin(h, MCL_K_NORMALISE);
   k_wstats_partial<<<(unsigned)ntiles, MCL_BLOCK, 0, h->stream>>>(h->lw, h->n, h->goff, part);
@@ -1455,7 +1410,7 @@ int mcl_inject_uniform(mcl_handle* h, double fraction, const mcl_box* box, const
     RET_IF(upload_replay_uniforms(h, replay_uniforms, 4));
     rp = h->replay_dev;
   }
-  if (!h->inject_cnt) HIPCHK(h, hipMalloc(&h->inject_cnt, sizeof(u64) * (1 + MCL_MAX_GRID)));
+  RESERVE(h, h->inject_cnt, 1 + MCL_MAX_GRID);
   RET_IF(cancel_state_gather(h));
   h->uni_valid = false;
   h->visit_ready = false;

@@ -464,3 +464,23 @@ __device__ __forceinline__ bool shl53_gt_mul(u64 r, u64 U, u64 T) {
   const u64 m_lo = U * T, m_hi = __umul64hi(U, T);
   return l_hi > m_hi || (l_hi == m_hi && (or_equal ? l_lo >= m_lo : l_lo > m_lo));
 }
+
+// ---------------------------------------------------------------- host: who owns device and pinned memory
+// (here because every host file -- the handle, the mesh, the landmark grid, the map builder -- includes this header)
+#include "mcl_buffer.h"
+inline int hip_status(hipError_t e) {
+  return e == hipSuccess ? MCL_OK : (e == hipErrorOutOfMemory ? MCL_ERR_ALLOC : MCL_ERR_HIP);
+}
+struct DeviceAlloc {
+  static int alloc(void** p, size_t bytes) { return hip_status(hipMalloc(p, bytes)); }
+  static void release(void* p) { (void)hipFree(p); }
+};
+template <unsigned FLAGS>
+struct PinnedAlloc {
+  static int alloc(void** p, size_t bytes) { return hip_status(hipHostMalloc(p, bytes, FLAGS)); }
+  static void release(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using DevBuf = Buffer<T, DeviceAlloc>;
+template <class T, unsigned FLAGS = hipHostMallocDefault>
+using PinBuf = Buffer<T, PinnedAlloc<FLAGS>>;

@@ -16,11 +16,10 @@ struct mcl_gridmap {
   int device = 0;
   int nx = 0, ny = 0;
   double ox = 0, oy = 0, res = 1;
-  long long* sum = nullptr;   // nx*ny fixed-point depth sums
-  u32* cnt = nullptr;         // nx*ny hit counts
-  float* za = nullptr;        // finalize ping-pong
-  float* zb = nullptr;
-  u32* empty_cnt = nullptr;
+  DevBuf<long long> sum;   // nx*ny fixed-point depth sums
+  DevBuf<u32> cnt;         // nx*ny hit counts
+  DevBuf<float> za, zb;       // finalize ping-pong
+  DevBuf<u32> empty_cnt;
   hipStream_t stream = nullptr;
   std::string err;
 };
@@ -172,9 +171,8 @@ int mcl_gridmap_create(int32_t nx, int32_t ny, double ox, double oy, double res,
   g->res = res;
   const size_t n = (size_t)nx * ny;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&g->stream) != hipSuccess ||
-      hipMalloc(&g->sum, n * sizeof(long long)) != hipSuccess || hipMalloc(&g->cnt, n * sizeof(u32)) != hipSuccess ||
-      hipMalloc(&g->za, n * sizeof(float)) != hipSuccess || hipMalloc(&g->zb, n * sizeof(float)) != hipSuccess ||
-      hipMalloc(&g->empty_cnt, sizeof(u32)) != hipSuccess) {
+      g->sum.reserve(n) != MCL_OK || g->cnt.reserve(n) != MCL_OK || g->za.reserve(n) != MCL_OK || g->zb.reserve(n) != MCL_OK ||
+      g->empty_cnt.reserve(1) != MCL_OK) {
     gm_detail::g_gm_create_err = "gridmap_create: device allocation failed";
     mcl_gridmap_destroy(g);
     return MCL_ERR_ALLOC;
@@ -187,11 +185,8 @@ void mcl_gridmap_destroy(mcl_gridmap* g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
   if (g->stream) (void)hipStreamSynchronize(g->stream);
-  void* bufs[] = {g->sum, g->cnt, g->za, g->zb, g->empty_cnt};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
   if (g->stream) (void)hipStreamDestroy(g->stream);
-  delete g;
+  delete g;   // (frees its buffers)
 }
 
 const char* mcl_gridmap_last_error(const mcl_gridmap* g) { return g ? g->err.c_str() : gm_detail::g_gm_create_err.c_str(); }
@@ -214,23 +209,19 @@ int mcl_gridmap_add_pings(mcl_gridmap* g, const double* poses6, int64_t n_pings,
     return gm_detail::fail(g, MCL_ERR_INVALID, "gridmap_add_pings: bad argument");
   GMCHK(g, hipSetDevice(g->device));
   const size_t nb = (size_t)n_pings * n_beams;
-  double* poses_d = nullptr;
-  float* ranges_d = nullptr;
-  float2* sc_d = nullptr;
-  double* pts_d = nullptr;
+  DevBuf<double> poses_d, pts_d;
+  DevBuf<float> ranges_d;
+  DevBuf<float2> sc_d;
   std::vector<float2> sc((size_t)n_beams);
   for (int b = 0; b < n_beams; ++b) sc[b] = make_float2((float)std::sin((double)beam_angles[b]), (float)std::cos((double)beam_angles[b]));
   int rc = MCL_OK;
-  hipError_t e = hipMalloc(&poses_d, sizeof(double) * 6 * (size_t)n_pings);
-  if (e == hipSuccess) e = hipMalloc(&ranges_d, sizeof(float) * nb);
-  if (e == hipSuccess) e = hipMalloc(&sc_d, sizeof(float2) * (size_t)n_beams);
-  if (e == hipSuccess && points_out) e = hipMalloc(&pts_d, sizeof(double) * 3 * nb);
-  if (e != hipSuccess) {
+  if (poses_d.reserve(6 * (size_t)n_pings) != MCL_OK || ranges_d.reserve(nb) != MCL_OK || sc_d.reserve((size_t)n_beams) != MCL_OK ||
+      (points_out && pts_d.reserve(3 * nb) != MCL_OK)) {
     g->err = "gridmap_add_pings: device allocation failed";
     rc = MCL_ERR_ALLOC;
   }
   if (rc == MCL_OK) {
-    e = hipMemcpyAsync(poses_d, poses6, sizeof(double) * 6 * (size_t)n_pings, hipMemcpyHostToDevice, g->stream);
+    hipError_t e = hipMemcpyAsync(poses_d, poses6, sizeof(double) * 6 * (size_t)n_pings, hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ranges_d, ranges, sizeof(float) * nb, hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(sc_d, sc.data(), sizeof(float2) * (size_t)n_beams, hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) {
@@ -267,10 +258,6 @@ int mcl_gridmap_add_pings(mcl_gridmap* g, const double* poses6, int64_t n_pings,
       rc = MCL_ERR_HIP;
     }
   }
-  if (poses_d) (void)hipFree(poses_d);
-  if (ranges_d) (void)hipFree(ranges_d);
-  if (sc_d) (void)hipFree(sc_d);
-  if (pts_d) (void)hipFree(pts_d);
   return rc;
 }
 

@@ -70,65 +70,64 @@ struct mcl_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   // particle state: two ping-pong SoA buffers of 6*n doubles; multi-shard: a global copy
-  double* state[2] = {nullptr, nullptr};
+  DevBuf<double> state[2];
   int cur = 0;
-  double* state_glob = nullptr;  // 6*ng (world > 1)
-  double* lw = nullptr;          // n log-weights
-  double* wnorm = nullptr;       // n (lazily)
-  u64* q = nullptr;              // n fixed-point weights
-  u32* ncum = nullptr;           // ng offspring CDF (global)
-  u32* zcum = nullptr;           // ng scratch (generic keep/lost/dupes of the explicit-index schemes)
-  u32* zr = nullptr;             // n: rank of a lost slot among the lost slots, or ZR_SURVIVOR
-  u32* dupes32 = nullptr;        // ng: dupes[k] = ancestor copied into the k-th lost slot
-  u64* desc = nullptr;           // ntiles_glob look-back descriptors
-  unsigned char* ctrl = nullptr; // control block: max-lw slots | MBES work counter | kernel tickets (CTRL_* offsets)
+  DevBuf<double> state_glob;  // 6*ng (world > 1)
+  DevBuf<double> lw;          // n log-weights
+  DevBuf<double> wnorm;       // n (lazily)
+  DevBuf<u64> q;              // n fixed-point weights
+  DevBuf<u32> ncum;           // ng offspring CDF (global)
+  DevBuf<u32> zcum;           // ng scratch (generic keep/lost/dupes of the explicit-index schemes)
+  DevBuf<u32> zr;             // n: rank of a lost slot among the lost slots, or ZR_SURVIVOR
+  DevBuf<u32> dupes32;        // ng: dupes[k] = ancestor copied into the k-th lost slot
+  DevBuf<u64> desc;           // ntiles_glob look-back descriptors
+  DevBuf<unsigned char> ctrl; // control block: max-lw slots | MBES work counter | kernel tickets (CTRL_* offsets)
   u32 epoch = 0;                 // look-back epoch (one per k_cdf_expand launch)
   bool max_valid = false;        // the slots hold max lw of the current log-weights
   int slot_set = 0;              // ... which set: 0 = CTRL_SLOTS (MBES kernels, k_max_slots), 1 = CTRL_SLOTS2 (fused landmark update)
   bool pose_ready = false;       // pose_dev already holds the records of the current state (fused predict)
-  u64* tile64 = nullptr;
-  u32* tile32 = nullptr;
+  DevBuf<u64> tile64;
+  DevBuf<u32> tile32;
   long long ntiles_loc = 0, ntiles_glob = 0;
-  double* part = nullptr;     // reduction partials [7][MCL_MAX_GRID]
-  double* scal = nullptr;     // device scalars: [0] max lw, [8..14] sums7, [16..21] cov6
-  u64* totals = nullptr;      // device, world entries (+1 scratch)
-  int* idx = nullptr;         // n (lazily)
-  double* replay_dev = nullptr;
-  double* pose7 = nullptr;
+  DevBuf<double> part;     // reduction partials [7][MCL_MAX_GRID]
+  DevBuf<double> scal;     // device scalars: [0] max lw, [8..14] sums7, [16..21] cov6
+  DevBuf<u64> totals;      // device, world entries (+1 scratch)
+  DevBuf<int> idx;         // n (lazily)
+  DevBuf<double> replay_dev;
+  DevBuf<double> pose7;
   double* host_pin_dev = nullptr;  // device-side address of host_pin (kernels write results into the ring directly)
   MomentsDest moments_dest = MOMENTS_SCAL;   // of the last gather
-  double* host_pin = nullptr;  // pinned ring: MEAN_RING entries of 16 doubles (sums7, pad, cov-sums6, pad2)
+  PinBuf<double> host_pin;  // pinned ring: MEAN_RING entries of 16 doubles (sums7, pad, cov-sums6, pad2)
   long long mean_count = 0;     // number of mean/cov results produced so far
   // MBES
-  float2* beam_sc = nullptr;
-  float* ranges_dev = nullptr;
-  float* exp_dev = nullptr;
-  MbesPose* pose_dev = nullptr;
-  MbesGroup* mbes_groups = nullptr;  // one record per group of MBES_WAVES particles
+  DevBuf<float2> beam_sc;
+  DevBuf<float> ranges_dev;
+  DevBuf<float> exp_dev;   // expected ranges (mcl_mbes_expected, mcl_ranges_expected), grown on demand
+  DevBuf<MbesPose> pose_dev;
+  DevBuf<MbesGroup> mbes_groups;  // one record per group of MBES_WAVES particles
   // visiting order for dispersed clouds: Morton keys, radix sort (rocPRIM), permutation
-  u32 *sort_keys = nullptr, *sort_keys_out = nullptr, *sort_idx = nullptr, *mbes_perm = nullptr;
-  void* sort_tmp = nullptr;
+  DevBuf<u32> sort_keys, sort_keys_out, sort_idx, mbes_perm;
+  DevBuf<unsigned char> sort_tmp;
   size_t sort_tmp_bytes = 0;
   // pinned ring of 4 slots x 4 ints, one slot per MBES update: [0] groups the natural-order classification deferred,
   // [1] particles the sweep handed to the general kernel.  An update reads
   // the slot of the update TWO before it, after waiting for that update's event (long since complete when the host
   // runs ahead): the visiting-order and grid-size decisions are a function of the filter's history, never of timing.
-  int* work_host = nullptr;
+  PinBuf<int> work_host;
   hipEvent_t ev_upd[4] = {nullptr, nullptr, nullptr, nullptr};
   unsigned long long upd_seq = 0;
   int env_sort = -1;            // MCL_SORT_VISITS=0/1 forces the decision (tests, A/B)
-  int* mbes_worklist = nullptr;  // ngroups + 1 ints; [ngroups] is the counter
-  int* lm_worklist = nullptr;    // n + 1 ints; [n] is the counter (landmark assignment: particles with clashes)
+  DevBuf<int> mbes_worklist;  // ngroups + 1 ints; [ngroups] is the counter
+  DevBuf<int> lm_worklist;    // n + 1 ints; [n] is the counter (landmark assignment: particles with clashes)
   // alternative resamplers (lazily allocated)
-  u64* cq = nullptr;       // inclusive scan of q
-  u64* u53 = nullptr;      // uniforms as 53-bit integers
-  u32 *cnt = nullptr, *first = nullptr, *flags = nullptr, *fcum = nullptr, *copies = nullptr, *ccum = nullptr;
-  int* dupes = nullptr;
-  double *cs = nullptr, *chunk = nullptr, *uni_dev = nullptr;
+  DevBuf<u64> cq;       // inclusive scan of q
+  DevBuf<u64> u53;      // uniforms as 53-bit integers
+  DevBuf<u32> cnt, first, flags, fcum, copies, ccum;
+  DevBuf<int> dupes;
+  DevBuf<double> cs, chunk, uni_dev;
   long long residual_k = -1;  // copies count cached by mcl_resample_prepare
   bool idx_explicit = false;  // last resample produced idx[] directly (non-systematic)
-  size_t exp_cap = 0;
-  int beams_cap = 0;
+  int beams_cap = 0;   // beams beam_sc AND ranges_dev have room for (the angle cache describes them): committed when both exist
   std::vector<float> beam_cache;  // last uploaded angles
   int beam_lo = -1, beam_hi = -1;  // extreme-angle beams (footprint shortcut)
   bool beams_sorted = false;
@@ -139,23 +138,23 @@ struct mcl_handle {
   int sweep_cap = 0;
   // the table travels on its own stream into alternating device buffers, so the 12 KiB copy of ping k + 1 overlaps
   // the kernels of ping k instead of standing between two steps (4 us of copy + its launch gaps)
-  float4* sweep_buf[2] = {nullptr, nullptr};
-  float* sweep_stage[2] = {nullptr, nullptr};   // pinned staging, one per buffer
+  DevBuf<float> sweep_buf[2];   // a SweepBlock each (mcl_host_update.h)
+  PinBuf<float> sweep_stage[2];   // pinned staging, one per buffer
   hipEvent_t ev_stage[2] = {nullptr, nullptr};
   bool stage_used[2] = {false, false};
   int sweep_sel = 0;
   hipStream_t copy_stream = nullptr;
-  u32* defer_idx = nullptr;         // particles the sweep hands to k_mbes_cast<., ., 2>
-  u32* defer2_idx = nullptr;        // TIN with holes: what the fan slice -- the sweep's hand-over kernel there -- declines in turn
+  DevBuf<u32> defer_idx;         // particles the sweep hands to k_mbes_cast<., ., 2>
+  DevBuf<u32> defer2_idx;        // TIN with holes: what the fan slice -- the sweep's hand-over kernel there -- declines in turn
   int env_handover_slice = -1;      // MCL_HANDOVER_SLICE=0: the ray traversal takes the TIN sweep's hand-overs even on meshes with holes (A/B)
-  unsigned* reasons_dev = nullptr;  // -DSWEEP_REASONS builds: why the sweep declined (16 counters)
+  DevBuf<unsigned> reasons_dev;  // -DSWEEP_REASONS builds: why the sweep declined (16 counters)
   // spatial visiting order of the sweep (mcl_kernels.h: VisitArgs): prepared by the fused step's gather, used by the
   // next fused predict
-  u32 *visit_okey = nullptr, *visit_base = nullptr;
-  unsigned short* visit_cnt = nullptr;
-  u64* visit_desc = nullptr;
+  DevBuf<u32> visit_okey, visit_base;
+  DevBuf<unsigned short> visit_cnt;
+  DevBuf<u64> visit_desc;
   u32 visit_epoch = 0;
-  VisitPar* visit_par = nullptr;    // two entries: read / written alternately
+  DevBuf<VisitPar> visit_par;    // two entries: read / written alternately
   unsigned visit_flip = 0;
   bool gather_attr_set = false;     // k_resample_gather<true, true, true> may use its 112 KiB of dynamic LDS
   bool visit_ready = false;         // okey / hist / binbase describe the slots of the current state
@@ -173,20 +172,19 @@ struct mcl_handle {
   bool handover_slice_now = false;  // the last update's sweep hand-overs went through the fan slice first (TIN with holes)
   int env_slice = -1;               // MCL_SLICE=0 keeps the ray traversal on triangle soups (tests, A/B)
   int env_slice_group = -1;         // MCL_SLICE_GROUP=0: the fan slice casts every particle on its own (no shared candidate lists)
-  u32* slice_loose = nullptr;       // k_mbes_slice_group: the groups of SLICE_G pose records it left to k_mbes_slice
+  DevBuf<u32> slice_loose;       // k_mbes_slice_group: the groups of SLICE_G pose records it left to k_mbes_slice
   bool slice_attr_set = false;
   bool slice_group_ran = false;     // the last sliced update went through k_mbes_slice_group first
   size_t slice_attr_bytes = 0;
-  float* grid = nullptr;
-  float* grid_pad = nullptr;   // the same heights inside a one-node ring of NaNs (fan sweep: MbesArgs::grid_pad)
+  DevBuf<float> grid;
+  DevBuf<float> grid_pad;   // the same heights inside a one-node ring of NaNs (fan sweep: MbesArgs::grid_pad)
   int gnx = 0, gny = 0;
   double gox = 0, goy = 0, gres = 1;
   float gzmin = 0, gzmax = 0;
   double gslope_max = 0;       // steepest patch gradient of the height grid (the fan sweep's tilt bound)
   MeshDev* mesh = nullptr;
   LandmarkDev* landmarks = nullptr;
-  double* det_dev = nullptr;
-  int det_cap = 0;
+  DevBuf<double> det_dev;   // 3 x detections, grown on demand
   // fused landmark step: the detections ride in the per-ping beam table's staged copy (its own stream, under the previous
   // step's kernels) instead of a copy on the compute stream in front of the predict
   const double* det_ride = nullptr;      // host detections waiting for the next table upload (3 x det_ride_n doubles)
@@ -203,8 +201,8 @@ struct mcl_handle {
   // global localisation / recovery (include/mcl_recovery.h)
   uint32_t step_inject = 0;       // Philox step of the next mcl_inject_uniform; reset by both init calls
   double map_xy[4] = {0, 0, 0, 0};  // footprint of the map (x_min, x_max, y_min, y_max; MAP frame), valid while map_kind >= 0
-  double* wstats_dev = nullptr;   // weight statistics: WS_OUT_WORDS result words, then one 32-byte record per tile (lazily)
-  u64* inject_cnt = nullptr;      // injection: the replaced-particle total, then one count per workgroup (lazily)
+  DevBuf<double> wstats_dev;   // weight statistics: WS_OUT_WORDS result words, then one 32-byte record per tile (lazily)
+  DevBuf<u64> inject_cnt;      // injection: the replaced-particle total, then one count per workgroup (lazily)
   bool timing = false;
   std::vector<TimedRegion> regions;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -229,20 +227,19 @@ struct mcl_handle {
   // surplus copies packed for the peers, copies received for this shard's lost slots
   bool exch_allgather = false;   // MCL_EXCHANGE=allgather: the all-gather exchange of rounds 1-2 instead
   // one collective for "maximum, then totals" (mcl_resample.h: k_quantise_tiles' records, k_shift_scan)
-  u64* shrec = nullptr;          // device: world x SHREC_WORDS all-gathered shard records, then the shift word
-  unsigned short* tile_bits = nullptr;   // device: ntiles_loc x 64 bit counts of this shard's tiles
+  DevBuf<u64> shrec;          // device: world x SHREC_WORDS all-gathered shard records, then the shift word
+  DevBuf<unsigned short> tile_bits;   // device: ntiles_loc x 64 bit counts of this shard's tiles
   const u64* qshift_cur = nullptr;       // the shift the weights in `q` are read with (nullptr: none) -- set by every resample
   bool shrec_dirty = false;              // a launch that accumulates into the record is queued and k_shift_scan (which zeroes it) is not
   // the fused step's moments ride with the NEXT step's records instead of an all-reduce of their own:
   bool mom_pending = false;              // a ring entry is reserved whose sums still lie, per shard, in the records
   long long mom_pending_entry = -1;      // ... which one (index into the result ring, before the modulo)
-  u64* lsx = nullptr;            // device, world x 4 words
-  u64* lsx_host = nullptr;       // pinned, world x 4 words + the sequence word k_publish_ls writes last
+  DevBuf<u64> lsx;            // device, world x 4 words
+  PinBuf<u64, hipHostMallocMapped | hipHostMallocCoherent> lsx_host;   // pinned (fine-grained: the host polls it while kernels run), world x 4 words + the sequence word k_publish_ls writes last
   u64* lsx_host_dev = nullptr;   // its device-side address
   u64 ls_seq = 0;
-  double* xsend = nullptr;       // 6 x xsend_cap
-  size_t xsend_cap = 0;
-  double* xrecv = nullptr;       // 6 x n
+  DevBuf<double> xsend;       // 6 doubles per entry: xsend.cap / 6 copies
+  DevBuf<double> xrecv;       // 6 x n
   std::vector<u32> ex_L, ex_S;   // per shard, filled by exchange_ls
   std::vector<u32> ex_Lpre, ex_Spre;
   unsigned long long ex_sent = 0, ex_lost = 0;  // particle states sent to peers / lost slots, summed over the resamples
@@ -254,14 +251,12 @@ struct mcl_handle {
   bool env_debug_work = false, env_force_comm = false, env_no_overlap = false;
   // pinned staging so that asynchronous uploads never read caller-owned pageable memory after the call returns
   struct PinSlot {
-    void* p = nullptr;
-    size_t cap = 0;
+    PinBuf<unsigned char> buf;
     hipEvent_t ev = nullptr;  // recorded after the async copy out of this slot
     bool used = false;
   } pin_ring[8];
   unsigned pin_next = 0;
-  int* asg_dev = nullptr;  // landmark assignment output (cached, grown on demand)
-  size_t asg_cap = 0;
+  DevBuf<int> asg_dev;  // landmark assignment output (cached, grown on demand)
   std::string err;
 };
 
@@ -275,6 +270,18 @@ namespace {
       snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
       (h)->err = buf_;                                                                         \
       return MCL_ERR_HIP;                                                                      \
+    }                                                                                          \
+  } while (0)
+// room for `count` elements in a DevBuf / PinBuf of the handle (mcl_buffer.h: within its capacity nothing happens; the
+// contents are not kept; a failure leaves the buffer empty): MCL_ERR_ALLOC when the memory is not there, else MCL_ERR_HIP
+#define RESERVE(h, buf, count)                                                                 \
+  do {                                                                                         \
+    const int rc_ = (buf).reserve(count);                                                      \
+    if (rc_ != MCL_OK) {                                                                       \
+      char buf_[512];                                                                          \
+      snprintf(buf_, sizeof buf_, "%s.reserve(%s) failed: %s (%s:%d)", #buf, #count, hipGetErrorString(hipGetLastError()), __FILE__, __LINE__); \
+      (h)->err = buf_;                                                                         \
+      return rc_;                                                                              \
     }                                                                                          \
   } while (0)
 #define NCCLCHK(h, call)                                                                       \
@@ -379,25 +386,21 @@ int upload(mcl_handle* h, void* dst, const void* src, size_t bytes) {
   }
   mcl_handle::PinSlot& sl = h->pin_ring[h->pin_next++ % 8u];
   if (sl.used) HIPCHK(h, hipEventSynchronize(sl.ev));
-  if (sl.cap < bytes) {
-    if (sl.p) (void)hipHostFree(sl.p);
-    sl.p = nullptr;
-    sl.cap = 0;
+  if (sl.buf.cap < bytes) {
     size_t cap = 4096;
     while (cap < bytes) cap <<= 1;
-    HIPCHK(h, hipHostMalloc(&sl.p, cap, hipHostMallocDefault));
-    sl.cap = cap;
+    RESERVE(h, sl.buf, cap);
   }
   if (!sl.ev) HIPCHK(h, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-  memcpy(sl.p, src, bytes);
-  HIPCHK(h, hipMemcpyAsync(dst, sl.p, bytes, hipMemcpyHostToDevice, h->stream));
+  memcpy(sl.buf, src, bytes);
+  HIPCHK(h, hipMemcpyAsync(dst, sl.buf, bytes, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipEventRecord(sl.ev, h->stream));
   sl.used = true;
   return MCL_OK;
 }
 
 int upload_replay(mcl_handle* h, const double* normals) {
-  if (!h->replay_dev) HIPCHK(h, hipMalloc(&h->replay_dev, sizeof(double) * 6 * (size_t)h->n));
+  RESERVE(h, h->replay_dev, 6 * (size_t)h->n);
   return upload(h, h->replay_dev, normals, sizeof(double) * 6 * (size_t)h->n);
 }
 

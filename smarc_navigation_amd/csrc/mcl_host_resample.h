@@ -98,11 +98,11 @@ int phase_quantise(mcl_handle* h, bool from_slots, bool fused_next = false) {
 // Weight modes other than log-likelihoods (GPS: linear weights relative to the maximum's) keep the two-step form.
 bool one_collective(const mcl_handle* h) { return h->comm && h->weight_mode == MCL_WEIGHT_LOG_SHIFT; }
 int alloc_shrec(mcl_handle* h) {
-  if (h->shrec) return MCL_OK;
   const size_t words = (size_t)h->world * SHREC_WORDS + 1;
-  HIPCHK(h, hipMalloc(&h->shrec, sizeof(u64) * words));
-  HIPCHK(h, hipMemsetAsync(h->shrec, 0, sizeof(u64) * words, h->stream));
-  HIPCHK(h, hipMalloc(&h->tile_bits, sizeof(unsigned short) * 64 * (size_t)h->ntiles_loc));
+  const bool fresh = !h->shrec;
+  RESERVE(h, h->shrec, words);
+  if (fresh) HIPCHK(h, hipMemsetAsync(h->shrec, 0, sizeof(u64) * words, h->stream));
+  RESERVE(h, h->tile_bits, 64 * (size_t)h->ntiles_loc);
   return MCL_OK;
 }
 int phase_quantise_shard(mcl_handle* h) {
@@ -295,9 +295,9 @@ int phase_expand(mcl_handle* h, bool fused_cdf, uint64_t u53) {
 
 // ---- O(n)-per-rank exchange -------------------------------------------------------------------------------
 int alloc_lsx(mcl_handle* h) {
-  if (h->lsx) return MCL_OK;
-  HIPCHK(h, hipMalloc(&h->lsx, sizeof(u64) * 4 * (size_t)h->world));
-  HIPCHK(h, hipHostMalloc(&h->lsx_host, sizeof(u64) * (4 * (size_t)h->world + 1), hipHostMallocMapped | hipHostMallocCoherent));  // (fine-grained: the host polls it while kernels run)
+  RESERVE(h, h->lsx, 4 * (size_t)h->world);
+  if (h->lsx_host) return MCL_OK;
+  RESERVE(h, h->lsx_host, 4 * (size_t)h->world + 1);
   memset(h->lsx_host, 0, sizeof(u64) * (4 * (size_t)h->world + 1));
   if (hipHostGetDevicePointer((void**)&h->lsx_host_dev, h->lsx_host, 0) != hipSuccess) h->lsx_host_dev = nullptr;
   return MCL_OK;
@@ -410,13 +410,9 @@ int exchange_ls_group(mcl_handle** sh, int ns) {
 // from the records on the device, so it can be queued before the host has read them (exchange_ls)
 int launch_pack(mcl_handle* h, u64 publish_seq) {
   RET_IF(set_device(h));
-  if (!h->xrecv) HIPCHK(h, hipMalloc(&h->xrecv, sizeof(double) * 6 * (size_t)h->n));
-  if (!h->xsend) {
-    // a shard's surplus is statistically a few per cent of its slots; n / 4 entries to start with, grown on demand
-    const size_t cap = std::max<size_t>((size_t)h->n / 4, 4096);
-    HIPCHK(h, hipMalloc(&h->xsend, sizeof(double) * 6 * cap));
-    h->xsend_cap = cap;
-  }
+  RESERVE(h, h->xrecv, 6 * (size_t)h->n);
+  // a shard's surplus is statistically a few per cent of its slots; n / 4 entries to start with, grown on demand
+  if (!h->xsend) RESERVE(h, h->xsend, 6 * std::max<size_t>((size_t)h->n / 4, 4096));
   h->gather_uni_mask = uni_mask(h);
   PackArgs a;
   a.src = state_ptrs(h->state[h->cur], h->n);
@@ -424,7 +420,7 @@ int launch_pack(mcl_handle* h, u64 publish_seq) {
   a.lsx = h->lsx;
   a.rank = h->rank;
   a.world = h->world;
-  a.cap = (u32)std::min<size_t>(h->xsend_cap, 0xffffffffull);
+  a.cap = (u32)std::min<size_t>(h->xsend.cap / 6, 0xffffffffull);
   a.nship = shipped_components(h->gather_uni_mask, a.ship);
   h->ex_nship = a.nship;
   a.send = h->xsend;
@@ -443,16 +439,10 @@ int launch_pack(mcl_handle* h, u64 publish_seq) {
 int phase_pack(mcl_handle* h, bool already_packed) {
   RET_IF(set_device(h));
   const u32 S = h->ex_S[h->rank];
-  if (already_packed && (size_t)S <= h->xsend_cap) return MCL_OK;
-  if ((size_t)S > h->xsend_cap) {
-    if (h->xsend) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      (void)hipFree(h->xsend);
-      h->xsend = nullptr;
-    }
-    const size_t cap = std::max<size_t>((size_t)S + (size_t)S / 4, 4096);
-    HIPCHK(h, hipMalloc(&h->xsend, sizeof(double) * 6 * cap));
-    h->xsend_cap = cap;
+  if (already_packed && (size_t)S <= h->xsend.cap / 6) return MCL_OK;
+  if ((size_t)S > h->xsend.cap / 6) {
+    if (h->xsend) HIPCHK(h, hipStreamSynchronize(h->stream));   // (the pack kernel in flight writes the old block)
+    RESERVE(h, h->xsend, 6 * std::max<size_t>((size_t)S + (size_t)S / 4, 4096));
   }
   return launch_pack(h);
 }
@@ -627,13 +617,13 @@ GatherPlan plan_gather(mcl_handle* h, bool with_moments, bool replay) {
 }
 
 int ensure_visit_buffers(mcl_handle* h) {
-  if (h->visit_okey) return MCL_OK;
-  HIPCHK(h, hipMalloc(&h->visit_okey, sizeof(u32) * (size_t)h->n));
-  HIPCHK(h, hipMalloc(&h->visit_base, sizeof(u32) * (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS));
-  HIPCHK(h, hipMalloc(&h->visit_cnt, sizeof(unsigned short) * (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS));
-  HIPCHK(h, hipMalloc(&h->visit_desc, sizeof(u64) * (VISIT_MAX_BINS / 64)));
+  if (h->visit_par) return MCL_OK;   // (the last one allocated: all five exist)
+  RESERVE(h, h->visit_okey, (size_t)h->n);
+  RESERVE(h, h->visit_base, (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS);
+  RESERVE(h, h->visit_cnt, (size_t)GATHER_MAX_GRID * VISIT_MAX_BINS);
+  RESERVE(h, h->visit_desc, VISIT_MAX_BINS / 64);
   HIPCHK(h, hipMemsetAsync(h->visit_desc, 0, sizeof(u64) * (VISIT_MAX_BINS / 64), h->stream));
-  HIPCHK(h, hipMalloc(&h->visit_par, sizeof(VisitPar) * 2));
+  RESERVE(h, h->visit_par, 2);
   HIPCHK(h, hipMemsetAsync(h->visit_par, 0, sizeof(VisitPar) * 2, h->stream));
   return MCL_OK;
 }
@@ -725,27 +715,22 @@ int phase_gather(mcl_handle* h, const double* replay_normals, bool with_moments)
 // ------------------------------------------------------------------------------------------
 // stratified / multinomial / residual (single shard): explicit ancestor vector + generic reassign
 // ------------------------------------------------------------------------------------------
-template <class T>
-int lazy_alloc(mcl_handle* h, T** p, size_t count) {
-  if (!*p) HIPCHK(h, hipMalloc(p, sizeof(T) * count));
-  return MCL_OK;
-}
 int alt_alloc(mcl_handle* h) {
   const size_t n = (size_t)h->n;
-  RET_IF(lazy_alloc(h, &h->cq, n));
-  RET_IF(lazy_alloc(h, &h->u53, n));
-  RET_IF(lazy_alloc(h, &h->cnt, n));
-  RET_IF(lazy_alloc(h, &h->first, n));
-  RET_IF(lazy_alloc(h, &h->flags, n));
-  RET_IF(lazy_alloc(h, &h->fcum, n));
-  RET_IF(lazy_alloc(h, &h->copies, n));
-  RET_IF(lazy_alloc(h, &h->ccum, n));
-  RET_IF(lazy_alloc(h, &h->dupes, n));
-  RET_IF(lazy_alloc(h, &h->cs, n));
-  RET_IF(lazy_alloc(h, &h->chunk, n / 8192 + 2));
-  RET_IF(lazy_alloc(h, &h->uni_dev, n));
-  RET_IF(lazy_alloc(h, &h->wnorm, n));
-  RET_IF(lazy_alloc(h, &h->idx, n));
+  RESERVE(h, h->cq, n);
+  RESERVE(h, h->u53, n);
+  RESERVE(h, h->cnt, n);
+  RESERVE(h, h->first, n);
+  RESERVE(h, h->flags, n);
+  RESERVE(h, h->fcum, n);
+  RESERVE(h, h->copies, n);
+  RESERVE(h, h->ccum, n);
+  RESERVE(h, h->dupes, n);
+  RESERVE(h, h->cs, n);
+  RESERVE(h, h->chunk, n / 8192 + 2);
+  RESERVE(h, h->uni_dev, n);
+  RESERVE(h, h->wnorm, n);
+  RESERVE(h, h->idx, n);
   return MCL_OK;
 }
 // inclusive u32 scan of `in` into `out` (n local); uses tile32 as scratch

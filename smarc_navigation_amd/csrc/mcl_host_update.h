@@ -10,12 +10,11 @@ int upload_beams(mcl_handle* h, const float* ranges, const float* beam_angles, i
   h->det_ride = nullptr;   // (detections of a fused landmark step that failed before its table upload: the caller's buffer is gone)
   h->det_ride_dev = nullptr;
   if (B > h->beams_cap) {
-    if (h->beam_sc) (void)hipFree(h->beam_sc);
-    if (h->ranges_dev) (void)hipFree(h->ranges_dev);
-    HIPCHK(h, hipMalloc(&h->beam_sc, sizeof(float2) * (size_t)B));
-    HIPCHK(h, hipMalloc(&h->ranges_dev, sizeof(float) * (size_t)B));
-    h->beams_cap = B;
+    h->beams_cap = 0;   // (committed when both buffers exist)
     h->beam_cache.clear();
+    RESERVE(h, h->beam_sc, (size_t)B);
+    RESERVE(h, h->ranges_dev, (size_t)B);
+    h->beams_cap = B;
   }
   if ((int)h->beam_cache.size() != B || memcmp(h->beam_cache.data(), beam_angles, sizeof(float) * B) != 0) {
     std::vector<float2> sc(B);
@@ -97,27 +96,19 @@ int upload_sweep_beams(mcl_handle* h, bool with_ranges, int B, double sigma, dou
                        int* nvalid_out) {
   const SweepBlock lay{(size_t)B};
   const bool grow_ride = h->det_ride && h->det_ride_n > h->det_ride_cap;
-  // (the new capacities are COMMITTED only when both buffers of both halves exist -- ADVICE r5: a failed allocation
-  //  used to leave null buffers behind capacities that said there was room, and the next fused landmark step built its
-  //  table through a null pinned pointer)
+  // (sweep_cap and det_ride_cap describe the LAYOUT of all four buffers: committed only when every one of them exists)
   const int ride_cap = grow_ride ? std::max(h->det_ride_n, 16) : h->det_ride_cap;
   if (B > h->sweep_cap || grow_ride) {
     const size_t cap_b = (size_t)std::max(B, h->sweep_cap);
     const size_t alloc_floats = SweepBlock{cap_b}.floats(ride_cap);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-    for (int k = 0; k < 2; ++k) {
-      if (h->sweep_buf[k]) (void)hipFree(h->sweep_buf[k]);
-      if (h->sweep_stage[k]) (void)hipHostFree(h->sweep_stage[k]);
-      h->sweep_buf[k] = nullptr;
-      h->sweep_stage[k] = nullptr;
-      h->stage_used[k] = false;
-    }
-    h->sweep_cap = 0;       // (nothing is allocated from here until every allocation below has succeeded)
+    h->sweep_cap = 0;
     h->det_ride_cap = 0;
     for (int k = 0; k < 2; ++k) {
-      HIPCHK(h, hipMalloc(&h->sweep_buf[k], sizeof(float) * alloc_floats));
-      HIPCHK(h, hipHostMalloc(&h->sweep_stage[k], sizeof(float) * alloc_floats, hipHostMallocDefault));
+      h->stage_used[k] = false;
+      RESERVE(h, h->sweep_buf[k], alloc_floats);
+      RESERVE(h, h->sweep_stage[k], alloc_floats);
       if (!h->ev_stage[k]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_stage[k], hipEventDisableTiming));
     }
     if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
@@ -125,7 +116,7 @@ int upload_sweep_beams(mcl_handle* h, bool with_ranges, int B, double sigma, dou
     h->det_ride_cap = ride_cap;
   }
   const int sel = (h->sweep_sel ^= 1);
-  float* dev = (float*)h->sweep_buf[sel];
+  float* dev = h->sweep_buf[sel];
   if (h->stage_used[sel]) HIPCHK(h, hipEventSynchronize(h->ev_stage[sel]));   // (two updates old: long complete)
   float* blk = h->sweep_stage[sel];   // (the table is built straight into the pinned staging buffer)
   float4* tb = (float4*)blk;
@@ -215,19 +206,19 @@ void rot_rpy(double roll, double pitch, double yaw, double R[9]) {
 // Morton visiting order of the particles' pose records (k_mbes_keys): h->mbes_perm
 int sort_visiting_order(mcl_handle* h, const MbesArgs& a) {
   const size_t n = (size_t)h->n;
-  if (!h->sort_keys) {
-    HIPCHK(h, hipMalloc(&h->sort_keys, sizeof(u32) * n));
-    HIPCHK(h, hipMalloc(&h->sort_keys_out, sizeof(u32) * n));
-    HIPCHK(h, hipMalloc(&h->sort_idx, sizeof(u32) * n));
-    HIPCHK(h, hipMalloc(&h->mbes_perm, sizeof(u32) * n));
-    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, h->sort_tmp_bytes, h->sort_keys, h->sort_keys_out, h->sort_idx,
-                                        h->mbes_perm, n, 0, 24, h->stream));
-    HIPCHK(h, hipMalloc(&h->sort_tmp, h->sort_tmp_bytes));
+  RESERVE(h, h->sort_keys, n);
+  RESERVE(h, h->sort_keys_out, n);
+  RESERVE(h, h->sort_idx, n);
+  RESERVE(h, h->mbes_perm, n);
+  // (rocPRIM deduces its iterator types from the arguments: it gets the raw pointers, not their owners)
+  u32 *keys = h->sort_keys, *keys_out = h->sort_keys_out, *idx = h->sort_idx, *perm = h->mbes_perm;
+  if (!h->sort_tmp) {
+    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, h->sort_tmp_bytes, keys, keys_out, idx, perm, n, 0, 24, h->stream));
+    RESERVE(h, h->sort_tmp, h->sort_tmp_bytes);
   }
-  k_mbes_keys<<<grid_for(h->n), 256, 0, h->stream>>>(a, h->sort_keys, h->sort_idx);
+  k_mbes_keys<<<grid_for(h->n), 256, 0, h->stream>>>(a, keys, idx);
   // stable LSD radix sort of (key, slot) pairs: the visiting order is deterministic
-  HIPCHK(h, rocprim::radix_sort_pairs(h->sort_tmp, h->sort_tmp_bytes, h->sort_keys, h->sort_keys_out, h->sort_idx,
-                                      h->mbes_perm, n, 0, 24, h->stream));
+  HIPCHK(h, rocprim::radix_sort_pairs((void*)h->sort_tmp.p, h->sort_tmp_bytes, keys, keys_out, idx, perm, n, 0, 24, h->stream));
   return MCL_OK;
 }
 
@@ -303,7 +294,7 @@ struct MbesExpect {   // expected ranges of the particles [first, first + count)
 int attach_diag_counters(mcl_handle* h, MbesArgs& a) {
 #ifdef SWEEP_REASONS
   if (!h->reasons_dev) {
-    HIPCHK(h, hipMalloc(&h->reasons_dev, 64));
+    RESERVE(h, h->reasons_dev, 16);
     HIPCHK(h, hipMemset(h->reasons_dev, 0, 64));
   }
   a.reasons = h->reasons_dev;
@@ -378,7 +369,7 @@ int plan_mbes(mcl_handle* h, int B, double sigma, double r_max, const double sen
     // the cast kernels leave max lw in the control block's slots: the normalisation needs no reduction pass
     a.max_slots = (u64*)(h->ctrl + CTRL_SLOTS);
   }
-  if (!h->pose_dev) HIPCHK(h, hipMalloc(&h->pose_dev, sizeof(MbesPose) * (size_t)h->n));
+  RESERVE(h, h->pose_dev, (size_t)h->n);
   a.pose = h->pose_dev;
   a.sweep_nsub = 1;
   a.sweep_c2z_min = 2.f;
@@ -386,8 +377,8 @@ int plan_mbes(mcl_handle* h, int B, double sigma, double r_max, const double sen
   RET_IF(attach_diag_counters(h, a));
   // every map kind: the pose kernel classifies the groups, k_mbes_fast casts the eligible ones, k_mbes_cast<., ., 1>
   // the worklist
-  if (!h->mbes_worklist) HIPCHK(h, hipMalloc(&h->mbes_worklist, sizeof(int) * (size_t)(p.ngroups + 1)));
-  if (!h->mbes_groups) HIPCHK(h, hipMalloc(&h->mbes_groups, sizeof(MbesGroup) * (size_t)p.ngroups));
+  RESERVE(h, h->mbes_worklist, (size_t)(p.ngroups + 1));
+  RESERVE(h, h->mbes_groups, (size_t)p.ngroups);
   a.worklist = h->mbes_worklist;
   a.groups = h->mbes_groups;
   a.work_count = (int*)(h->ctrl + CTRL_WORK);
@@ -416,7 +407,7 @@ int plan_mbes(mcl_handle* h, int B, double sigma, double r_max, const double sen
     a.ranges = h->ranges_dev;
   }
   if (p.path != MBES_TRAVERSAL) {   // the hand-over list of the sweep and of the slice
-    if (!h->defer_idx) HIPCHK(h, hipMalloc(&h->defer_idx, sizeof(u32) * (size_t)h->n));
+    RESERVE(h, h->defer_idx, (size_t)h->n);
     a.defer_idx = h->defer_idx;
     a.slice = p.path == MBES_SLICE ? 1 : 0;
   }
@@ -545,9 +536,9 @@ bool staged_handover(const mcl_handle* h, const MbesPlan& p) {
 // sweep -> slice group -> slice -> cast
 int run_staged_handover(mcl_handle* h, const MbesPlan& p, const SweepGrid& g, const MbesArgs& a, MbesArgs d, const MbesCounters& wh) {
   const int B = p.B;
-  if (!h->defer2_idx) HIPCHK(h, hipMalloc(&h->defer2_idx, sizeof(u32) * (size_t)h->n));
+  RESERVE(h, h->defer2_idx, (size_t)h->n);
   const long long ngr = (h->n + SLICE_G - 1) / SLICE_G;
-  if (!h->slice_loose) HIPCHK(h, hipMalloc(&h->slice_loose, sizeof(u32) * (size_t)ngr));
+  RESERVE(h, h->slice_loose, (size_t)ngr);
   t_begin(h, MCL_K_MBES_MAIN);
   if (h->mesh->tin_rims)
     k_mbes_sweep<6, false><<<g.sgrid, SWEEP_THREADS, g.lds, h->stream>>>(a);
@@ -659,7 +650,7 @@ int run_slice(mcl_handle* h, const MbesPlan& p, MbesArgs& a, const MbesCounters&
   h->slice_group_ran = false;
   if (pose_done && h->pose_visit && h->env_slice_group != 0) {
     const long long ngr = (h->n + SLICE_G - 1) / SLICE_G;
-    if (!h->slice_loose) HIPCHK(h, hipMalloc(&h->slice_loose, sizeof(u32) * (size_t)ngr));
+    RESERVE(h, h->slice_loose, (size_t)ngr);
     // (a beam table too long for the staging layout: the per-particle kernel casts everything)
     if (slice_group_fits(B)) {
       const size_t lds_g = slice_group_lds_bytes(B);
@@ -748,7 +739,7 @@ int run_mbes(mcl_handle* h, const MbesPlan& p, bool pose_done) {
   MbesArgs a = p.args;
   // ---- counters of the update two before this one (deterministic lag, see mcl_handle::work_host)
   if (!h->work_host) {
-    HIPCHK(h, hipHostMalloc(&h->work_host, 64, hipHostMallocDefault));
+    RESERVE(h, h->work_host, 16);
     memset(h->work_host, 0, 64);
     for (int k = 0; k < 4; ++k) HIPCHK(h, hipEventCreateWithFlags(&h->ev_upd[k], hipEventDisableTiming));
   }
@@ -849,7 +840,7 @@ int do_predict(mcl_handle* h, const mcl_odom* od, double dt, const double* repla
       // (the whole block: ONE aligned fill; the kernel tickets in it are zero between launches anyway)
       HIPCHK(h, hipMemsetAsync(h->ctrl, 0, CTRL_BYTES, h->stream));
     } else {
-      a.zero_ptr = (unsigned long long*)h->ctrl;   // the kernel's first workgroup zeroes it: no memset launch
+      a.zero_ptr = (unsigned long long*)h->ctrl.p;   // the kernel's first workgroup zeroes it: no memset launch
       a.zero_words = CTRL_BYTES / 8;
       if ((pose_for->sweep_beams || (pose_for->slice && h->env_slice_group != 0)) && h->visit_ready) {
         // the fan sweep visits the particles in the spatial order the last gather prepared: the records go to their

@@ -522,36 +522,28 @@ __global__ void __launch_bounds__(LA_PER_BLOCK * LM_SUB) k_landmark_assign(Landm
 
 struct LandmarkDev {
   std::vector<double> host_xyz;  // as given
-  double* lm = nullptr;
-  u32* cell_start = nullptr;
-  u32* orig = nullptr;      // cell-ordered slot -> index in the caller's landmark list
-  uint2* nb_cell = nullptr;   // (gx + 4) x (gy + 4): flattened 3 x 3 neighbourhood of a query cell (k_landmark_update)
-  double4* nb_list = nullptr;
+  DevBuf<double> lm;
+  DevBuf<u32> cell_start;
+  DevBuf<u32> orig;      // cell-ordered slot -> index in the caller's landmark list
+  DevBuf<uint2> nb_cell;   // (gx + 4) x (gy + 4): flattened 3 x 3 neighbourhood of a query cell (k_landmark_update)
+  DevBuf<double4> nb_list;
   int gx = 0, gy = 0;
   double x0 = 0, y0 = 0, cs = 0;
-  double built_for = -1.0;  // gate radius the grid was built for
+  double built_for = -1.0;  // gate radius the grid was built for (-1: not built, also after a build that failed partway)
   // Mahalanobis mode (mcl_set_landmark_noise)
   std::vector<double> host_cov;  // n x 6 as given, or empty
-  double* lmcov = nullptr;       // cell order
+  DevBuf<double> lmcov;       // cell order
   bool maha = false, have_q = false;
   double Q[6] = {0, 0, 0, 0, 0, 0};
   double lam_cov_max = 0.0;      // largest eigenvalue over the landmark covariances (bound: Gershgorin)
 };
 
-inline void landmarks_free(LandmarkDev* L) {
-  if (!L) return;
-  if (L->lm) (void)hipFree(L->lm);
-  if (L->cell_start) (void)hipFree(L->cell_start);
-  if (L->orig) (void)hipFree(L->orig);
-  if (L->nb_cell) (void)hipFree(L->nb_cell);
-  if (L->nb_list) (void)hipFree(L->nb_list);
-  if (L->lmcov) (void)hipFree(L->lmcov);
-  delete L;
-}
+inline void landmarks_free(LandmarkDev* L) { delete L; }
 
 // (re)build the xy cell grid for a gate radius r (cells >= r, at most 2048 x 2048)
 inline int landmarks_build(LandmarkDev* L, double r, std::string* err) {
   if (L->built_for == r && L->lm) return MCL_OK;
+  L->built_for = -1.0;
   const size_t n = L->host_xyz.size() / 3;
   double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
   for (size_t i = 0; i < n; ++i) {
@@ -587,15 +579,8 @@ inline int landmarks_build(LandmarkDev* L, double r, std::string* err) {
     sorted[3 * r2 + 1] = L->host_xyz[3 * i + 1];
     sorted[3 * r2 + 2] = L->host_xyz[3 * i + 2];
   }
-  if (L->lm) (void)hipFree(L->lm);
-  if (L->cell_start) (void)hipFree(L->cell_start);
-  if (L->orig) (void)hipFree(L->orig);
-  L->lm = nullptr;
-  L->cell_start = nullptr;
-  L->orig = nullptr;
-  if (hipMalloc(&L->lm, sizeof(double) * sorted.size()) != hipSuccess ||
-      hipMalloc(&L->orig, sizeof(u32) * orig.size()) != hipSuccess ||
-      hipMalloc(&L->cell_start, sizeof(u32) * (nc + 1)) != hipSuccess) {
+  if (L->lm.reserve(sorted.size()) != MCL_OK || L->orig.reserve(orig.size()) != MCL_OK ||
+      L->cell_start.reserve(nc + 1) != MCL_OK) {
     *err = "update_landmarks: device allocation failed";
     return MCL_ERR_ALLOC;
   }
@@ -633,12 +618,7 @@ inline int landmarks_build(LandmarkDev* L, double r, std::string* err) {
         nb[(size_t)(qx + 2) * ey + (qy + 2)] = make_uint2((u32)first, (u32)(list.size() - first));
       }
     if (list.empty()) list.push_back(double4{0, 0, 0, 0});
-    if (L->nb_cell) (void)hipFree(L->nb_cell);
-    if (L->nb_list) (void)hipFree(L->nb_list);
-    L->nb_cell = nullptr;
-    L->nb_list = nullptr;
-    if (hipMalloc(&L->nb_cell, sizeof(uint2) * nb.size()) != hipSuccess ||
-        hipMalloc(&L->nb_list, sizeof(double4) * list.size()) != hipSuccess) {
+    if (L->nb_cell.reserve(nb.size()) != MCL_OK || L->nb_list.reserve(list.size()) != MCL_OK) {
       *err = "update_landmarks: device allocation failed";
       return MCL_ERR_ALLOC;
     }
@@ -648,13 +628,12 @@ inline int landmarks_build(LandmarkDev* L, double r, std::string* err) {
       return MCL_ERR_HIP;
     }
   }
-  if (L->lmcov) (void)hipFree(L->lmcov);
-  L->lmcov = nullptr;
+  L->lmcov.reset();   // (null says: no landmark covariances)
   if (!L->host_cov.empty()) {
     std::vector<double> sc(6 * std::max<size_t>(n, 1));
     for (size_t r2 = 0; r2 < n; ++r2)
       for (int k = 0; k < 6; ++k) sc[6 * r2 + k] = L->host_cov[6 * (size_t)orig[r2] + k];
-    if (hipMalloc(&L->lmcov, sizeof(double) * sc.size()) != hipSuccess ||
+    if (L->lmcov.reserve(sc.size()) != MCL_OK ||
         hipMemcpy(L->lmcov, sc.data(), sizeof(double) * sc.size(), hipMemcpyHostToDevice) != hipSuccess) {
       *err = "update_landmarks: covariance upload failed";
       return MCL_ERR_ALLOC;

@@ -21,17 +21,17 @@
 #include "mcl_mbes.h"
 
 struct MeshDev {
-  float4* tri = nullptr;       // 3 float4 per (cell, triangle) record, plane form (see mesh_build)
-  float4* tri_mt = nullptr;    // Moller-Trumbore form (v0, e1, e2), only if some triangle is near-vertical
-  u32* cell_start = nullptr;   // gx*gy + 1
-  uint2* cell_info = nullptr;  // per cell: x = half2(zmin rounded down, zmax rounded up), y = start | count << 27
+  DevBuf<float4> tri;       // 3 float4 per (cell, triangle) record, plane form (see mesh_build)
+  DevBuf<float4> tri_mt;    // Moller-Trumbore form (v0, e1, e2), only if some triangle is near-vertical
+  DevBuf<u32> cell_start;   // gx*gy + 1
+  DevBuf<uint2> cell_info;  // per cell: x = half2(zmin rounded down, zmax rounded up), y = start | count << 27
   int gx = 0, gy = 0;
   double x0 = 0, y0 = 0, cs = 1;
   float zmin = 0, zmax = 0;
   size_t n_records = 0;
   // structured mesh (a triangulated regular height grid): node heights, diagonal bit in the LSB
-  float* heights = nullptr;  // (gx+1)*(gy+1), or nullptr if the mesh is not structured
-  float* heights_pad = nullptr;  // the same inside a one-node ring of NaNs, (gx+3)*(gy+3) (fan sweep: MbesArgs::grid_pad)
+  DevBuf<float> heights;  // (gx+1)*(gy+1), or nullptr if the mesh is not structured
+  DevBuf<float> heights_pad;  // the same inside a one-node ring of NaNs, (gx+3)*(gy+3) (fan sweep: MbesArgs::grid_pad)
   size_t n_vertical = 0;  // triangles whose xy projection is degenerate (cannot be a height field)
   int diag_mode = 0;      // structured: 1 = every cell split along 00-11, 2 = along 10-01, 0 = mixed (LSB per cell)
   double slope_max = 0;   // steepest triangle, |grad h| (the fan sweep's tilt bound, mcl_sweep.h)
@@ -46,26 +46,28 @@ struct MeshDev {
   // load; input order -- the walk's neighbours megabytes apart when the caller's triangles come in no spatial order).
   // tin_ok: every edge has at most two triangles and their third vertices lie on opposite sides of it in the xy
   // projection (no fold: the mesh is a height field), no vertical triangle, no two triangles overlapping in xy.
-  uint4* tin_he = nullptr;
+  DevBuf<uint4> tin_he;
   size_t tin_he_bytes = 0;
   bool tin_ok = false;
   size_t tin_nhe = 0;       // half-edge records (3 x triangles); behind them rim records, behind those chunk records (mcl_halfedge.h)
   size_t tin_outline = 0;   // first rim record of the OUTLINE when it is linked (a sensor beyond it starts its walk there), else 0
   size_t tin_rims = 0;      // rim records behind the 3 nt half-edge records: the edges of the holes the walk crosses by itself (mcl_halfedge.h: link_holes)
-  u32* cell_rim = nullptr;   // per cell of the cell grid: the first rim record of the linked hole whose bounding box reaches into the cell (0xffffffff: none, 0xfffffffe: more than one) -- where a walk starts whose nadir ray falls into a gap
+  DevBuf<u32> cell_rim;   // per cell of the cell grid: the first rim record of the linked hole whose bounding box reaches into the cell (0xffffffff: none, 0xfffffffe: more than one) -- where a walk starts whose nadir ray falls into a gap
   bool tin_holes = false;   // some edge of the TIN has no triangle on its far side and does not lie on the bounding box: a hole or a ragged outline (walks that reach it hand their particle over)
   // fan slice over an arbitrary triangle soup (mcl_slice.h): per (cell, triangle) record the three vertices of its source
   // triangle in MAP-FRAME coordinates, 3 float4 {x, y, z, -}, same indexing as `tri`.  (Absolute, not cell-relative: a
   // vertex has the same bits in every record it appears in, so the slices of two triangles that share an edge meet in
   // one point.  No index indirection: the walk over a cell's records is one dependent load, not two.)
-  float4* cell_tri = nullptr;
+  DevBuf<float4> cell_tri;
 };
 
 // The height array of a lattice map inside a one-node ring of quiet NaNs whose payload names the border: 1 = beyond an
 // x side (i = -1 or nx), 2 = beyond a y side, 3 = a corner.  The fan sweep (mcl_sweep.h) walks node by node: stepping
 // off the map it loads a NaN, which ends the walk through the test that ends it anyway -- no bounds test per step.
-inline hipError_t upload_padded_heights(const float* z, int nx, int ny, float** out) {
-  const size_t nyp = (size_t)ny + 2, cnt = ((size_t)nx + 2) * nyp;
+inline size_t padded_heights_count(int nx, int ny) { return ((size_t)nx + 2) * ((size_t)ny + 2); }
+// (out: room for padded_heights_count(nx, ny) floats on the device)
+inline hipError_t upload_padded_heights(const float* z, int nx, int ny, float* out) {
+  const size_t nyp = (size_t)ny + 2, cnt = padded_heights_count(nx, ny);
   std::vector<float> pad(cnt);
   auto nanp = [](uint32_t payload) {
     const uint32_t b = 0x7fc00000u | payload;
@@ -78,25 +80,10 @@ inline hipError_t upload_padded_heights(const float* z, int nx, int ny, float** 
       const bool ox = i == 0 || i == (size_t)nx + 1, oy = j == 0 || j == nyp - 1;
       pad[i * nyp + j] = (ox || oy) ? nanp((ox ? 1u : 0u) | (oy ? 2u : 0u)) : z[(i - 1) * (size_t)ny + (j - 1)];
     }
-  *out = nullptr;
-  hipError_t e = hipMalloc(out, sizeof(float) * cnt);
-  if (e != hipSuccess) return e;
-  return hipMemcpy(*out, pad.data(), sizeof(float) * cnt, hipMemcpyHostToDevice);
+  return hipMemcpy(out, pad.data(), sizeof(float) * cnt, hipMemcpyHostToDevice);
 }
 
-inline void mesh_free(MeshDev* m) {
-  if (!m) return;
-  if (m->tri) (void)hipFree(m->tri);
-  if (m->cell_start) (void)hipFree(m->cell_start);
-  if (m->cell_info) (void)hipFree(m->cell_info);
-  if (m->tri_mt) (void)hipFree(m->tri_mt);
-  if (m->heights) (void)hipFree(m->heights);
-  if (m->heights_pad) (void)hipFree(m->heights_pad);
-  if (m->tin_he) (void)hipFree(m->tin_he);
-  if (m->cell_rim) (void)hipFree(m->cell_rim);
-  if (m->cell_tri) (void)hipFree(m->cell_tri);
-  delete m;
-}
+inline void mesh_free(MeshDev* m) { delete m; }
 
 // float -> IEEE half bits with directed rounding (dir < 0: toward -inf, dir > 0: toward +inf)
 inline float half_bits_to_float(uint16_t h) {
@@ -328,11 +315,8 @@ inline int mesh_build(const float* verts, int64_t nv, const uint32_t* tris, int6
     info[c].x = (u32)hlo | ((u32)hhi << 16);
     info[c].y = start[c] | (std::min(cnt, 31u) << 27);  // count 31 = "31 or more": read cell_start
   }
-  hipError_t e1 = hipMalloc(&m->tri, sizeof(float4) * rec.size());
-  hipError_t e2 = hipMalloc(&m->cell_start, sizeof(u32) * (nc + 1));
-  hipError_t e3 = hipMalloc(&m->cell_info, sizeof(uint2) * nc);
-  hipError_t e4 = any_vertical ? hipMalloc(&m->tri_mt, sizeof(float4) * rec_mt.size()) : hipSuccess;
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
+  if (m->tri.reserve(rec.size()) != MCL_OK || m->cell_start.reserve(nc + 1) != MCL_OK || m->cell_info.reserve(nc) != MCL_OK ||
+      (any_vertical && m->tri_mt.reserve(rec_mt.size()) != MCL_OK)) {
     *err = "set_map_mesh: device allocation failed";
     mesh_free(m);
     return MCL_ERR_ALLOC;
@@ -406,7 +390,6 @@ inline int mesh_build(const float* verts, int64_t nv, const uint32_t* tris, int6
     if (ok) {
       std::vector<halfedge::Rec> he;
       halfedge::build_table(verts, tris, nt, twin, ccw, new_of_old, xmin, xmax, ymin, ymax, he);
-      static_assert(sizeof(halfedge::Rec) == 2 * sizeof(uint4), "the device reads a half-edge record as two 16-byte words");
       const bool link = !(getenv("MCL_TIN_RIMS") && atoi(getenv("MCL_TIN_RIMS")) == 0);   // (0: no hole is crossed -- A/B, tests)
       const bool box_outline = getenv("MCL_TIN_BOX_OUTLINE") && atoi(getenv("MCL_TIN_BOX_OUTLINE")) == 1;   // (mcl_halfedge.h: link an outline that lies on the bounding box all around as well -- INTEGRATION.md 4a)
       const halfedge::Links links = link ? halfedge::link_holes(he, nt, box_outline) : halfedge::Links();
@@ -444,9 +427,10 @@ inline int mesh_build(const float* verts, int64_t nv, const uint32_t* tris, int6
         }
       }
       m->tin_he_bytes = sizeof(halfedge::Rec) * he.size();
-      if (hipMalloc(&m->tin_he, m->tin_he_bytes) == hipSuccess &&
+      static_assert(sizeof(halfedge::Rec) == 2 * sizeof(uint4), "the device reads a half-edge record as two 16-byte words");
+      if (m->tin_he.reserve(2 * he.size()) == MCL_OK &&
           hipMemcpy(m->tin_he, he.data(), m->tin_he_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-          (cell_rim.empty() || (hipMalloc(&m->cell_rim, 4 * cell_rim.size()) == hipSuccess &&
+          (cell_rim.empty() || (m->cell_rim.reserve(cell_rim.size()) == MCL_OK &&
                                 hipMemcpy(m->cell_rim, cell_rim.data(), 4 * cell_rim.size(), hipMemcpyHostToDevice) == hipSuccess))) {
         m->tin_ok = true;
         m->slope_max = std::sqrt(g2);
@@ -545,9 +529,9 @@ inline int mesh_build(const float* verts, int64_t nv, const uint32_t* tris, int6
           }
         m->slope_max = std::sqrt(g2) / cs;
       }
-      if (hipMalloc(&m->heights, sizeof(float) * hts.size()) != hipSuccess ||
+      if (m->heights.reserve(hts.size()) != MCL_OK || m->heights_pad.reserve(padded_heights_count((int)nnx, (int)nny)) != MCL_OK ||
           hipMemcpy(m->heights, hts.data(), sizeof(float) * hts.size(), hipMemcpyHostToDevice) != hipSuccess ||
-          upload_padded_heights(hts.data(), (int)nnx, (int)nny, &m->heights_pad) != hipSuccess) {
+          upload_padded_heights(hts.data(), (int)nnx, (int)nny, m->heights_pad) != hipSuccess) {
         *err = "set_map_mesh: device allocation failed";
         mesh_free(m);
         return MCL_ERR_ALLOC;
@@ -569,13 +553,10 @@ inline int mesh_build(const float* verts, int64_t nv, const uint32_t* tris, int6
       }
       memcpy(&ct[3 * r].w, &k, 4);   // the source triangle's index in the first vertex's spare word (k_mbes_slice_group: a triangle recorded in several cells is staged once)
     }
-    if (hipMalloc(&m->cell_tri, sizeof(float4) * ct.size()) != hipSuccess) {
+    if (m->cell_tri.reserve(ct.size()) != MCL_OK ||
+        hipMemcpy(m->cell_tri, ct.data(), sizeof(float4) * ct.size(), hipMemcpyHostToDevice) != hipSuccess) {
       (void)hipGetLastError();
-      m->cell_tri = nullptr;
-    } else if (hipMemcpy(m->cell_tri, ct.data(), sizeof(float4) * ct.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(m->cell_tri);
-      m->cell_tri = nullptr;
+      m->cell_tri.reset();
     }
   }
   *out = m;

@@ -6,6 +6,7 @@
 // order with mixed windings, its invariants checked record by record, and WALKED on the CPU by the kernel's own rule
 // (mcl_sweep.h: sweep_side_tin -- the new vertex replaces the end on its side of the plane; which of next_a / next_b is
 // taken follows from that and from one bit of state) from every triangle a random vertical plane cuts to the mesh border.
+// mcl_buffer.h -- the owner of every device and pinned buffer -- over malloc, with an allocator that fails on command.
 // Exit code 0 and no sanitizer report = pass; the properties checked here are the ones tests/test_exchange_plan.py and
 // tests/test_dr_golden.py check through the real library.
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include <random>
 #include <unordered_map>
 
+#include "../../smarc_navigation_amd/csrc/mcl_buffer.h"
 #include "../../smarc_navigation_amd/csrc/mcl_host_pure.h"
 #include "../../smarc_navigation_amd/csrc/mcl_halfedge.h"
 #include "../../smarc_navigation_amd/csrc/mcl_dr_impl.h"
@@ -607,8 +609,115 @@ static int check_hole_rims(std::mt19937_64& rng) {
   return 0;
 }
 
+// ---- mcl_buffer.h: the owner of every device and pinned buffer, over malloc with an allocator that fails on command.
+// (What ASan and LeakSanitizer add to the counts: a block freed twice, a block never freed.)
+struct FailingAlloc {
+  static int allocs, frees, live, fail_next;   // fail_next: 1 = out of memory, 2 = another error; consumed by one call
+  static int alloc(void** p, size_t bytes) {
+    ++allocs;
+    if (fail_next) {
+      const int rc = fail_next == 1 ? MCL_ERR_ALLOC : MCL_ERR_HIP;
+      fail_next = 0;
+      return rc;
+    }
+    *p = std::malloc(bytes ? bytes : 1);
+    ++live;
+    return MCL_OK;
+  }
+  static void release(void* p) {
+    std::free(p);
+    ++frees;
+    --live;
+  }
+};
+int FailingAlloc::allocs = 0, FailingAlloc::frees = 0, FailingAlloc::live = 0, FailingAlloc::fail_next = 0;
+
+static int check_buffer_owner(std::mt19937_64& rng) {
+  typedef FailingAlloc A;
+  typedef Buffer<double, A> Buf;
+  {
+    Buf b;
+    CHECK(!b && b.p == nullptr && b.cap == 0);
+    CHECK(b.reserve(0) == MCL_OK && A::allocs == 0);                       // nothing asked for, nothing done
+    CHECK(b.reserve(100) == MCL_OK && b.p && b.cap == 100 && A::allocs == 1 && A::live == 1);
+    double* const first = b;                                                // (the implicit conversion kernels' argument blocks use)
+    first[99] = 1.0;                                                        // the whole block is there (ASan)
+    CHECK(*(b + 99) == 1.0 && b[99] == 1.0);
+    CHECK(b.reserve(100) == MCL_OK && b.reserve(7) == MCL_OK && b.reserve(0) == MCL_OK);
+    CHECK(A::allocs == 1 && A::frees == 0 && b.p == first && b.cap == 100);  // within the capacity: no allocation
+    CHECK(b.reserve(101) == MCL_OK && b.cap == 101 && A::allocs == 2 && A::frees == 1 && A::live == 1);   // a growth frees the old block once
+    b[100] = 2.0;
+    // a growth that fails: empty, whichever error it was, and the old block freed exactly once
+    A::fail_next = 1;
+    CHECK(b.reserve(1000) == MCL_ERR_ALLOC && b.p == nullptr && b.cap == 0 && !b && A::frees == 2 && A::live == 0);
+    // ... and the next request of ANY size allocates: no stale capacity says there is room
+    CHECK(b.reserve(1) == MCL_OK && b.p && b.cap == 1 && A::allocs == 4 && A::live == 1);
+    b[0] = 3.0;
+    A::fail_next = 2;
+    CHECK(b.reserve(2) == MCL_ERR_HIP && b.p == nullptr && b.cap == 0 && A::live == 0);
+    CHECK(b.reserve(50) == MCL_OK && b.cap == 50);
+    // move: the source is left empty, the target's old block is freed
+    Buf c(std::move(b));
+    CHECK(b.p == nullptr && b.cap == 0 && c.p && c.cap == 50 && A::live == 1);
+    Buf d;
+    CHECK(d.reserve(5) == MCL_OK && A::live == 2);
+    d = std::move(c);
+    CHECK(c.p == nullptr && c.cap == 0 && d.cap == 50 && A::live == 1);
+    d.reset();
+    CHECK(d.p == nullptr && d.cap == 0 && A::live == 0);
+    d.reset();                                                              // (twice: nothing to free)
+    A::fail_next = 1;
+    CHECK(d.reserve(9) == MCL_ERR_ALLOC);
+  }   // destruction after a failed growth, of moved-from and of reset owners: nothing freed twice
+  CHECK(A::live == 0 && A::frees + 3 == A::allocs);   // (the three failed calls count as allocations asked for)
+  // ---- random sequences of reserve / fail / reset / move over a few owners
+  for (int trial = 0; trial < 400; ++trial) {
+    {
+      Buffer<unsigned char, A> b[3];
+      const int steps = 1 + (int)(rng() % 40);
+      for (int k = 0; k < steps; ++k) {
+        Buffer<unsigned char, A>& x = b[rng() % 3];
+        const int op = (int)(rng() % 8);
+        if (op < 4) {
+          const size_t want = (size_t)(rng() % 5000), cap0 = x.cap;
+          unsigned char* const p0 = x.p;
+          const int before = A::allocs;
+          A::fail_next = op == 3 ? 1 + (int)(rng() % 2) : 0;
+          const int rc = x.reserve(want);
+          if (want <= cap0) {
+            CHECK(rc == MCL_OK && x.p == p0 && x.cap == cap0 && A::allocs == before);
+          } else if (op == 3) {
+            CHECK(rc != MCL_OK && x.p == nullptr && x.cap == 0);
+          } else {
+            CHECK(rc == MCL_OK && x.p && x.cap == want && A::allocs == before + 1);
+            x[want - 1] = (unsigned char)k;
+            x[0] = (unsigned char)k;
+          }
+          A::fail_next = 0;
+        } else if (op == 4) {
+          x.reset();
+          CHECK(!x && x.cap == 0);
+        } else {
+          Buffer<unsigned char, A>& y = b[rng() % 3];
+          const size_t cap0 = x.cap;
+          unsigned char* const p0 = x.p;
+          y = std::move(x);
+          if (&x != &y) CHECK(x.p == nullptr && x.cap == 0);
+          CHECK(y.p == p0 && y.cap == cap0);
+        }
+        int owned = 0;
+        for (int q = 0; q < 3; ++q) owned += b[q].p ? 1 : 0;
+        CHECK(A::live == owned);
+      }
+    }
+    CHECK(A::live == 0);
+  }
+  return 0;
+}
+
 int main() {
   std::mt19937_64 rng(12345);
+  if (check_buffer_owner(rng) != 0) return 1;
   if (check_halfedge_tables(rng) != 0) return 1;
   if (check_hole_rims(rng) != 0) return 1;
   // ---- transfer plan: for random worlds, what q sends r is what r receives from q, and every lost slot is filled once
