@@ -6,6 +6,9 @@
 #include "mcl_host_resample.h"
 #include "mcl_host_moments.h"
 #include "mcl_host_update.h"
+#include "mcl_host_landmarks.h"
+#include "mcl_host_ranges.h"
+#include "mcl_host_step.h"
 // global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
 #include "mcl_recovery.h"
 
@@ -86,13 +89,17 @@ int mcl_create(const mcl_config* cfg, mcl_handle** out) {
       const char* v = getenv(name);
       return v && v[0] == '1';
     };
+    auto env_tristate = [](const char* name) {   // -1 not set, 1 for "1...", else 0
+      const char* v = getenv(name);
+      return !v ? -1 : (v[0] == '1' ? 1 : 0);
+    };
     h->env_debug_work = getenv("MCL_DEBUG_WORK") != nullptr;
-    if (const char* sv = getenv("MCL_SORT_VISITS")) h->env_sort = sv[0] == '1' ? 1 : 0;
-    if (const char* sv = getenv("MCL_SWEEP")) h->env_sweep = sv[0] == '1' ? 1 : 0;
-    if (const char* sv = getenv("MCL_SLICE")) h->env_slice = sv[0] == '1' ? 1 : 0;
-    if (const char* sv = getenv("MCL_SLICE_GROUP")) h->env_slice_group = sv[0] == '1' ? 1 : 0;
-    if (const char* sv = getenv("MCL_HANDOVER_SLICE")) h->env_handover_slice = sv[0] == '1' ? 1 : 0;
-    if (const char* sv = getenv("MCL_VISIT")) h->env_visit = sv[0] == '1' ? 1 : 0;
+    h->env_sort = env_tristate("MCL_SORT_VISITS");
+    h->env_sweep = env_tristate("MCL_SWEEP");
+    h->env_slice = env_tristate("MCL_SLICE");
+    h->env_slice_group = env_tristate("MCL_SLICE_GROUP");
+    h->env_handover_slice = env_tristate("MCL_HANDOVER_SLICE");
+    h->env_visit = env_tristate("MCL_VISIT");
     if (const char* sv = getenv("MCL_VISIT_BINS")) {
       int b[3] = {0, 0, 0};
       if (sscanf(sv, "%d,%d,%d", &b[0], &b[1], &b[2]) == 3 && b[0] >= 1 && b[1] >= 1 && b[2] >= 1 &&
@@ -174,9 +181,7 @@ int mcl_destroy(mcl_handle* h) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
   }
-  if (h->comm2) ncclCommDestroy(h->comm2);
-  if (h->comm) ncclCommDestroy(h->comm);
-  h->comm2 = h->comm = nullptr;
+  comm_teardown(h, false);
   if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
   if (h->ev_state_ready) (void)hipEventDestroy(h->ev_state_ready);
   if (h->ev_gather_done) (void)hipEventDestroy(h->ev_gather_done);
@@ -206,18 +211,13 @@ int mcl_init_particles(mcl_handle* h, const double* replay_normals) {
     RET_IF(upload_replay(h, replay_normals));
     rp = h->replay_dev;
   }
-  RET_IF(cancel_state_gather(h));
-  h->uni_valid = false;
-  h->visit_ready = false;
+  RET_IF(state_overwritten(h));
   NoiseArgs a = noise_args(h, h->cfg.init_cov, 0u, 0u);
   t_begin(h, MCL_K_NOISE);
   k_add_noise<<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, rp, 1);
   t_end(h);
   HIPCHK(h, hipGetLastError());
-  h->step_predict = 0;
-  h->step_resample = 0;
-  h->step_inject = 0;
-  h->have_lw = h->have_cdf = false;
+  filter_restarted(h);
   return MCL_OK;
 }
 
@@ -275,20 +275,7 @@ int mcl_set_map_grid(mcl_handle* h, const float* z, int32_t nx, int32_t ny, doub
   h->gres = res;
   h->gzmin = mn;
   h->gzmax = mx;
-  {
-    // steepest gradient of a bilinear patch: its x slope lies between those of the cell's two x edges, its y slope
-    // between those of the two y edges
-    double g2 = 0.0;
-    for (int ix = 0; ix + 1 < nx; ++ix)
-      for (int iy = 0; iy + 1 < ny; ++iy) {
-        const size_t k = (size_t)ix * ny + iy;
-        const double h00 = z[k], h01 = z[k + 1], h10 = z[k + ny], h11 = z[k + ny + 1];
-        const double ax = std::max(std::fabs(h10 - h00), std::fabs(h11 - h01));
-        const double ay = std::max(std::fabs(h01 - h00), std::fabs(h11 - h10));
-        g2 = std::max(g2, ax * ax + ay * ay);
-      }
-    h->gslope_max = std::sqrt(g2) / res;
-  }
+  h->gslope_max = grid_slope_max(z, nx, ny, res);
   h->map_kind = 0;
   h->map_xy[0] = ox;
   h->map_xy[1] = ox + (nx - 1) * res;
@@ -380,44 +367,9 @@ int mcl_set_landmarks(mcl_handle* h, const double* xyz, int64_t n_landmarks) {
   return MCL_OK;
 }
 
-namespace {
-// largest eigenvalue bound of a symmetric 3x3 (xx xy xz yy yz zz): Gershgorin
-double sym3_lam_bound(const double* s) {
-  const double r0 = s[0] + std::fabs(s[1]) + std::fabs(s[2]), r1 = s[3] + std::fabs(s[1]) + std::fabs(s[4]),
-               r2 = s[5] + std::fabs(s[2]) + std::fabs(s[4]);
-  return std::max(r0, std::max(r1, r2));
-}
-double sym3_det(const double* s) {
-  return s[0] * (s[3] * s[5] - s[4] * s[4]) - s[1] * (s[1] * s[5] - s[4] * s[2]) + s[2] * (s[1] * s[4] - s[3] * s[2]);
-}
-// measurement covariance of this update: the Q of mcl_set_landmark_noise, else sigma^2 I
-void landmark_q(const LandmarkDev* L, double sigma, double Q[6]) {
-  if (L->have_q) {
-    for (int k = 0; k < 6; ++k) Q[k] = L->Q[k];
-  } else {
-    Q[0] = Q[3] = Q[5] = sigma * sigma;
-    Q[1] = Q[2] = Q[4] = 0.0;
-  }
-}
-// every landmark inside the gate lies within this distance of the detection: d^2 >= |nu|^2 / lambda_max(S)
-double landmark_gate_radius(const LandmarkDev* L, double sigma, double gate) {
-  if (!L->maha) return sigma * std::sqrt(gate);
-  double Q[6];
-  landmark_q(L, sigma, Q);
-  return std::sqrt(gate * (L->lam_cov_max + sym3_lam_bound(Q)));
-}
-void landmark_noise_args(const LandmarkDev* L, double sigma, LandmarkArgs& a) {
-  a.maha = L->maha ? 1 : 0;
-  a.lmcov = L->lmcov;
-  landmark_q(L, sigma, a.Q);
-  a.logdet_q = std::log(sym3_det(a.Q));
-  a.lognorm = 1.5 * std::log(2.0 * MCL_PI) + 0.5 * a.logdet_q;  // isotropic: 3/2 log 2pi + 3 log sigma
-}
-}  // namespace
-
 int mcl_set_landmark_noise(mcl_handle* h, const double* cov6, const double Q6[6]) {
   if (!h) return MCL_ERR_INVALID;
-  if (!h->landmarks) return fail(h, MCL_ERR_STATE, "set_landmark_noise: no feature map (call mcl_set_landmarks first)");
+  RET_IF(need_feature_map(h, "set_landmark_noise"));
   RET_IF(set_device(h));
   LandmarkDev* L = h->landmarks;
   const size_t n = L->host_xyz.size() / 3;
@@ -443,108 +395,12 @@ int mcl_set_landmark_noise(mcl_handle* h, const double* cov6, const double Q6[6]
   return MCL_OK;
 }
 
-namespace {
-// one landmark observation (mcl_update_landmarks' arguments)
-struct LandmarkObs {
-  const double* det;
-  int n_det;
-  double sigma;
-  int k;
-  double gate;
-  const double* so;
-};
-int landmarks_upload(mcl_handle* h, const LandmarkObs& o) {
-  RESERVE(h, h->det_dev, 3 * (size_t)o.n_det);
-  return upload(h, h->det_dev, o.det, sizeof(double) * 3 * (size_t)o.n_det);
-}
-// argument checks and the cell grid for this gate radius.  (A grid rebuild drains the
-// stream -- the old arrays may still be read by a kernel in flight -- so the fused step calls this BEFORE its predict.)
-// ride: the fused step -- the detections are not copied here; they wait for the beam table's staged copy of the same
-// step (upload_sweep_beams; landmarks_launch copies them itself if the update took a path without that table)
-int landmarks_prepare(mcl_handle* h, const LandmarkObs& o, const char* who, bool ride = false) {
-  if (!o.det || o.n_det < 1 || !(o.sigma > 0.0) || o.k < 1 || o.k > LM_MAX_K || !(o.gate > 0.0))
-    return fail(h, MCL_ERR_INVALID, std::string(who) + ": bad argument (1 <= k <= 4)");
-  if (!h->landmarks) return fail(h, MCL_ERR_STATE, std::string(who) + ": no feature map (call mcl_set_landmarks first)");
-  RET_IF(set_device(h));
-  const double radius = landmark_gate_radius(h->landmarks, o.sigma, o.gate);
-  if (!(h->landmarks->built_for == radius && h->landmarks->lm)) {
-    std::string err;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    int rc = landmarks_build(h->landmarks, radius, &err);
-    if (rc != MCL_OK) {
-      h->err = err;
-      return rc;
-    }
-  }
-  h->det_ride = nullptr;
-  h->det_ride_dev = nullptr;
-  if (ride) {
-    h->det_ride = o.det;
-    h->det_ride_n = o.n_det;
-  }
-  return MCL_OK;   // (landmarks_launch copies detections that did not ride)
-}
-// the k-NN landmark likelihood of every particle.  fused: inside mcl_step_mbes_landmarks -- the predict kernel of the
-// same call may have left z, roll, pitch unstored (uni_deferred), and the kernel leaves max lw in the second slot set
-int landmarks_launch(mcl_handle* h, const LandmarkObs& o, bool accumulate, bool fused) {
-  static const double zero6[6] = {0, 0, 0, 0, 0, 0};
-  const double* so = o.so ? o.so : zero6;
-  // the detections: where the beam table's copy of this step left them, or (an update without that table: no sweep)
-  // copied now
-  const double* det = h->det_ride_dev;
-  if (!det) {
-    RET_IF(landmarks_upload(h, o));
-    det = h->det_dev;
-  }
-  h->det_ride = nullptr;
-  h->det_ride_dev = nullptr;
-  LandmarkArgs a;
-  memset(&a, 0, sizeof a);
-  for (int c = 0; c < 6; ++c) a.st[c] = h->state[h->cur] + (size_t)c * h->n;
-  a.n = h->n;
-  for (int q = 0; q < 12; ++q) a.m2o[q] = h->cfg.m2o[q];
-  for (int q = 0; q < 3; ++q) a.off_t[q] = so[q];
-  rot_rpy(so[3], so[4], so[5], a.off_R);
-  a.det = det;
-  a.n_det = o.n_det;
-  a.lm = h->landmarks->lm;
-  a.cell_start = h->landmarks->cell_start;
-  a.nb_cell = h->landmarks->nb_cell;
-  a.nb_list = h->landmarks->nb_list;
-  a.gx = h->landmarks->gx;
-  a.gy = h->landmarks->gy;
-  a.x0 = h->landmarks->x0;
-  a.y0 = h->landmarks->y0;
-  a.inv_cs = 1.0 / h->landmarks->cs;
-  a.inv_s2 = 1.0 / (o.sigma * o.sigma);
-  a.gate = o.gate;
-  landmark_noise_args(h->landmarks, o.sigma, a);
-  a.k = o.k;
-  a.accumulate = accumulate ? 1 : 0;
-  a.lw = h->lw;
-  a.uni_mask = (fused && h->uni_deferred) ? UNI_ZRP : 0u;
-  for (int c = 0; c < 3; ++c) a.uni[c] = h->uni_val[c];
-  a.max_slots = fused ? (u64*)(h->ctrl + CTRL_SLOTS2) : nullptr;   // (zeroed with the whole block by this step's predict / pose launch)
-  t_begin(h, MCL_K_UPDATE_LANDMARKS);
-  long long blocks = (h->n + 255) / 256;   // (a wave per 64 particles, four waves per workgroup)
-  if (blocks > 16384) blocks = 16384;
-  if (a.maha)
-    k_landmark_update<true><<<(unsigned)blocks, 256, 0, h->stream>>>(a);
-  else
-    k_landmark_update<false><<<(unsigned)blocks, 256, 0, h->stream>>>(a);
-  t_end(h);
-  HIPCHK(h, hipGetLastError());
-  weights_written(h, accumulate ? WEIGHT_MODE_KEEP : MCL_WEIGHT_LOG_SHIFT, fused ? SLOTS_SET1 : SLOTS_NONE);
-  return MCL_OK;
-}
-}  // namespace
-
 int mcl_update_landmarks(mcl_handle* h, const double* det_xyz, int32_t n_det, double sigma, int32_t k, double gate,
                          const double sensor_offset[6], int32_t accumulate) {
   if (!h) return MCL_ERR_INVALID;
   const LandmarkObs o = {det_xyz, n_det, sigma, k, gate, sensor_offset};
   RET_IF(landmarks_prepare(h, o, "update_landmarks"));
-  if (accumulate && !h->have_lw) return fail(h, MCL_ERR_STATE, "update_landmarks: nothing to accumulate onto");
+  if (accumulate) RET_IF(need_weights_to_add(h, "update_landmarks"));
   return landmarks_launch(h, o, accumulate != 0, false);
 }
 
@@ -554,137 +410,13 @@ int mcl_update_landmarks_assign(mcl_handle* h, const double* det_xyz, int32_t n_
   if (!h || !det_xyz || n_det < 1 || n_det > LM_SUB || !(sigma > 0.0) || k_cand < 1 || k_cand > LA_KC || !(gate > 0.0) ||
       !(new_mh_dist >= 0.0) || n_keep < 0 || (n_keep > 0 && !assign_out))
     return fail(h, MCL_ERR_INVALID, "update_landmarks_assign: bad argument (n_det <= 16, 1 <= k_cand <= 8)");
-  if (!h->landmarks) return fail(h, MCL_ERR_STATE, "update_landmarks_assign: no feature map (call mcl_set_landmarks first)");
-  if (accumulate && !h->have_lw) return fail(h, MCL_ERR_STATE, "update_landmarks_assign: nothing to accumulate onto");
+  RET_IF(need_feature_map(h, "update_landmarks_assign"));
+  if (accumulate) RET_IF(need_weights_to_add(h, "update_landmarks_assign"));
   RET_IF(set_device(h));
-  {
-    // the cell grid depends on the gate radius only: rebuild (and drain the stream first -- the old
-    // arrays may still be read by a kernel in flight) only when it changes
-    const double radius = landmark_gate_radius(h->landmarks, sigma, gate);
-    if (!(h->landmarks->built_for == radius && h->landmarks->lm)) {
-      std::string err;
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      int rc = landmarks_build(h->landmarks, radius, &err);
-      if (rc != MCL_OK) {
-        h->err = err;
-        return rc;
-      }
-    }
-  }
-  RET_IF(landmarks_upload(h, LandmarkObs{det_xyz, n_det, sigma, k_cand, gate, sensor_offset}));
-  if (n_keep > h->n) n_keep = h->n;
-  int* asg_dev = nullptr;
-  if (n_keep > 0) {
-    RESERVE(h, h->asg_dev, (size_t)n_keep * (size_t)n_det);
-    asg_dev = h->asg_dev;
-  }
-  static const double zero6[6] = {0, 0, 0, 0, 0, 0};
-  const double* so = sensor_offset ? sensor_offset : zero6;
-  LandmarkAssignArgs aa;
-  memset(&aa, 0, sizeof aa);   // (uni_mask = 0, max_slots = nullptr: the state is read as stored)
-  LandmarkArgs& a = aa.base;
-  for (int c = 0; c < 6; ++c) a.st[c] = h->state[h->cur] + (size_t)c * h->n;
-  a.n = h->n;
-  for (int q = 0; q < 12; ++q) a.m2o[q] = h->cfg.m2o[q];
-  for (int q = 0; q < 3; ++q) a.off_t[q] = so[q];
-  rot_rpy(so[3], so[4], so[5], a.off_R);
-  a.det = h->det_dev;
-  a.n_det = n_det;
-  a.lm = h->landmarks->lm;
-  a.cell_start = h->landmarks->cell_start;
-  a.nb_cell = h->landmarks->nb_cell;
-  a.nb_list = h->landmarks->nb_list;
-  a.gx = h->landmarks->gx;
-  a.gy = h->landmarks->gy;
-  a.x0 = h->landmarks->x0;
-  a.y0 = h->landmarks->y0;
-  a.inv_cs = 1.0 / h->landmarks->cs;
-  a.inv_s2 = 1.0 / (sigma * sigma);
-  a.gate = gate;
-  landmark_noise_args(h->landmarks, sigma, a);
-  a.k = k_cand;
-  a.accumulate = accumulate ? 1 : 0;
-  a.lw = h->lw;
-  aa.orig = h->landmarks->orig;
-  aa.new_mh = new_mh_dist;
-  aa.k_cand = k_cand;
-  aa.assign_out = asg_dev;
-  aa.n_keep = n_keep;
-  RESERVE(h, h->lm_worklist, (size_t)h->n + 1);
-  aa.worklist = h->lm_worklist;
-  aa.work_count = h->lm_worklist + h->n;
-  hipError_t le = hipMemsetAsync(aa.work_count, 0, sizeof(int), h->stream);
-  if (le == hipSuccess) {
-    t_begin(h, MCL_K_UPDATE_LANDMARKS);
-    long long blocks = (h->n + LA_PER_BLOCK - 1) / LA_PER_BLOCK;
-    if (blocks > 32768) blocks = 32768;
-    // every particle: conflict-free answer or worklist entry; then the solver over the worklist (its grid
-    // strides over the device-side count)
-    k_landmark_assign<false><<<(unsigned)blocks, LA_PER_BLOCK * LM_SUB, 0, h->stream>>>(aa);
-    k_landmark_assign<true><<<(unsigned)std::min<long long>(blocks, 2048), LA_PER_BLOCK * LM_SUB, 0, h->stream>>>(aa);
-    t_end(h);
-    le = hipGetLastError();
-  }
-  if (le == hipSuccess && n_keep > 0)
-    le = hipMemcpyAsync(assign_out, asg_dev, sizeof(int) * (size_t)n_keep * n_det, hipMemcpyDeviceToHost, h->stream);
-  if (le == hipSuccess && n_keep > 0) le = hipStreamSynchronize(h->stream);
-  HIPCHK(h, le);
-  weights_written(h, accumulate ? WEIGHT_MODE_KEEP : MCL_WEIGHT_LOG_SHIFT, SLOTS_NONE);
-  return MCL_OK;
+  RET_IF(ensure_landmark_grid(h, sigma, gate));
+  const LandmarkObs o = {det_xyz, n_det, sigma, k_cand, gate, sensor_offset};
+  return landmarks_assign_launch(h, o, new_mh_dist, accumulate != 0, assign_out, n_keep);
 }
-
-namespace {
-// DVL / altimeter ranges (mcl_ranges.h): the beam table -- directions normalised in fp64, then rounded -- and the map go
-// into the kernel's argument block; one launch over the particles [first, first + count).
-int ranges_launch(mcl_handle* h, const float* ranges, const float* dirs, int B, double sigma, double r_max,
-                  const double sensor_offset[6], bool accumulate, double* lw_out, float* exp_out, long long first,
-                  long long count) {
-  RangesArgs ra;
-  memset(&ra, 0, sizeof ra);
-  for (int b = 0; b < B; ++b) {
-    const double x = dirs[3 * b], y = dirs[3 * b + 1], z = dirs[3 * b + 2];
-    const double nrm = std::sqrt(x * x + y * y + z * z);
-    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(h, MCL_ERR_INVALID, "update_ranges: a beam direction is zero or not finite");
-    ra.beam[b] = make_float4((float)(x / nrm), (float)(y / nrm), (float)(z / nrm), ranges ? ranges[b] : 0.f);
-  }
-  RET_IF(materialise_uniform(h));
-  fill_frames_and_map(h, sensor_offset, r_max, ra.m);
-  // the map walk: 0 the height grid, 2 the node heights of a triangulated regular grid, 1 triangle records
-  const int map = h->map_kind == 0 ? 0 : (structured_mesh(h) ? 2 : 1);
-  int lg = 0;
-  while ((1 << lg) < B) ++lg;
-  ra.i0 = first;
-  ra.i1 = first + count;
-  ra.n_beams = B;
-  ra.lg_bp = lg;
-  ra.accumulate = accumulate ? 1 : 0;
-  ra.sigma = sigma;
-  ra.lognorm = std::log(sigma * std::sqrt(2.0 * MCL_PI));
-  ra.lw = lw_out;
-  ra.exp_out = exp_out;
-  const long long per_block = RANGES_THREADS >> lg;
-  const unsigned grid = (unsigned)std::min<long long>((count + per_block - 1) / per_block, 1ll << 16);
-  const bool expect = exp_out != nullptr;
-  if (!expect) t_begin(h, MCL_K_UPDATE_MBES);
-#define LAUNCH_RANGES(MAPV)                                                              \
-  do {                                                                                   \
-    if (expect)                                                                          \
-      k_ranges_update<MAPV, true><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);           \
-    else                                                                                 \
-      k_ranges_update<MAPV, false><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);          \
-  } while (0)
-  if (map == 0)
-    LAUNCH_RANGES(0);
-  else if (map == 2)
-    LAUNCH_RANGES(2);
-  else
-    LAUNCH_RANGES(1);
-#undef LAUNCH_RANGES
-  if (!expect) t_end(h);
-  HIPCHK(h, hipGetLastError());
-  return MCL_OK;
-}
-}  // namespace
 
 int mcl_update_ranges(mcl_handle* h, const float* ranges, const float* dirs, int32_t n_beams, double sigma, double r_max,
                       const double sensor_offset[6], int32_t accumulate) {
@@ -692,8 +424,8 @@ int mcl_update_ranges(mcl_handle* h, const float* ranges, const float* dirs, int
   if (!ranges || !dirs || n_beams < 1 || n_beams > RANGES_MAX_BEAMS || !(sigma > 0.0) || !(r_max > 0.0))
     return fail(h, MCL_ERR_INVALID, "update_ranges: bad argument (1 <= n_beams <= 16, sigma > 0, r_max > 0)");
   RET_IF(set_device(h));
-  if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "update_ranges: no map (call mcl_set_map_grid/mesh first)");
-  if (accumulate && !h->have_lw) return fail(h, MCL_ERR_STATE, "update_ranges: nothing to accumulate onto");
+  RET_IF(need_map(h, "update_ranges"));
+  if (accumulate) RET_IF(need_weights_to_add(h, "update_ranges"));
   RET_IF(ranges_launch(h, ranges, dirs, n_beams, sigma, r_max, sensor_offset, accumulate != 0, h->lw, nullptr, 0, h->n));
   weights_written(h, accumulate ? WEIGHT_MODE_KEEP : MCL_WEIGHT_LOG_SHIFT, SLOTS_NONE);
   return MCL_OK;
@@ -706,7 +438,7 @@ int mcl_ranges_expected(mcl_handle* h, int64_t first, int64_t count, const float
       first + count > h->n)
     return fail(h, MCL_ERR_INVALID, "ranges_expected: bad argument");
   RET_IF(set_device(h));
-  if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "ranges_expected: no map (call mcl_set_map_grid/mesh first)");
+  RET_IF(need_map(h, "ranges_expected"));
   const size_t need = (size_t)count * (size_t)n_beams;
   RESERVE(h, h->exp_dev, need);
   RET_IF(ranges_launch(h, nullptr, dirs, n_beams, 1.0, r_max, sensor_offset, false, nullptr, h->exp_dev, first, count));
@@ -822,9 +554,7 @@ int mcl_get_particles(mcl_handle* h, double* soa, double* w) {
 int mcl_set_particles(mcl_handle* h, const double* soa) {
   if (!h || !soa) return MCL_ERR_INVALID;
   RET_IF(set_device(h));
-  RET_IF(cancel_state_gather(h));
-  h->uni_valid = false;
-  h->visit_ready = false;
+  RET_IF(state_overwritten(h));
   HIPCHK(h, hipMemcpyAsync(h->state[h->cur], soa, sizeof(double) * 6 * (size_t)h->n, hipMemcpyHostToDevice,
                            h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -903,89 +633,39 @@ int abandon_step(mcl_handle* failed, mcl_handle** sh, int n, int rc) {
   return rc;
 }
 // the fused step of one handle (mcl_step_mbes; with a landmark observation: mcl_step_mbes_landmarks)
-int step_mbes_impl(mcl_handle* h, const mcl_odom* odom, double dt, const float* ranges, const float* beam_angles, int32_t B,
-                   double sigma, double r_max, const double sensor_offset[6], const LandmarkObs* lm, const char* who) {
-  if (!h || !odom || !ranges || !beam_angles) return MCL_ERR_INVALID;
-  const std::string w(who);
-  if (h->cfg.rng_mode != MCL_RNG_NATIVE) return fail(h, MCL_ERR_INVALID, w + ": NATIVE rng only");
-  if (h->world > 1 && !h->comm) return fail(h, MCL_ERR_STATE, w + ": multi-shard handle needs mcl_comm_init");
-  if (B < 1 || !(sigma > 0.0) || !(r_max > 0.0)) return fail(h, MCL_ERR_INVALID, w + ": bad argument");
-  if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, w + ": no map (call mcl_set_map_grid/mesh first)");
-  RET_IF(set_device(h));
-  // predict writes the MBES pose records of the new state in the same pass (the map and sensor offset are known here)
-  // (the beam table first: the group classification in that kernel follows the two extreme beams)
-  RET_IF(upload_beams(h, ranges, beam_angles, B));
-  if (lm) RET_IF(landmarks_prepare(h, *lm, who, true));   // (after upload_beams: it forgets detections an earlier call left waiting)
-  MbesPlan plan;
-  RET_IF(plan_mbes(h, B, sigma, r_max, sensor_offset, nullptr, plan));
-  bool pose_done = false;
-  const bool sys = h->cfg.resample_scheme == MCL_RESAMPLE_SYSTEMATIC || h->cfg.resample_scheme == MCL_RESAMPLE_NAIVE;
+int step_mbes_impl(mcl_handle* h, const StepIn& in) {
+  if (!h || !in.odom || !in.ranges || !in.beam_angles) return MCL_ERR_INVALID;
+  RET_IF(step_check(h, in, false));
+  RET_IF(step_stage(h, in));
   // (systematic scheme: the gather of this call substitutes z, roll, pitch -- the predict kernel does not store them)
-  RET_IF(do_predict(h, odom, dt, nullptr, &plan.args, &pose_done, sys));
-  int rc_u = h->fault_step ? fail(h, MCL_ERR_STATE, w + ": injected fault after predict") : start_state_gather(h);
-  if (rc_u == MCL_OK) rc_u = run_mbes(h, plan, pose_done);
-  if (rc_u == MCL_OK) {
-    weights_written(h, MCL_WEIGHT_LOG_SHIFT, SLOTS_SET0);
-    // the landmark likelihood of the same ping on top (BASELINE config 5): reads the state the predict left (z, roll,
-    // pitch from the odometry when that kernel did not store them), leaves max lw in the second slot set
-    if (lm) rc_u = landmarks_launch(h, *lm, true, true);
-  }
-  if (rc_u != MCL_OK) {
+  const bool sys = h->cfg.resample_scheme == MCL_RESAMPLE_SYSTEMATIC || h->cfg.resample_scheme == MCL_RESAMPLE_NAIVE;
+  int rc = step_front(h, in, sys, true);
+  if (rc != MCL_OK) {
     const std::string keep = h->err;
     (void)cancel_state_gather(h);
     (void)materialise_uniform(h);
     h->err = keep;
-    return rc_u;
+    return rc;
   }
   // resample; the gather pass also accumulates the sums of update_loc_pose of the new state
-  rc_u = run_resample(&h, 1, nullptr, 0, nullptr, sys);
-  if (rc_u != MCL_OK) return abandon_step(h, &h, 1, rc_u);
-  if (sys)
-    RET_IF(collect_fused_moments(&h, 1));
-  else
-    RET_IF(run_mean_cov_async(&h, 1));
-  return MCL_OK;
+  rc = run_resample(&h, 1, nullptr, 0, nullptr, sys);
+  if (rc != MCL_OK) return abandon_step(h, &h, 1, rc);
+  return sys ? collect_fused_moments(&h, 1) : run_mean_cov_async(&h, 1);
 }
 
-int group_step_mbes_impl(mcl_handle** shards, int32_t ns, const mcl_odom* odom, double dt, const float* ranges,
-                         const float* beam_angles, int32_t B, double sigma, double r_max, const double sensor_offset[6],
-                         const LandmarkObs* lm, const char* who) {
-  if (!shards || ns < 1 || !odom || !ranges || !beam_angles) return MCL_ERR_INVALID;
-  const std::string w(who);
+int group_step_mbes_impl(mcl_handle** shards, int32_t ns, const StepIn& in) {
+  if (!shards || ns < 1 || !in.odom || !in.ranges || !in.beam_angles) return MCL_ERR_INVALID;
   for (int s = 0; s < ns; ++s)
     if (!shards[s] || shards[s]->world != ns || shards[s]->rank != s)
-      return fail(shards[0], MCL_ERR_INVALID, w + ": shards must be ranks 0..n-1 of one world");
-  if (B < 1 || !(sigma > 0.0) || !(r_max > 0.0)) return fail(shards[0], MCL_ERR_INVALID, w + ": bad argument");
-  for (int s = 0; s < ns; ++s) {
-    mcl_handle* h = shards[s];
-    if (h->cfg.rng_mode != MCL_RNG_NATIVE) return fail(h, MCL_ERR_INVALID, w + ": NATIVE rng only");
-    if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, w + ": no map (call mcl_set_map_grid/mesh first)");
-    if (h->cfg.resample_scheme != MCL_RESAMPLE_SYSTEMATIC && h->cfg.resample_scheme != MCL_RESAMPLE_NAIVE)
-      return fail(h, MCL_ERR_UNSUPPORTED, w + ": only the systematic scheme is sharded");
-    if (lm && !h->landmarks) return fail(h, MCL_ERR_STATE, w + ": no feature map (call mcl_set_landmarks first)");
-  }
+      return fail(shards[0], MCL_ERR_INVALID, std::string(in.who) + ": shards must be ranks 0..n-1 of one world");
+  for (int s = 0; s < ns; ++s) RET_IF(step_check(shards[s], in, true));
   // everything that can fail before a kernel is queued, for EVERY shard first: a later shard's failure must not find
   // earlier shards with a predict in flight whose z / roll / pitch stores were deferred to the gather
+  for (int s = 0; s < ns; ++s) RET_IF(step_stage(shards[s], in));
   for (int s = 0; s < ns; ++s) {
     mcl_handle* h = shards[s];
-    RET_IF(set_device(h));
-    RET_IF(upload_beams(h, ranges, beam_angles, B));
-    if (lm) RET_IF(landmarks_prepare(h, *lm, who, true));
-  }
-  for (int s = 0; s < ns; ++s) {
-    mcl_handle* h = shards[s];
-    // the same fused front half as mcl_step_mbes: predict writes the pose records, the sweep leaves max lw in the slots
     int rc = set_device(h);
-    MbesPlan plan;
-    if (rc == MCL_OK) rc = plan_mbes(h, B, sigma, r_max, sensor_offset, nullptr, plan);
-    bool pose_done = false;
-    if (rc == MCL_OK) rc = do_predict(h, odom, dt, nullptr, &plan.args, &pose_done, true);
-    if (rc == MCL_OK && h->fault_step) rc = fail(h, MCL_ERR_STATE, w + ": injected fault after predict");
-    if (rc == MCL_OK) rc = run_mbes(h, plan, pose_done);
-    if (rc == MCL_OK) {
-      weights_written(h, MCL_WEIGHT_LOG_SHIFT, SLOTS_SET0);
-      if (lm) rc = landmarks_launch(h, *lm, true, true);
-    }
+    if (rc == MCL_OK) rc = step_front(h, in, true, false);   // (no overlapped gather in a LOCAL group: device copies)
     if (rc != MCL_OK) return abandon_step(h, shards, s + 1, rc);
   }
   const int rc = run_resample(shards, ns, nullptr, 0, nullptr, true);
@@ -996,20 +676,20 @@ int group_step_mbes_impl(mcl_handle** shards, int32_t ns, const mcl_odom* odom, 
 
 int mcl_step_mbes(mcl_handle* h, const mcl_odom* odom, double dt, const float* ranges, const float* beam_angles,
                   int32_t B, double sigma, double r_max, const double sensor_offset[6]) {
-  return step_mbes_impl(h, odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, nullptr, "step_mbes");
+  return step_mbes_impl(h, StepIn{odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, nullptr, "step_mbes"});
 }
 
 int mcl_step_mbes_landmarks(mcl_handle* h, const mcl_odom* odom, double dt, const float* ranges, const float* beam_angles,
                             int32_t B, double sigma, double r_max, const double sensor_offset[6], const double* det_xyz,
                             int32_t n_det, double lm_sigma, int32_t k, double gate, const double lm_sensor_offset[6]) {
   const LandmarkObs o = {det_xyz, n_det, lm_sigma, k, gate, lm_sensor_offset};
-  return step_mbes_impl(h, odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, &o, "step_mbes_landmarks");
+  return step_mbes_impl(h, StepIn{odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, &o, "step_mbes_landmarks"});
 }
 
 int mcl_group_step_mbes(mcl_handle** shards, int32_t ns, const mcl_odom* odom, double dt, const float* ranges,
                         const float* beam_angles, int32_t B, double sigma, double r_max, const double sensor_offset[6]) {
-  return group_step_mbes_impl(shards, ns, odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, nullptr,
-                              "group_step_mbes");
+  return group_step_mbes_impl(shards, ns,
+                              StepIn{odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, nullptr, "group_step_mbes"});
 }
 
 int mcl_group_step_mbes_landmarks(mcl_handle** shards, int32_t ns, const mcl_odom* odom, double dt, const float* ranges,
@@ -1017,8 +697,8 @@ int mcl_group_step_mbes_landmarks(mcl_handle** shards, int32_t ns, const mcl_odo
                                   const double sensor_offset[6], const double* det_xyz, int32_t n_det, double lm_sigma,
                                   int32_t k, double gate, const double lm_sensor_offset[6]) {
   const LandmarkObs o = {det_xyz, n_det, lm_sigma, k, gate, lm_sensor_offset};
-  return group_step_mbes_impl(shards, ns, odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, &o,
-                              "group_step_mbes_landmarks");
+  return group_step_mbes_impl(
+      shards, ns, StepIn{odom, dt, ranges, beam_angles, B, sigma, r_max, sensor_offset, &o, "group_step_mbes_landmarks"});
 }
 
 int mcl_exchange_plan(int32_t world, const uint32_t* lost, const uint32_t* surplus, int32_t rank, uint32_t* send_off,
@@ -1114,13 +794,6 @@ int wait_event_ms(hipEvent_t ev, int timeout_ms) {
       return 1;
     std::this_thread::sleep_for(std::chrono::microseconds(200));
   }
-}
-void comm_teardown(mcl_handle* h, bool abort) {
-  if (h->comm2) (void)(abort ? ncclCommAbort(h->comm2) : ncclCommDestroy(h->comm2));
-  if (h->comm) (void)(abort ? ncclCommAbort(h->comm) : ncclCommDestroy(h->comm));
-  h->comm2 = nullptr;
-  h->comm = nullptr;
-  h->gather_inflight = false;
 }
 }  // namespace
 
@@ -1281,14 +954,10 @@ int mcl_mbes_visit_order(mcl_handle* h, uint32_t* slots, int32_t* sorted) {
 namespace {
 // the argument block of k_uniform_state from a caller's box: bounds checked, the MAP frame resolved against cfg.m2o
 int uniform_args(mcl_handle* h, const mcl_box* box, uint32_t purpose, uint32_t step, const char* who, UniformArgs& a) {
-  const std::string w(who);
+  const char* reason;
+  const int rc = check_box(box, h->cfg.m2o, &reason);
+  if (rc != MCL_OK) return fail(h, rc, std::string(who) + ": " + reason);
   const double b[6] = {box->x_min, box->x_max, box->y_min, box->y_max, box->yaw_min, box->yaw_max};
-  for (int c = 0; c < 3; ++c) {
-    if (!std::isfinite(b[2 * c]) || !std::isfinite(b[2 * c + 1])) return fail(h, MCL_ERR_INVALID, w + ": a bound of the box is not finite");
-    if (b[2 * c + 1] < b[2 * c]) return fail(h, MCL_ERR_INVALID, w + ": a maximum of the box lies below its minimum");
-  }
-  if (box->yaw_max - box->yaw_min > 2.0 * MCL_PI) return fail(h, MCL_ERR_INVALID, w + ": the yaw interval is longer than 2 pi");
-  if (box->frame != MCL_FRAME_ODOM && box->frame != MCL_FRAME_MAP) return fail(h, MCL_ERR_INVALID, w + ": unknown frame");
   memset(&a, 0, sizeof a);
   for (int c = 0; c < 3; ++c) {
     a.lo[c] = b[2 * c];
@@ -1297,9 +966,6 @@ int uniform_args(mcl_handle* h, const mcl_box* box, uint32_t purpose, uint32_t s
   }
   if (box->frame == MCL_FRAME_MAP) {
     const double* m = h->cfg.m2o;
-    if (std::fabs(m[2]) > 1e-12 || std::fabs(m[6]) > 1e-12 || std::fabs(m[8]) > 1e-12 || std::fabs(m[9]) > 1e-12 ||
-        std::fabs(m[10] - 1.0) > 1e-12)
-      return fail(h, MCL_ERR_UNSUPPORTED, w + ": a box in the map frame needs an m2o that turns about z alone");
     a.r00 = m[0];
     a.r01 = m[1];
     a.r10 = m[4];
@@ -1325,7 +991,7 @@ int upload_replay_uniforms(mcl_handle* h, const double* u, int per) {
 
 int mcl_map_bounds(mcl_handle* h, double xy_min_max[4]) {
   if (!h || !xy_min_max) return MCL_ERR_INVALID;
-  if (h->map_kind < 0) return fail(h, MCL_ERR_STATE, "map_bounds: no map (call mcl_set_map_grid/mesh first)");
+  RET_IF(need_map(h, "map_bounds"));
   for (int k = 0; k < 4; ++k) xy_min_max[k] = h->map_xy[k];
   return MCL_OK;
 }
@@ -1342,17 +1008,12 @@ int mcl_init_particles_uniform(mcl_handle* h, const mcl_box* box, const double* 
     RET_IF(upload_replay_uniforms(h, replay_uniforms, 3));
     rp = h->replay_dev;
   }
-  RET_IF(cancel_state_gather(h));
-  h->uni_valid = false;
-  h->visit_ready = false;
+  RET_IF(state_overwritten(h));
   t_begin(h, MCL_K_NOISE);
   k_uniform_state<false><<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, rp, nullptr);
   t_end(h);
   HIPCHK(h, hipGetLastError());
-  h->step_predict = 0;
-  h->step_resample = 0;
-  h->step_inject = 0;
-  h->have_lw = h->have_cdf = false;
+  filter_restarted(h);
   return MCL_OK;
 }
 
@@ -1411,9 +1072,7 @@ int mcl_inject_uniform(mcl_handle* h, double fraction, const mcl_box* box, const
     rp = h->replay_dev;
   }
   RESERVE(h, h->inject_cnt, 1 + MCL_MAX_GRID);
-  RET_IF(cancel_state_gather(h));
-  h->uni_valid = false;
-  h->visit_ready = false;
+  RET_IF(state_overwritten(h));
   const int grid = grid_for(h->n);
   t_begin(h, MCL_K_NOISE);
   k_uniform_state<true><<<grid, MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, rp, h->inject_cnt + 1);

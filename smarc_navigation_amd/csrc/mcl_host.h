@@ -1,6 +1,7 @@
 // mcl_host.h -- host side of libmcl_hip.so, part 1: the handle (device buffers, streams, communicators, caches) and
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
-// One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h
+// One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
+// mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -434,6 +435,45 @@ void weights_written(mcl_handle* h, int mode, WeightSlots slots) {
   h->max_valid = slots != SLOTS_NONE;
   if (slots != SLOTS_NONE) h->slot_set = slots == SLOTS_SET1 ? 1 : 0;
   h->residual_k = -1;
+}
+
+// The particle state was overwritten by something that is neither a predict nor a resample (init, set_particles,
+// injection): an overlapped gather of the old state is forgotten, z / roll / pitch are no longer the odometry's and the
+// visiting order no longer describes the slots.  (A stale uni_valid would put the old odometry back, silently.)
+int cancel_state_gather(mcl_handle* h);   // (mcl_host_resample.h)
+int state_overwritten(mcl_handle* h) {
+  RET_IF(cancel_state_gather(h));
+  h->uni_valid = false;
+  h->visit_ready = false;
+  return MCL_OK;
+}
+// The filter starts again from fresh particles (both init calls): the Philox steps count from 0, no weights, no CDF.
+void filter_restarted(mcl_handle* h) {
+  h->step_predict = h->step_resample = h->step_inject = 0;
+  h->have_lw = h->have_cdf = false;
+}
+
+// What a call needs to have been there before it: MCL_ERR_STATE with the one sentence that says what to call first.
+int need_map(mcl_handle* h, const char* who) {
+  if (h->map_kind >= 0) return MCL_OK;
+  return fail(h, MCL_ERR_STATE, std::string(who) + ": no map (call mcl_set_map_grid/mesh first)");
+}
+int need_feature_map(mcl_handle* h, const char* who) {
+  if (h->landmarks) return MCL_OK;
+  return fail(h, MCL_ERR_STATE, std::string(who) + ": no feature map (call mcl_set_landmarks first)");
+}
+int need_weights_to_add(mcl_handle* h, const char* who) {
+  if (h->have_lw) return MCL_OK;
+  return fail(h, MCL_ERR_STATE, std::string(who) + ": nothing to accumulate onto");
+}
+
+// the communicators go (destroyed, or aborted after a collective that hung); an overlapped gather goes with them
+void comm_teardown(mcl_handle* h, bool abort) {
+  if (h->comm2) (void)(abort ? ncclCommAbort(h->comm2) : ncclCommDestroy(h->comm2));
+  if (h->comm) (void)(abort ? ncclCommAbort(h->comm) : ncclCommDestroy(h->comm));
+  h->comm2 = nullptr;
+  h->comm = nullptr;
+  h->gather_inflight = false;
 }
 
 }  // namespace

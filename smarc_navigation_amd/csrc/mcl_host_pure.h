@@ -1,6 +1,7 @@
 // mcl_host_pure.h -- the host arithmetic of libmcl_hip.so that touches no device: tf.transformations' Euler /
 // quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
-// weight statistics.  No HIP header: the
+// weight statistics, and the safety bounds kernels rely on unchecked (steepest patch gradient of a height grid, landmark
+// gate radius, the box of the uniform draws, the range update's beam table).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -186,6 +187,81 @@ int matrix_from_tf_impl(const double translation[3], const double quaternion[4],
   }
   m16[12] = m16[13] = m16[14] = 0.0;
   m16[15] = 1.0;
+  return MCL_OK;
+}
+
+// ---- safety bounds: each of them says how far something can reach, and a kernel relies on it unchecked
+
+// steepest gradient of the bilinear patches of a height grid (z[ix * ny + iy], node spacing res): the fan sweep's tilt
+// bound.  A patch's x slope lies between those of the cell's two x edges, its y slope between those of the two y edges.
+double grid_slope_max(const float* z, int nx, int ny, double res) {
+  double g2 = 0.0;
+  for (int ix = 0; ix + 1 < nx; ++ix)
+    for (int iy = 0; iy + 1 < ny; ++iy) {
+      const size_t k = (size_t)ix * ny + iy;
+      const double h00 = z[k], h01 = z[k + 1], h10 = z[k + ny], h11 = z[k + ny + 1];
+      const double ax = std::max(std::fabs(h10 - h00), std::fabs(h11 - h01));
+      const double ay = std::max(std::fabs(h01 - h00), std::fabs(h11 - h10));
+      g2 = std::max(g2, ax * ax + ay * ay);
+    }
+  return std::sqrt(g2) / res;
+}
+
+// largest eigenvalue bound of a symmetric 3x3 (xx xy xz yy yz zz): Gershgorin
+double sym3_lam_bound(const double* s) {
+  const double r0 = s[0] + std::fabs(s[1]) + std::fabs(s[2]), r1 = s[3] + std::fabs(s[1]) + std::fabs(s[4]),
+               r2 = s[5] + std::fabs(s[2]) + std::fabs(s[4]);
+  return std::max(r0, std::max(r1, r2));
+}
+double sym3_det(const double* s) {
+  return s[0] * (s[3] * s[5] - s[4] * s[4]) - s[1] * (s[1] * s[5] - s[4] * s[2]) + s[2] * (s[1] * s[4] - s[3] * s[2]);
+}
+// measurement covariance of a landmark update: the Q of mcl_set_landmark_noise (q_set; nullptr: none given), else sigma^2 I
+void landmark_q(const double* q_set, double sigma, double Q[6]) {
+  for (int k = 0; k < 6; ++k) Q[k] = q_set ? q_set[k] : 0.0;
+  if (!q_set) Q[0] = Q[3] = Q[5] = sigma * sigma;
+}
+// every landmark inside the gate lies within this distance of the detection: d^2 >= |nu|^2 / lambda_max(S), with
+// lambda_max(S) <= lam_cov_max + lambda_max(Q) in Mahalanobis mode (maha) and S = sigma^2 I otherwise.  The landmark cell
+// grid is built for this radius: a smaller one would let the kernels miss a gated landmark.
+double landmark_gate_radius(bool maha, double lam_cov_max, const double Q[6], double sigma, double gate) {
+  if (!maha) return sigma * std::sqrt(gate);
+  return std::sqrt(gate * (lam_cov_max + sym3_lam_bound(Q)));
+}
+
+// the box of mcl_init_particles_uniform / mcl_inject_uniform against its own rules and, in the map frame, against the
+// map -> odom transform m2o (rows of a 3 x 4): MCL_OK, or the status with *reason saying which rule
+int check_box(const mcl_box* box, const double m2o[12], const char** reason) {
+  const double b[6] = {box->x_min, box->x_max, box->y_min, box->y_max, box->yaw_min, box->yaw_max};
+  *reason = nullptr;
+  for (int c = 0; c < 3 && !*reason; ++c) {
+    if (!std::isfinite(b[2 * c]) || !std::isfinite(b[2 * c + 1])) *reason = "a bound of the box is not finite";
+    else if (b[2 * c + 1] < b[2 * c]) *reason = "a maximum of the box lies below its minimum";
+  }
+  if (!*reason && box->yaw_max - box->yaw_min > 2.0 * 3.14159265358979323846) *reason = "the yaw interval is longer than 2 pi";
+  if (!*reason && box->frame != MCL_FRAME_ODOM && box->frame != MCL_FRAME_MAP) *reason = "unknown frame";
+  if (*reason) return MCL_ERR_INVALID;
+  if (box->frame == MCL_FRAME_MAP &&
+      (std::fabs(m2o[2]) > 1e-12 || std::fabs(m2o[6]) > 1e-12 || std::fabs(m2o[8]) > 1e-12 || std::fabs(m2o[9]) > 1e-12 ||
+       std::fabs(m2o[10] - 1.0) > 1e-12)) {
+    *reason = "a box in the map frame needs an m2o that turns about z alone";
+    return MCL_ERR_UNSUPPORTED;
+  }
+  return MCL_OK;
+}
+
+// beam table of a range update: B directions normalised in fp64, then rounded; out[4 b ...] = unit x, y, z and the
+// measured range (0 without ranges).  A zero or non-finite direction is refused.
+int normalise_beams(const float* dirs, const float* ranges, int B, float* out) {
+  for (int b = 0; b < B; ++b) {
+    const double x = dirs[3 * b], y = dirs[3 * b + 1], z = dirs[3 * b + 2];
+    const double nrm = std::sqrt(x * x + y * y + z * z);
+    if (!(nrm > 0.0) || !std::isfinite(nrm)) return MCL_ERR_INVALID;
+    out[4 * b] = (float)(x / nrm);
+    out[4 * b + 1] = (float)(y / nrm);
+    out[4 * b + 2] = (float)(z / nrm);
+    out[4 * b + 3] = ranges ? ranges[b] : 0.f;
+  }
   return MCL_OK;
 }
 

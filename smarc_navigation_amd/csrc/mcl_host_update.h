@@ -227,7 +227,7 @@ int sort_visiting_order(mcl_handle* h, const MbesArgs& a) {
 bool structured_mesh(const mcl_handle* h) { return h->map_kind == 1 && h->mesh->heights && !h->force_general_mesh; }
 
 // Frames and map of a beam update: st, n, m2o, off_t, off_R, r_max and every map field of an MbesArgs whose other
-// fields the caller has zeroed.  The MBES update (plan_mbes) and the DVL range update (mcl_api.hip: ranges_launch) both
+// fields the caller has zeroed.  The MBES update (plan_mbes) and the DVL range update (mcl_host_ranges.h: ranges_launch) both
 // start from here.
 void fill_frames_and_map(const mcl_handle* h, const double sensor_offset[6], double r_max, MbesArgs& a) {
   static const double zero6[6] = {0, 0, 0, 0, 0, 0};

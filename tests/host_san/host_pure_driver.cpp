@@ -7,6 +7,8 @@
 // (mcl_sweep.h: sweep_side_tin -- the new vertex replaces the end on its side of the plane; which of next_a / next_b is
 // taken follows from that and from one bit of state) from every triangle a random vertical plane cuts to the mesh border.
 // mcl_buffer.h -- the owner of every device and pinned buffer -- over malloc, with an allocator that fails on command.
+// The safety bounds of mcl_host_pure.h (steepest patch gradient of a height grid, landmark gate radius, the box checks of
+// the uniform draws, the range update's beam table): each against what it has to bound, by brute force.
 // Exit code 0 and no sanitizer report = pass; the properties checked here are the ones tests/test_exchange_plan.py and
 // tests/test_dr_golden.py check through the real library.
 #include <cstdio>
@@ -715,6 +717,134 @@ static int check_buffer_owner(std::mt19937_64& rng) {
   return 0;
 }
 
+// ---- the safety bounds of mcl_host_pure.h: each must really bound what a kernel relies on it to bound
+static int check_safety_bounds(std::mt19937_64& rng) {
+  std::uniform_real_distribution<double> U(-1.0, 1.0), U01(0.0, 1.0);
+  // grid_slope_max: a plane (heights that are exact in fp32: its gradient, to a handful of fp64 roundings) ...
+  {
+    const int nx = 8, ny = 8;
+    const double a = 0.375, b = -1.25, res = 0.5;
+    std::vector<float> z((size_t)nx * ny);
+    for (int ix = 0; ix < nx; ++ix)
+      for (int iy = 0; iy < ny; ++iy) z[(size_t)ix * ny + iy] = (float)(a * ix * res + b * iy * res);
+    const double want = std::sqrt(a * a + b * b);
+    CHECK(std::fabs(grid_slope_max(z.data(), nx, ny, res) - want) <= 1e-12 * want);
+  }
+  // ... a random grid: no bilinear patch is anywhere steeper than the bound ...
+  {
+    const int nx = 8, ny = 8;
+    const double res = 0.7;
+    std::vector<float> z((size_t)nx * ny);
+    for (float& v : z) v = (float)(3.0 * U(rng));
+    const double bound = grid_slope_max(z.data(), nx, ny, res);
+    CHECK(bound > 0.0);
+    for (int ix = 0; ix + 1 < nx; ++ix)
+      for (int iy = 0; iy + 1 < ny; ++iy) {
+        const size_t k = (size_t)ix * ny + iy;
+        const double h00 = z[k], h01 = z[k + 1], h10 = z[k + ny], h11 = z[k + ny + 1];
+        for (int su = 0; su < 16; ++su)
+          for (int sv = 0; sv < 16; ++sv) {
+            const double u = (su + 0.5) / 16.0, v = (sv + 0.5) / 16.0;   // z = h00 (1-u)(1-v) + h10 u (1-v) + h01 (1-u) v + h11 u v
+            const double gx = ((h10 - h00) * (1.0 - v) + (h11 - h01) * v) / res, gy = ((h01 - h00) * (1.0 - u) + (h11 - h10) * u) / res;
+            CHECK(std::sqrt(gx * gx + gy * gy) <= bound * (1.0 + 1e-12));
+          }
+      }
+  }
+  // ... and the smallest grids: nothing read outside them (ASan)
+  for (int ny = 2; ny <= 5; ++ny) {
+    std::vector<float> z((size_t)2 * ny);
+    for (float& v : z) v = (float)U(rng);
+    CHECK(std::isfinite(grid_slope_max(z.data(), 2, ny, 1.0)) && std::isfinite(grid_slope_max(z.data(), ny, 2, 1.0)));
+  }
+  // landmark_gate_radius: an innovation on the gate, nu' (P + Q)^-1 nu == gate, is never longer than the radius
+  for (int trial = 0; trial < 200; ++trial) {
+    double S6[2][6];   // P, Q = A A' + eps I (xx xy xz yy yz zz)
+    for (int m = 0; m < 2; ++m) {
+      double A[9];
+      for (double& v : A) v = 2.0 * U(rng);
+      const int ij[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+      for (int e = 0; e < 6; ++e) {
+        S6[m][e] = ij[e][0] == ij[e][1] ? 1e-3 : 0.0;
+        for (int k = 0; k < 3; ++k) S6[m][e] += A[3 * ij[e][0] + k] * A[3 * ij[e][1] + k];
+      }
+      CHECK(sym3_det(S6[m]) > 0.0 && sym3_lam_bound(S6[m]) >= std::max(S6[m][0], std::max(S6[m][3], S6[m][5])));
+    }
+    const double gate = 0.5 + 15.0 * U01(rng), sigma = 0.1 + U01(rng);
+    double Q[6], S[6];
+    landmark_q(S6[1], sigma, Q);
+    for (int e = 0; e < 6; ++e) {
+      CHECK(Q[e] == S6[1][e]);
+      S[e] = S6[0][e] + Q[e];
+    }
+    // x = S^-1 d by the adjugate; nu = d * sqrt(gate / d' S^-1 d)
+    const double d[3] = {U(rng), U(rng), U(rng)}, det = sym3_det(S);
+    const double inv[6] = {(S[3] * S[5] - S[4] * S[4]) / det, (S[2] * S[4] - S[1] * S[5]) / det, (S[1] * S[4] - S[2] * S[3]) / det,
+                           (S[0] * S[5] - S[2] * S[2]) / det, (S[1] * S[2] - S[0] * S[4]) / det, (S[0] * S[3] - S[1] * S[1]) / det};
+    const double x[3] = {inv[0] * d[0] + inv[1] * d[1] + inv[2] * d[2], inv[1] * d[0] + inv[3] * d[1] + inv[4] * d[2],
+                         inv[2] * d[0] + inv[4] * d[1] + inv[5] * d[2]};
+    const double m2 = d[0] * x[0] + d[1] * x[1] + d[2] * x[2];
+    CHECK(m2 > 0.0);
+    const double len = std::sqrt((d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) * gate / m2);
+    CHECK(len <= landmark_gate_radius(true, sym3_lam_bound(S6[0]), Q, sigma, gate));
+    // the isotropic form: sigma sqrt(gate), exactly; Q = sigma^2 I
+    CHECK(landmark_gate_radius(false, 123.0, Q, sigma, gate) == sigma * std::sqrt(gate));
+    landmark_q(nullptr, sigma, Q);
+    CHECK(Q[0] == sigma * sigma && Q[3] == Q[0] && Q[5] == Q[0] && Q[1] == 0.0 && Q[2] == 0.0 && Q[4] == 0.0);
+  }
+  // check_box: every rule, its status and its text
+  {
+    const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const double yawed[12] = {0.6, -0.8, 0, 5, 0.8, 0.6, 0, -3, 0, 0, 1, 2};
+    const double tilted[12] = {1, 0, 0, 0, 0, 0.8, -0.6, 0, 0, 0.6, 0.8, 0};
+    const mcl_box good = {-1.0, 2.0, -3.0, 4.0, -3.0, 3.0, MCL_FRAME_MAP};
+    const char* why = "";
+    CHECK(check_box(&good, eye, &why) == MCL_OK && why == nullptr);
+    CHECK(check_box(&good, yawed, &why) == MCL_OK);
+    struct { mcl_box box; const double* m2o; int rc; const char* text; } bad[] = {
+        {good, eye, MCL_ERR_INVALID, "a bound of the box is not finite"},
+        {good, eye, MCL_ERR_INVALID, "a bound of the box is not finite"},
+        {good, eye, MCL_ERR_INVALID, "a maximum of the box lies below its minimum"},
+        {good, eye, MCL_ERR_INVALID, "the yaw interval is longer than 2 pi"},
+        {good, eye, MCL_ERR_INVALID, "unknown frame"},
+        {good, tilted, MCL_ERR_UNSUPPORTED, "a box in the map frame needs an m2o that turns about z alone"},
+    };
+    bad[0].box.x_max = INFINITY;
+    bad[1].box.yaw_min = NAN;
+    bad[2].box.y_max = -3.5;
+    bad[3].box.yaw_max = 3.3;
+    bad[4].box.frame = 7;
+    for (const auto& c : bad) CHECK(check_box(&c.box, c.m2o, &why) == c.rc && why && std::strcmp(why, c.text) == 0);
+    mcl_box odom = good;
+    odom.frame = MCL_FRAME_ODOM;
+    CHECK(check_box(&odom, tilted, &why) == MCL_OK);   // (the odom frame does not ask m2o)
+  }
+  // normalise_beams: unit to float rounding, the ranges beside them; a zero or non-finite direction is refused
+  {
+    float out[4 * 16];
+    for (int trial = 0; trial < 200; ++trial) {
+      float dirs[3 * 16], ranges[16];
+      const int B = 1 + (int)(rng() % 16);
+      for (int b = 0; b < B; ++b) {
+        const double s = 3.0 / std::sqrt(3.0) * (trial == 0 ? 1.0 : 0.01 + 100.0 * U01(rng));
+        dirs[3 * b] = (float)(s * (trial == 0 ? 1.0 : U(rng)));
+        dirs[3 * b + 1] = (float)(s * (trial == 0 ? -1.0 : U(rng)));
+        dirs[3 * b + 2] = (float)(s * (trial == 0 ? 1.0 : 0.2 + U01(rng)));   // (never the zero vector)
+        ranges[b] = (float)(50.0 * U01(rng));
+      }
+      CHECK(normalise_beams(dirs, ranges, B, out) == MCL_OK);
+      for (int b = 0; b < B; ++b) {
+        const double n2 = (double)out[4 * b] * out[4 * b] + (double)out[4 * b + 1] * out[4 * b + 1] + (double)out[4 * b + 2] * out[4 * b + 2];
+        CHECK(std::fabs(n2 - 1.0) <= 4.0 * 1.1920929e-7 && out[4 * b + 3] == ranges[b]);   // (three components, half an ulp of 1 each, doubled by the square)
+      }
+      CHECK(normalise_beams(dirs, nullptr, B, out) == MCL_OK && out[3] == 0.f);
+    }
+    const float zero[3] = {0.f, 0.f, 0.f}, nan3[3] = {1.f, NAN, 0.f}, inf3[3] = {INFINITY, 0.f, 0.f};
+    CHECK(normalise_beams(zero, nullptr, 1, out) == MCL_ERR_INVALID && normalise_beams(nan3, nullptr, 1, out) == MCL_ERR_INVALID &&
+          normalise_beams(inf3, nullptr, 1, out) == MCL_ERR_INVALID);
+  }
+  return 0;
+}
+
 int main() {
   std::mt19937_64 rng(12345);
   if (check_buffer_owner(rng) != 0) return 1;
@@ -828,6 +958,10 @@ int main() {
     CHECK(!auv_pf_hip::load_map_file("/nonexistent/map.ply", m, err) && !err.empty());
     std::vector<double> lm;
     CHECK(!auv_pf_hip::load_landmark_file("/nonexistent/rocks.yaml", 1e300, lm, err));
+  }
+  {
+    std::mt19937_64 rng_bounds(20261);   // (its own generator: the draws of the checks above stay what they were)
+    if (check_safety_bounds(rng_bounds) != 0) return 1;
   }
   std::puts("host_pure_driver: ok");
   return 0;

@@ -209,3 +209,92 @@ def test_dense_cluster_more_gated_landmarks_than_candidates():
     e.update_landmarks_assign(det, 0.3, k_cand=8, gate=11.345, new_mh_dist=9.0, sensor_offset=off)
     ref = orc.landmark_assign_update_maha(soa, m2o, off, lm, det, 0.3, 8, 11.345, 9.0, lmcov=cov, Q6=Q6)
     np.testing.assert_allclose(e.get_log_weights(), ref, rtol=1e-9, atol=1e-9)
+
+
+def _cache_scene():
+    rs = np.random.RandomState(21)
+    n, n_lm = 130, 50   # 130: not a multiple of the 8 particles per assignment block
+    lm = np.stack([rs.uniform(-10, 10, n_lm), rs.uniform(-10, 10, n_lm), rs.uniform(-6, -4, n_lm)], axis=1)
+    soa = rs.randn(6, n) * np.array([0.5, 0.5, 0.1, 0.01, 0.01, 0.02])[:, None]
+    near = np.argsort(np.sum(lm[:, :2] ** 2, axis=1))[:4]
+    det = lm[near] + 0.1 * rs.randn(4, 3)
+    cov6 = np.zeros((n_lm, 6))
+    for j in range(n_lm):
+        A = rs.randn(3, 3) * np.array([0.4, 0.2, 0.1])
+        S = A.dot(A.T) + 0.01 * np.identity(3)
+        cov6[j] = [S[0, 0], S[0, 1], S[0, 2], S[1, 1], S[1, 2], S[2, 2]]
+    Aq = rs.randn(3, 3) * 0.15
+    Q = Aq.dot(Aq.T) + 0.02 * np.identity(3)
+    return lm, soa, det, cov6, np.array([Q[0, 0], Q[0, 1], Q[0, 2], Q[1, 1], Q[1, 2], Q[2, 2]])
+
+
+def test_both_landmark_updates_share_one_grid_cache():
+    """The cell grid is built for a gate radius and kept until that changes; the k-NN update and the assignment update
+    look it up through the same function.  Alternating them -- another gate, then another noise model -- gives each time
+    the bits of a fresh engine that makes that one call alone, and the oracle's numbers."""
+    from smarc_navigation_amd import engine as eng
+    from oracle import oracle as orc
+    lm, soa, det, cov6, Q6 = _cache_scene()
+    eye, off0, sigma = np.identity(4), [0] * 6, 0.5
+
+    def knn(e):
+        e.update_landmarks(det, sigma, k=2, gate=11.345)
+
+    def assign(gate):
+        return lambda e: e.update_landmarks_assign(det, sigma, k_cand=8, gate=gate, new_mh_dist=9.0)
+
+    iso_knn = lambda: orc.landmark_update(soa, eye, off0, lm, det, sigma, 2, 11.345)
+    maha = dict(lmcov=cov6, Q6=Q6)
+    steps = [   # (the call, the oracle, Mahalanobis noise set)
+        (knn, iso_knn, False),
+        (assign(6.0), lambda: orc.landmark_assign_update(soa, eye, off0, lm, det, sigma, 8, 6.0, 9.0), False),
+        (knn, iso_knn, False),
+        (assign(11.345), lambda: orc.landmark_assign_update_maha(soa, eye, off0, lm, det, sigma, 8, 11.345, 9.0, **maha), True),
+        (knn, lambda: orc.landmark_update_maha(soa, eye, off0, lm, det, sigma, 2, 11.345, **maha), True),
+    ]
+    one = eng.Engine(soa.shape[1], rng_mode=eng.RNG_REPLAY)
+    one.set_particles(soa)
+    one.set_landmarks(lm)
+    noisy = False
+    for k, (call, oracle, want_noise) in enumerate(steps):
+        if want_noise and not noisy:
+            one.set_landmark_noise(cov6, Q6)
+            noisy = True
+        call(one)
+        lw = one.get_log_weights()
+        fresh = eng.Engine(soa.shape[1], rng_mode=eng.RNG_REPLAY)
+        fresh.set_particles(soa)
+        fresh.set_landmarks(lm)
+        if want_noise:
+            fresh.set_landmark_noise(cov6, Q6)
+        call(fresh)
+        lw_fresh = fresh.get_log_weights()
+        fresh.close()
+        ref = oracle()
+        print('step', k, 'max |lw - oracle| =', np.max(np.abs(lw - ref)), 'max |oracle| =', np.max(np.abs(ref)))
+        assert np.array_equal(lw, lw_fresh), k
+        np.testing.assert_allclose(lw, ref, rtol=1e-11, atol=1e-9, err_msg='step %d' % k)
+        assert np.std(ref) > 0.1, k
+    one.close()
+
+
+def test_assignment_update_state_errors_leave_the_filter_untouched():
+    from smarc_navigation_amd import engine as eng
+    lm, soa, det, _, _ = _cache_scene()
+    e = eng.Engine(soa.shape[1], rng_mode=eng.RNG_REPLAY)
+    e.set_particles(soa)
+    with pytest.raises(eng.MclError, match='no feature map') as ei:
+        e.update_landmarks_assign(det, 0.5)
+    assert ei.value.status == -5
+    assert np.array_equal(e.get_particles(), soa)
+    e.set_landmarks(lm)
+    with pytest.raises(eng.MclError, match='nothing to accumulate') as ei:
+        e.update_landmarks_assign(det, 0.5, accumulate=True)
+    assert ei.value.status == -5
+    assert np.array_equal(e.get_particles(), soa)
+    e.update_landmarks_assign(det, 0.5)
+    lw = e.get_log_weights()
+    assert np.all(np.isfinite(lw)) and np.std(lw) > 0.0
+    e.update_landmarks_assign(det, 0.5, accumulate=True)
+    np.testing.assert_allclose(e.get_log_weights(), 2.0 * lw, rtol=1e-14)
+    e.close()

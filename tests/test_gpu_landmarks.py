@@ -169,6 +169,34 @@ def test_fused_landmark_step_argument_and_state_errors():
     assert np.all(np.isfinite(e.last_mean_cov()[0]))
 
 
+def test_group_landmark_step_fails_for_every_shard_before_any_shard_predicts():
+    """mcl_group_step_mbes_landmarks stages every shard -- checks, beam table, landmark grid -- before the first shard
+    predicts: a fault of the second shard leaves the first shard's particles as they were."""
+    from smarc_navigation_amd import engine as eng
+    many = [eng.Engine(256, rank=r, world=2, n_global=512, global_offset=256 * r, seed=1) for r in range(2)]
+    for e in many:
+        e.set_map_grid(np.full((32, 32), -20.0), (-16.0, -16.0), 1.0)
+        e.init_particles()
+    ba = synth.beam_angles(16)
+    r = np.full(16, 20.0, np.float32)
+    od = ([1.0, 0, 0], 0.0, [0, 0, 0, 1.0], -2.0, 0.1)
+    before = [e.get_particles() for e in many]
+    many[0].set_landmarks(np.zeros((4, 3)))
+    with pytest.raises(eng.MclError) as ei:
+        eng.group_step_mbes_landmarks(many, *od, r, ba, 0.2, 100.0, np.zeros((2, 3)), 0.3)
+    # (the text lies with the shard that failed; the wrapper reads the first shard's)
+    from smarc_navigation_amd import _lib
+    assert ei.value.status == -5 and b'no feature map' in _lib.load().mcl_last_error(many[1].h)
+    assert all(np.array_equal(e.get_particles(), b) for e, b in zip(many, before))
+    many[1].set_landmarks(np.zeros((4, 3)))
+    with pytest.raises(eng.MclError, match='bad argument'):
+        eng.group_step_mbes_landmarks(many, *od, r, ba, 0.2, 100.0, np.zeros((2, 3)), 0.3, k=9)
+    assert all(np.array_equal(e.get_particles(), b) for e, b in zip(many, before))
+    eng.group_step_mbes_landmarks(many, *od, r, ba, 0.2, 100.0, np.zeros((2, 3)), 0.3)
+    assert np.all(np.isfinite(many[0].last_mean_cov()[0]))
+    assert not np.array_equal(many[0].get_particles(), before[0])   # (the step did run)
+
+
 @pytest.mark.parametrize('seed', range(10))
 def test_landmark_update_fuzz_against_bruteforce(seed):
     """Random feature maps (1 .. 3 000 landmarks, clustered or spread), gates, 1 .. 40 detections, k = 1 .. 4, isotropic and

@@ -407,6 +407,46 @@ def test_update_after_an_injection_equals_a_fresh_handle_with_the_same_state(eng
     b.close()
 
 
+@pytest.mark.parametrize('last_dt', [0.1, 0.0])
+@pytest.mark.parametrize('how', ['set_particles', 'uniform'])
+def test_fused_step_after_the_state_was_replaced_equals_the_separate_calls(eng, how, last_dt):
+    """A fused step leaves "z, roll, pitch are the odometry's on every particle" behind.  mcl_set_particles and
+    mcl_init_particles_uniform void that: the next fused step -- with a predict, and with dt = 0, where no predict runs and
+    the three components are read from the state -- equals predict + update_mbes + resample on a handle that went the
+    same way, bit for bit.  (It fails if z, roll, pitch are still taken from the odometry after the state was replaced.)"""
+    n, origin = 3001, (-32.0, -32.0)
+    z = synth.bathymetry_grid(64, 64, 1.0, origin, seed=3)
+    ba = synth.beam_angles(16)
+    rs = np.random.RandomState(4)
+    ranges = [(18.0 + rs.rand(16)).astype(np.float32) for _ in range(2)]
+    X = rs.randn(6, n) * np.array([2.0, 2.0, 0.3, 0.05, 0.05, 0.2])[:, None]
+    X[2] -= 3.0   # (depth, roll and pitch that are NOT the odometry's)
+    cov = dict(process_cov=[1e-3, 1e-3, 0, 0, 0, 1e-5], resample_cov=[1e-3, 1e-3, 0, 0, 0, 1e-5], seed=11)
+    od = ([1.0, 0.1, 0.0], 0.02, synth.quat_from_rpy(0.03, -0.02, 0.3), -2.0)
+    a, b = eng.Engine(n, **cov), eng.Engine(n, **cov)
+    for e in (a, b):
+        e.set_map_grid(z, origin, 1.0)
+        e.init_particles()
+        e.step_mbes(*od, 0.1, ranges[0], ba, 0.3, 60.0)
+        if how == 'set_particles':
+            e.set_particles(X)
+        else:
+            e.init_particles_uniform((-8.0, 8.0, -8.0, 8.0), frame='odom', yaw=(-0.5, 0.5))   # (z = roll = pitch = 0)
+    a.step_mbes(*od, last_dt, ranges[1], ba, 0.3, 60.0)
+    b.predict(*od, last_dt)
+    b.update_mbes(ranges[1], ba, 0.3, 60.0)
+    lw_b = b.get_log_weights()
+    b.resample()
+    assert np.std(lw_b) > 0.0
+    assert np.array_equal(a.get_log_weights(), lw_b)
+    assert np.array_equal(a.last_indices(), b.last_indices())
+    assert np.array_equal(a.get_particles(), b.get_particles())
+    if last_dt == 0.0 and how == 'set_particles':   # no predict ran: the resampled particles carry X's own z (plus no noise: its variance is 0)
+        assert np.all(np.isin(a.get_particles()[2], X[2]))
+    a.close()
+    b.close()
+
+
 # ------------------------------------------------------------------ closed loops
 # Scene of both loops: a 192 m x 192 m synthetic bathymetry with relief (swell 2 m, fBm 3 m), 1 m nodes; a 64-beam fan of
 # +-60 degrees, sigma 1.5 m (a tempered likelihood: what a global search over 36 864 m^2 x the full circle needs at

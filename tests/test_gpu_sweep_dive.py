@@ -62,7 +62,7 @@ def _c2z(soa, m2o=None, off=None):
 
 
 def _slope_grid(z, res):
-    """mcl_api.hip, mcl_set_map_grid: a bilinear patch's x slope lies between those of its two x edges, its y slope between
+    """mcl_host_pure.h, grid_slope_max: a bilinear patch's x slope lies between those of its two x edges, its y slope between
     those of its two y edges"""
     h = z.astype(np.float64)
     ax = np.maximum(np.abs(h[1:, :-1] - h[:-1, :-1]), np.abs(h[1:, 1:] - h[:-1, 1:]))
