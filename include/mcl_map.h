@@ -14,7 +14,15 @@
  *   sweeps (an empty node takes the mean of its non-empty 8-neighbours of the previous sweep).
  * Beam geometry, sensor pose and validity rules are those of mcl_update_mbes (mcl.h): beam b looks along
  * (0, sin a_b, -cos a_b) in the sensor frame, sensor pose = m2o * T(xyz) R(rpy) * T_off R_off, ranges
- * <= 0, NaN or >= r_max are skipped.  Conventions as in mcl.h (int status, one owner thread). */
+ * <= 0, NaN or >= r_max are skipped.  Conventions as in mcl.h (int status, one owner thread).
+ * Two roundings are part of the definition (tests/test_gpu_gridmap_edges.py pins both):
+ *   - the beam table is single precision, like the cloud of the reference's laser projector: sin a_b and cos a_b are
+ *     taken in double of the float angle and rounded to float; every later operation is in double;
+ *   - the validity test is made in float: r_max is rounded to the nearest float first and a range is used iff
+ *     0 < r < (float)r_max.  With r_max = 60.0000001 a range of 60.0f is therefore skipped, and an r_max that rounds up
+ *     admits the float below it; +inf is skipped.
+ * The node of a point is floor((x - ox) * (1 / res) + 0.5) (halves round up), taken iff 0 <= i < nx and 0 <= j < ny; a
+ * point outside the grid is still returned in points_out. */
 #ifndef MCL_MAP_H
 #define MCL_MAP_H
 #include "mcl.h"
