@@ -1,4 +1,4 @@
-"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h and mcl_recovery.h).
+"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h and mcl_modes.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -57,6 +57,18 @@ class WStats(C.Structure):
     _fields_ = [('n', C.c_int64), ('n_live', C.c_int64), ('argmax_gid', C.c_int64), ('max_lw', C.c_double),
                 ('sum_w', C.c_double), ('sum_w2', C.c_double), ('n_eff', C.c_double), ('log_mean_lik', C.c_double),
                 ('map_pose', C.c_double * 6)]
+
+
+class ModeGrid(C.Structure):
+    """mcl_mode_grid (include/mcl_modes.h): the lattice over (x, y, yaw), odom frame"""
+    _fields_ = [('x0', C.c_double), ('y0', C.c_double), ('cell', C.c_double), ('nx', C.c_int32), ('ny', C.c_int32),
+                ('n_yaw', C.c_int32), ('reserved', C.c_int32)]
+
+
+class Mode(C.Structure):
+    """mcl_mode (include/mcl_modes.h)"""
+    _fields_ = [('count', C.c_int64), ('score', C.c_int64), ('ix', C.c_int32), ('iy', C.c_int32), ('iyaw', C.c_int32),
+                ('reserved', C.c_int32), ('mean6', C.c_double * 6), ('cov_xy', C.c_double * 3), ('yaw_R', C.c_double)]
 
 
 # every symbol include/mcl.h, mcl_dr.h and mcl_map.h declare: name -> (restype, argtypes)
@@ -151,6 +163,12 @@ RECOVERY_SYMBOLS = {
     'mcl_inject_uniform': (C.c_int, [_vp, _d, C.POINTER(Box), _vp, C.POINTER(C.c_int64)]),
 }
 
+# include/mcl_modes.h: the dominant modes of the cloud (a table of its own, like RECOVERY_SYMBOLS)
+MODES_SYMBOLS = {
+    'mcl_mode_grid_check': (C.c_int, [C.POINTER(ModeGrid), C.POINTER(C.c_int64)]),
+    'mcl_pose_modes': (C.c_int, [_vp, C.POINTER(ModeGrid), _i32, C.POINTER(Mode), C.POINTER(_i32), C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -163,7 +181,7 @@ def load():
         raise ImportError('libmcl_hip.so not built (%s): the MCL hot path has no fallback; run '
                           '__graft_entry__.build()' % SO_PATH)
     lib = C.CDLL(SO_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -29,6 +29,7 @@
 #include "mcl_resample_alt.h"
 #include "mcl_landmarks.h"
 #include "mcl_ranges.h"
+#include "mcl_modes.h"
 
 #define MEAN_RING 4096
 #define RING_STRIDE 20  // doubles per mean/cov result: 16 payload + [16] format tag
@@ -204,6 +205,14 @@ struct mcl_handle {
   double map_xy[4] = {0, 0, 0, 0};  // footprint of the map (x_min, x_max, y_min, y_max; MAP frame), valid while map_kind >= 0
   DevBuf<double> wstats_dev;   // weight statistics: WS_OUT_WORDS result words, then one 32-byte record per tile (lazily)
   DevBuf<u64> inject_cnt;      // injection: the replaced-particle total, then one count per workgroup (lazily)
+  // dominant modes (include/mcl_modes.h; all lazily)
+  bool have_state = false;     // the particles were initialised (either init call, mcl_set_particles)
+  DevBuf<u32> modes_hist;      // H: particles per cell of the caller's lattice
+  DevBuf<u32> modes_score;     // S: the window sums of H, dense
+  DevBuf<u32> modes_cell;      // n: the cell id of every particle (MODES_OUTSIDE: none)
+  DevBuf<u64> modes_rec;       // per-workgroup records: MCL_MAX_GRID outside counts, then MCL_MAX_GRID selection keys
+  DevBuf<double> modes_part;   // per-workgroup moment sums [k][MODES_SUMS][grid]
+  DevBuf<double> modes_res;    // MODES_RES_WORDS: the summed moments, the peaks, the outside count
   bool timing = false;
   std::vector<TimedRegion> regions;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

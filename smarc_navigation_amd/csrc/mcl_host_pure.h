@@ -1,7 +1,7 @@
 // mcl_host_pure.h -- the host arithmetic of libmcl_hip.so that touches no device: tf.transformations' Euler /
 // quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
 // weight statistics, and the safety bounds kernels rely on unchecked (steepest patch gradient of a height grid, landmark
-// gate radius, the box of the uniform draws, the range update's beam table).  No HIP header: the
+// gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -13,6 +13,7 @@
 
 #include "../../include/mcl.h"
 #include "../../include/mcl_recovery.h"
+#include "../../include/mcl_modes.h"
 
 namespace {
 
@@ -247,6 +248,25 @@ int check_box(const mcl_box* box, const double m2o[12], const char** reason) {
     *reason = "a box in the map frame needs an m2o that turns about z alone";
     return MCL_ERR_UNSUPPORTED;
   }
+  return MCL_OK;
+}
+
+// the lattice of mcl_pose_modes against its rules (include/mcl_modes.h): MCL_OK and *n_cells = nx ny n_yaw, or
+// MCL_ERR_INVALID with *reason saying which rule.  The histogram kernels index u32 arrays of n_cells words with the cell
+// ids this admits, unchecked.
+int mode_grid_check_impl(const mcl_mode_grid* g, int64_t* n_cells, const char** reason) {
+  const char* why = nullptr;
+  if (!g) why = "null grid";
+  else if (!std::isfinite(g->cell) || !(g->cell > 0.0)) why = "cell must be finite and > 0";
+  else if (!std::isfinite(g->x0) || !std::isfinite(g->y0)) why = "x0 or y0 is not finite";
+  else if (g->nx < 1 || g->ny < 1 || g->n_yaw < 1) why = "nx, ny and n_yaw must be >= 1";
+  else if (g->n_yaw > MCL_MODES_MAX_YAW) why = "n_yaw > 64";
+  else if ((int64_t)g->nx * (int64_t)g->ny > MCL_MODES_MAX_CELLS ||   // (each factor < 2^31: neither product overflows)
+           (int64_t)g->nx * (int64_t)g->ny * (int64_t)g->n_yaw > MCL_MODES_MAX_CELLS)
+    why = "more than 2^24 cells";
+  if (reason) *reason = why;
+  if (why) return MCL_ERR_INVALID;
+  if (n_cells) *n_cells = (int64_t)g->nx * (int64_t)g->ny * (int64_t)g->n_yaw;
   return MCL_OK;
 }
 

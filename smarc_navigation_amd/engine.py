@@ -51,6 +51,32 @@ class WeightStats(object):
         return 'WeightStats(%r)' % (self.as_dict(),)
 
 
+class PoseMode(object):
+    """mcl_mode as a Python object: count, score, ix, iy, iyaw, mean (6: x, y, z, roll, pitch, circular-mean yaw),
+    cov_xy (xx, xy, yy), yaw_R"""
+
+    def __init__(self, c):
+        self.count, self.score = int(c.count), int(c.score)
+        self.ix, self.iy, self.iyaw = int(c.ix), int(c.iy), int(c.iyaw)
+        self.mean = np.array(c.mean6[:], dtype=np.float64)
+        self.cov_xy = np.array(c.cov_xy[:], dtype=np.float64)
+        self.yaw_R = float(c.yaw_R)
+
+    def as_dict(self):
+        return dict(count=self.count, score=self.score, ix=self.ix, iy=self.iy, iyaw=self.iyaw, mean=self.mean.tolist(),
+                    cov_xy=self.cov_xy.tolist(), yaw_R=self.yaw_R)
+
+    def __repr__(self):
+        return 'PoseMode(%r)' % (self.as_dict(),)
+
+
+def make_mode_grid(x0, y0, cell, nx, ny, n_yaw):
+    g = _lib.ModeGrid()
+    g.x0, g.y0, g.cell = float(x0), float(y0), float(cell)
+    g.nx, g.ny, g.n_yaw, g.reserved = int(nx), int(ny), int(n_yaw), 0
+    return g
+
+
 def make_box(xy, yaw=(-math.pi, math.pi), frame='map'):
     """mcl_box from (x_min, x_max, y_min, y_max), a yaw interval and 'map' / 'odom' (or FRAME_MAP / FRAME_ODOM)"""
     b = _lib.Box()
@@ -90,6 +116,7 @@ class Engine(object):
         cfg.meas_std = float(meas_std)
         m = np.identity(4) if m2o is None else np.asarray(m2o, dtype=np.float64)
         cfg.m2o[:] = [float(x) for x in m.reshape(-1)]
+        self.m2o = m.reshape(4, 4).copy()
         self.n = int(n_particles)
         self.n_global = int(n_global) if n_global else self.n
         self.h = C.c_void_p()
@@ -148,6 +175,41 @@ class Engine(object):
         k = C.c_int64(0)
         self._ck(self.lib.mcl_inject_uniform(self.h, float(fraction), C.byref(b), _ptr(u), C.byref(k) if count else None))
         return int(k.value) if count else None
+
+    # ---- dominant modes of the cloud (include/mcl_modes.h)
+    def mode_grid(self, cell, n_yaw=36, box=None):
+        """the lattice of pose_modes: box = (x_min, x_max, y_min, y_max) in the ODOM frame, or None: the bounding box of the
+        map footprint's four corners carried through the inverse of m2o (the rule of mcl_recovery.h; m2o must turn about z
+        alone); nx = ceil(extent / cell)"""
+        cell = float(cell)
+        if box is None:
+            m = self.m2o
+            if (abs(m[0, 2]) > 1e-12 or abs(m[1, 2]) > 1e-12 or abs(m[2, 0]) > 1e-12 or abs(m[2, 1]) > 1e-12 or
+                    abs(m[2, 2] - 1.0) > 1e-12):
+                raise MclError(-4, 'pose_modes: the map footprint needs an m2o that turns about z alone')
+            x_min, x_max, y_min, y_max = self.map_bounds()
+            xs, ys = [], []
+            for x, y in ((x_min, y_min), (x_min, y_max), (x_max, y_min), (x_max, y_max)):
+                dx, dy = x - m[0, 3], y - m[1, 3]
+                xs.append(m[0, 0] * dx + m[1, 0] * dy)
+                ys.append(m[0, 1] * dx + m[1, 1] * dy)
+            box = (min(xs), max(xs), min(ys), max(ys))
+        x_min, x_max, y_min, y_max = [float(v) for v in box]
+        if not (cell > 0.0 and np.isfinite(cell) and x_max >= x_min and y_max >= y_min):
+            raise MclError(-1, 'pose_modes: bad cell or box')
+        nx = max(1, int(math.ceil((x_max - x_min) / cell)))
+        ny = max(1, int(math.ceil((y_max - y_min) / cell)))
+        return make_mode_grid(x_min, y_min, cell, nx, ny, n_yaw)
+
+    def pose_modes(self, cell, n_yaw=36, k=4, box=None, grid=None):
+        """the up to k densest places of the cloud on a lattice of `cell` metres and n_yaw yaw bins (mcl_pose_modes):
+        returns (list of PoseMode, densest first; n_outside).  grid: a ModeGrid instead of cell / n_yaw / box."""
+        g = grid if grid is not None else self.mode_grid(cell, n_yaw, box)
+        k = int(k)
+        out = (_lib.Mode * max(k, 1))()
+        nm, no = C.c_int32(0), C.c_int64(0)
+        self._ck(self.lib.mcl_pose_modes(self.h, C.byref(g), k, out, C.byref(nm), C.byref(no)))
+        return [PoseMode(out[j]) for j in range(nm.value)], int(no.value)
 
     def predict(self, v, wz, q, z, dt, normals=None, stamp=0.0):
         nz = _f64(normals)

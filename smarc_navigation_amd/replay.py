@@ -293,22 +293,27 @@ def replay_bag(path, params=None, m2o=None, utm2map=None, grid=None, mesh=None, 
 
 def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=1.0, m2o=None, yaw=(-np.pi, np.pi),
                    process_cov=(0.01, 0.01, 0, 0, 0, 1e-4), resample_cov=(0.04, 0.04, 0, 0, 0, 1e-3), alpha_slow=0.001,
-                   alpha_fast=0.1, max_fraction=0.1, inject=True):
+                   alpha_fast=0.1, max_fraction=0.1, inject=True, estimate='mean', mode_cell=1.0, mode_n_yaw=36):
     """Global localisation with kidnap recovery on a recorded stream (--recover): the cloud starts uniform over the map's
     footprint, and every ping runs the separate calls  predict ... -> update_mbes -> weight_stats -> resample ->
     inject_uniform(fraction)  with the fraction of recovery.AugmentedMCL (the likelihood per valid beam, a short-term
-    against a long-term average).  The node class is not involved.  Returns dict(pf_xyz[m,3] mean pose after every ping,
+    against a long-term average).  The node class is not involved.  estimate='mean' publishes mcl_mean_cov's pose;
+    'mode' the heaviest cluster's (mode 0 of mcl_pose_modes on a lattice of mode_cell metres x mode_n_yaw bins over the
+    map's footprint) when there is one, otherwise the mean.  Returns dict(pf_xyz[m,3] published pose after every ping,
     pub_idx, fractions[m], injected[m], log_lik_per_beam[m], n_eff[m], summary)."""
     from . import engine as eng
     from . import recovery
     if 'mbes_idx' not in stream or (grid is None and mesh is None):
         raise ValueError('replay_recover: needs a stream with MBES pings and a map')
+    if estimate not in ('mean', 'mode'):
+        raise ValueError("replay_recover: estimate must be 'mean' or 'mode'")
     e = eng.Engine(int(particles), process_cov=process_cov, resample_cov=resample_cov, m2o=m2o, seed=seed)
     if grid is not None:
         e.set_map_grid(grid['z'], grid['origin'], float(grid['res']))
     else:
         e.set_map_mesh(mesh['verts'], mesh['tris'])
     e.init_particles_uniform(yaw=yaw)
+    lattice = e.mode_grid(mode_cell, mode_n_yaw) if estimate == 'mode' else None
     aug = recovery.AugmentedMCL(alpha_slow, alpha_fast, max_fraction)
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])}
     ang = np.asarray(stream['mbes_angles'], dtype=np.float32)
@@ -332,7 +337,12 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
         out['injected'].append(e.inject_uniform(frac, yaw=yaw) if frac > 0.0 else 0)
         if frac > 0.0:
             aug.injected()
-        out['pf_xyz'].append(e.mean_cov()[0][:3])
+        pose = e.mean_cov()[0][:3]
+        if lattice is not None:
+            modes = e.pose_modes(mode_cell, k=1, grid=lattice)[0]
+            if modes:
+                pose = modes[0].mean[:3]
+        out['pf_xyz'].append(pose)
         out['pub_idx'].append(k)
     e.close()
     for name in out:
@@ -364,6 +374,8 @@ def main(argv=None):
                     help='global localisation with kidnap recovery (replay_recover): uniform start over the map, '
                          'augmented-MCL injection; needs --map-grid and MBES pings in the stream')
     ap.add_argument('--sigma', type=float, default=1.0, help='--recover: MBES range sigma')
+    ap.add_argument('--estimate', choices=('mean', 'mode'), default='mean',
+                    help='--recover: publish the mean pose, or the heaviest cluster of the cloud (mcl_pose_modes)')
     a = ap.parse_args(argv)
     if a.bag:
         grid = dict(np.load(a.map_grid)) if a.map_grid else None
@@ -383,7 +395,8 @@ def main(argv=None):
                                            gps_map=stream.get('gps_map'), pressure_tf=ptf)
     grid = dict(np.load(a.map_grid)) if a.map_grid else None
     if a.recover:
-        res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=a.sigma, m2o=m2o)
+        res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=a.sigma, m2o=m2o,
+                             estimate=a.estimate)
         if a.out:
             np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz'], res['fractions']]), delimiter=',',
                        header='step,x,y,z,injected_fraction')
