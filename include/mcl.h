@@ -44,7 +44,7 @@ enum mcl_resample_scheme {
   MCL_RESAMPLE_RESIDUAL = 1,   /* resampling.py:27-76   -- what auv_pf.py:182 calls */
   MCL_RESAMPLE_STRATIFIED = 2, /* resampling.py:80-114 */
   MCL_RESAMPLE_MULTINOMIAL = 3,/* resampling.py:171-194 */
-  MCL_RESAMPLE_NAIVE = 4       /* resampling.py:116-131 -- systematic positions, `>` instead of `<`; sharded like it */
+  MCL_RESAMPLE_NAIVE = 4       /* resampling.py:116-131 -- systematic positions, first j with pos <= cs_j (systematic: pos < cs_j); sharded like it */
 };
 
 enum mcl_rng_mode {
@@ -238,7 +238,11 @@ int mcl_update_landmarks_assign(mcl_handle* h, const double* det_xyz, int32_t n_
 /* ---- a8-a12 + a2: auv_pf.resample (auv_pf.py:169-198): normalise, resample, keep/lost/dupes
  * reassign, add_noise(resampling_noise_covariance).
  * uniforms: REPLAY: scheme-dependent draws in reference order (systematic: 1); NATIVE: NULL.
- * replay_normals: n x 6 post-resample noise draws (REPLAY) or NULL. */
+ * replay_normals: n x 6 post-resample noise draws (REPLAY) or NULL.
+ * Degenerate log-weights (systematic, naive, stratified, multinomial; residual, a literal restatement of the reference's
+ * fp64 arithmetic, needs weights without NaN): a NaN among finite values is a particle without weight -- it never wins
+ * the maximum and receives no offspring; a vector without any finite value (all -inf, all NaN, or a mix) is resampled
+ * as a cloud of EQUAL weights, never an error. */
 int mcl_resample(mcl_handle* h, const double* uniforms, int64_t n_uniforms, const double* replay_normals);
 /* number of uniforms the next mcl_resample consumes in REPLAY mode: systematic 1, stratified and
  * multinomial n, residual n - sum(floor(n w)) (resampling.py:74; computed here from the weights) */
@@ -289,7 +293,10 @@ int mcl_last_mean_cov(mcl_handle* h, double mean6[6], double* yaw_mean, double c
 int mcl_mean_history(mcl_handle* h, int64_t last_k, double* mean6_out);
 
 /* ---- resampling.py as free functions on the GPU (fixed-point CDF):
- * weights need not be normalised; out: n int32 ancestor indices. */
+ * systematic, naive, stratified, multinomial: weights need not be normalised (the decisions are taken on C_j / T).
+ * MCL_RESAMPLE_RESIDUAL takes the weights as they are, like resampling.py does: they must sum to 1 (copies_i =
+ * floor(n w_i) is meant for that); other weights still give n indices in [0, n), but not residual resampling.
+ * out: n int32 ancestor indices. */
 int mcl_resample_indices(int32_t scheme, const double* weights, int64_t n, const double* uniforms,
                          int64_t n_uniforms, int32_t device, int32_t* out);
 

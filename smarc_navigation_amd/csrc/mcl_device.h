@@ -464,6 +464,13 @@ __device__ __forceinline__ bool shl53_gt_mul(u64 r, u64 U, u64 T) {
   const u64 m_lo = U * T, m_hi = __umul64hi(U, T);
   return l_hi > m_hi || (l_hi == m_hi && (or_equal ? l_lo >= m_lo : l_lo > m_lo));
 }
+// n_j = #{ i in [0, N) : (U + i 2^53) T < C_j N 2^53 }  (naive: <=) from quo = floor(C_j N / T) and its remainder.
+// The positions end at i = N - 1: at C_j = T (quo = N, rem = 0) the ">=" form with U = 0 would count the position
+// i = N as well -- N + 1 offspring for N slots, and a last particle without offspring that is not seen as lost.
+__device__ __forceinline__ u32 offspring_cum(u64 quo, u64 rem, u64 U, u64 T, u64 N) {
+  const u32 c = (u32)quo + (shl53_gt_mul(rem, U, T) ? 1u : 0u);
+  return c < (u32)N ? c : (u32)N;
+}
 
 // ---------------------------------------------------------------- host: who owns device and pinned memory
 // (here because every host file -- the handle, the mesh, the landmark grid, the map builder -- includes this header)

@@ -680,7 +680,8 @@ int launch_gather(mcl_handle* h, const GatherPlan& p, const double* rp) {
 
 // Every resample ends here: the other state buffer is the current one, the weights are spent.
 // via_cdf: the systematic pipeline (offspring CDF + gather); else an explicit ancestor vector (run_resample_alt: single
-// shard, separate calls only -- no exchange mask, no deferred stores, no fused pose records to void)
+// shard, from mcl_resample or from inside a fused step -- whose predict then stores all six components and defers
+// nothing, and whose moments come from run_mean_cov_async: no exchange mask, no deferred stores to void here)
 void finish_resample(mcl_handle* h, bool via_cdf) {
   h->cur ^= 1;
   h->step_resample++;

@@ -262,7 +262,8 @@ __device__ __forceinline__ void tile_scan_blocked(T (&v)[MCL_SCAN_ITEMS], T* sh 
 
 // pass 3: C_j = inclusive scan of q (+ shard offset); offspring CDF
 //   ncum[j] = #{ i in [0,N) : (U + i 2^53) T < C_j N 2^53 } = floor(C_j N / T) + [rem 2^53 > U T]
-// (systematic_resample, resampling.py:154-168, in exact integer arithmetic)
+// (systematic_resample, resampling.py:154-168, in exact integer arithmetic; naive: <= and >=, capped at N --
+// mcl_device.h: offspring_cum)
 struct CdfArgs {
   const u64* totals;   // per-shard totals, `world` entries (device)
   int rank, world;
@@ -293,7 +294,7 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_offspring_cdf(const u64* __restri
       if (base + k < n) {
         u64 quo, rem;
         muldiv_u64(v[k] + off, a.n_global, T, quo, rem);
-        ncum[base + k] = (u32)quo + (shl53_gt_mul(rem, a.u53, T) ? 1u : 0u);
+        ncum[base + k] = offspring_cum(quo, rem, a.u53, T, a.n_global);
       }
     }
     __syncthreads();

@@ -350,7 +350,7 @@ __global__ void __launch_bounds__(RS_BLOCK) k_cdf_expand(ExpandArgs a) {
       if (shard_off != 0ull) {
         u64 quo, rem;
         muldiv_u64(shard_off, a.n_global_u, T, quo, rem);
-        nc_start = (u32)quo + (shl53_gt_mul(rem, a.u53, T) ? 1u : 0u);
+        nc_start = offspring_cum(quo, rem, a.u53, T, a.n_global_u);
       }
     } else {
       // weight before this tile and total weight: every block adds the K1 tile sums up itself
@@ -383,7 +383,7 @@ __global__ void __launch_bounds__(RS_BLOCK) k_cdf_expand(ExpandArgs a) {
       if (base + k < a.n) {
         u64 quo, rem;
         muldiv_u64(v[k] + off, a.n_global_u, T, n_over_t, quo, rem);
-        nc[k] = (u32)quo + (shl53_gt_mul(rem, a.u53, T) ? 1u : 0u);
+        nc[k] = offspring_cum(quo, rem, a.u53, T, a.n_global_u);
         a.ncum[base + k] = nc[k];
       }
     }
@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(RS_BLOCK) k_cdf_expand(ExpandArgs a) {
     if (off != 0ull && w == 0) {   // (only thread 0 looks at it)
       u64 quo, rem;
       muldiv_u64(off, a.n_global_u, T, n_over_t, quo, rem);
-      prev_tile = (u32)quo + (shl53_gt_mul(rem, a.u53, T) ? 1u : 0u);
+      prev_tile = offspring_cum(quo, rem, a.u53, T, a.n_global_u);
     }
   } else {
 #pragma unroll

@@ -4,6 +4,7 @@ The replay driver re-enacts what oracle/ref_harness/gen_golden.py did to the ref
 (odom_callback per sample, update+resample per GPS fix, loc_loop per publish tick) against a
 `backend` object, regenerating the reference's RNG draws from the recorded seed
 (numpy legacy RandomState stream, consumption order SURVEY.md A.1)."""
+import bisect
 import os
 
 import numpy as np
@@ -248,3 +249,80 @@ def live_picks(lw, count, seed=0):
     best = live[np.argsort(lw[live])[-(count // 4):]]
     rest = np.setdiff1d(live, best)
     return np.concatenate([best, np.random.RandomState(seed).choice(rest, count - best.size, replace=False)])
+
+
+# ------------------------------------------------------------------ the resamplers as an exact integer specification
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al. 2011) on uint64 arrays holding 32-bit words"""
+    M = np.uint64(0xffffffff)
+    c0, c1, c2, c3 = [np.asarray(c, dtype=np.uint64) & M for c in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c0
+        p1 = np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M
+        k0 = (k0 + np.uint64(0x9E3779B9)) & M
+        k1 = (k1 + np.uint64(0xBB67AE85)) & M
+    return c0, c1, c2, c3
+
+
+def native_draws_u53(seed, step, count):
+    """The NATIVE uniforms of the explicit-index schemes (mcl_resample_alt.h: k_make_u53), as Python ints:
+    U_i = ((x >> 5) << 26) | (y >> 6) of philox4x32(i, 0, step, 4; seed_lo, seed_hi), i = 0 .. count - 1."""
+    x, y, _, _ = philox4x32_10(np.arange(int(count), dtype=np.uint64), 0, int(step), 4, seed & 0xffffffff, seed >> 32)
+    return [int(v) for v in ((x >> np.uint64(5)) << np.uint64(26)) | (y >> np.uint64(6))]
+
+
+def u53_of(u):
+    """U = floor(u 2^53) of doubles in [0, 1), as Python ints (exact: u 2^53 is a power-of-two scaling)"""
+    return [int(v * 9007199254740992.0) for v in np.atleast_1d(np.asarray(u, dtype=np.float64))]
+
+
+EXACT_SCHEMES = ('systematic', 'naive', 'stratified', 'multinomial')
+
+
+def exact_resample(q, U, scheme):
+    """Ancestor indices of the four CDF schemes in plain Python integers (mcl_device.h: shl53_gt_mul,
+    mcl_resample_alt.h).  q: the fixed-point weights (oracle.fixed_weights); U: 53-bit uniforms as ints -- one for
+    systematic / naive, n for stratified / multinomial.  With C_j the inclusive sum of q, T = C_{n-1}, N = n:
+
+        systematic   idx_i = min{ j : (U   + i 2^53) T <  C_j N 2^53 }
+        naive        idx_i = min{ j : (U   + i 2^53) T <= C_j N 2^53 }
+        stratified   idx_i = min{ j : (U_i + i 2^53) T <  C_j N 2^53 }
+        multinomial  idx_i = min{ j : C_j 2^53 >= U_i T }
+
+    and n - 1 where no j qualifies.  With T > 0 that never happens (the right-hand side at j = n - 1 is N T 2^53,
+    above every left-hand side).  T = 0 (no weight at all; only linear weights that are all zero can give it) makes
+    every product 0: the strict comparisons hold for no j -- index n - 1 everywhere --, the non-strict ones for j = 0
+    -- index 0 everywhere.  The right-hand sides are non-decreasing in j, so min{j} is a bisection."""
+    rhs, lhs, strict = _exact_sides(q, U, scheme)
+    n = len(rhs)
+    find = bisect.bisect_right if strict else bisect.bisect_left   # first j with rhs_j > lhs / rhs_j >= lhs
+    return np.array([min(find(rhs, v), n - 1) for v in lhs], dtype=np.int32)
+
+
+def exact_ties(q, U, scheme):
+    """how many of the n positions sit exactly ON a CDF edge (left-hand side == a right-hand side of exact_resample):
+    the decisions a `<` / `<=` mix-up would change"""
+    rhs, lhs, _ = _exact_sides(q, U, scheme)
+    return sum(1 for v in lhs if bisect.bisect_left(rhs, v) != bisect.bisect_right(rhs, v))
+
+
+def _exact_sides(q, U, scheme):
+    q = [int(v) for v in q]
+    n = len(q)
+    C, acc = [], 0
+    for v in q:
+        acc += v
+        C.append(acc)
+    T = C[-1]
+    if scheme == 'multinomial':
+        assert len(U) >= n
+        return [c << 53 for c in C], [int(U[i]) * T for i in range(n)], False
+    rhs = [(c * n) << 53 for c in C]
+    if scheme == 'stratified':
+        assert len(U) >= n
+        return rhs, [(int(U[i]) + (i << 53)) * T for i in range(n)], True
+    if scheme in ('systematic', 'naive'):
+        return rhs, [(int(U[0]) + (i << 53)) * T for i in range(n)], scheme == 'systematic'
+    raise ValueError(scheme)

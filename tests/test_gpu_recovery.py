@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from smarc_navigation_amd import synth
+from tests.helpers import philox4x32_10
 
 pytestmark = pytest.mark.gpu
 
@@ -25,20 +26,6 @@ def eng():
 
 
 # ------------------------------------------------------------------ numpy restatement of the draws
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 (Salmon et al. 2011) on uint64 arrays holding 32-bit words"""
-    M = np.uint64(0xffffffff)
-    c0, c1, c2, c3 = [np.asarray(c, dtype=np.uint64) & M for c in np.broadcast_arrays(c0, c1, c2, c3)]
-    k0, k1 = np.uint64(k0), np.uint64(k1)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M
-    return c0, c1, c2, c3
-
-
 def u53(hi, lo):
     """include/mcl_recovery.h: U(hi, lo) = (((hi >> 5) << 26) | (lo >> 6)) 2^-53"""
     return (((hi >> np.uint64(5)) << np.uint64(26)) | (lo >> np.uint64(6))).astype(np.float64) * 2.0 ** -53
