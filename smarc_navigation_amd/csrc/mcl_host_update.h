@@ -511,6 +511,8 @@ void launch_sweep(mcl_handle* h, const MbesPlan& p, const SweepGrid& g, const Mb
     t_begin(h, MCL_K_MBES_MAIN);
     if (p.nsub > 1)
       k_mbes_sweep<SURF, false, true><<<g.sgrid, g.sthreads, g.lds, h->stream>>>(a);
+    else if ((SURF == 2 || SURF == 3) && a.sweep_work)   // MCL_DEBUG_WORK: the same code, counting its walk steps (mcl_sweep.h: WORK)
+      k_mbes_sweep_work<(SURF == 3 ? 3 : 2)><<<g.sgrid, SWEEP_THREADS, g.lds, h->stream>>>(a);
     else
       k_mbes_sweep<SURF, false><<<g.sgrid, SWEEP_THREADS, g.lds, h->stream>>>(a);
     t_end(h);
@@ -583,8 +585,18 @@ void debug_sweep_handovers(mcl_handle* h, const MbesArgs& a) {
   int cnt = 0;
   (void)hipMemcpyAsync(&cnt, a.defer_count, sizeof(int), hipMemcpyDeviceToHost, h->stream);
   (void)hipStreamSynchronize(h->stream);
-  fprintf(stderr, "[mbes] sweep handed over %d of %lld particles (clamp to r_max %s)\n", cnt, (long long)h->n,
-          a.sweep_noclamp ? "proved idle: skipped" : "kept");
+  // ... and how much of the lattice walk its waves took with the triple in scalar registers (mcl_sweep.h: the shared walk)
+  unsigned long long shared = 0, steps = 0;
+  if (a.sweep_work) {
+    unsigned long long w[64];
+    (void)hipMemcpy(w, a.sweep_work, sizeof w, hipMemcpyDeviceToHost);
+    for (int k = 0; k < 64; ++k) {
+      shared += w[k] >> 32;
+      steps += w[k] & 0xffffffffull;
+    }
+  }
+  fprintf(stderr, "[mbes] sweep handed over %d of %lld particles (clamp to r_max %s); wave walk steps shared %llu of %llu\n", cnt,
+          (long long)h->n, a.sweep_noclamp ? "proved idle: skipped" : "kept", shared, steps);
 #ifdef SWEEP_REASONS
   // why (mcl_sweep.h: SWEEP_FAIL / SWEEP_NOTE codes, per particle SIDE): -DSWEEP_REASONS builds only
   unsigned why[16];
@@ -601,6 +613,14 @@ void debug_sweep_handovers(mcl_handle* h, const MbesArgs& a) {
 // general kernel through the hand-over list.
 int run_sweep(mcl_handle* h, const MbesPlan& p, MbesArgs& a, const MbesCounters& wh) {
   a.sweep_noclamp = sweep_noclamp(h, p) ? 1 : 0;
+  a.sweep_uniform = h->env_sweep_uniform == 1 ? 1 : 0;   // (off unless asked for: measured slower than the per-lane loop)
+  a.sweep_step_cap = h->env_sweep_step_cap;
+  a.sweep_work = nullptr;
+  if (h->env_debug_work) {
+    RESERVE(h, h->sweep_work_dev, 64);
+    HIPCHK(h, hipMemsetAsync(h->sweep_work_dev, 0, 64 * sizeof(unsigned long long), h->stream));
+    a.sweep_work = h->sweep_work_dev;
+  }
   SweepGrid g;
   g.sthreads = p.nsub == 4 ? 512 : SWEEP_THREADS;
   const int per_block = g.sthreads / 64 / (2 * p.nsub) * 64;

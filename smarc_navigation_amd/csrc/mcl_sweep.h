@@ -245,7 +245,7 @@ __device__ __forceinline__ bool sweep_border_final(const MbesArgs& a, float h, f
   return (side == 1u || side == 2u) & (lhs < rhs * fabsf(side == 1u ? c1x : c1y));
 }
 
-template <int SURF, bool EXPECT_ONLY, bool SUB = false>
+template <int SURF, bool EXPECT_ONLY, bool SUB = false, bool WORK = false>
 __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P, const float4* __restrict__ sbeam,
                                            const float* __restrict__ stail, int side, int sub, int nsub,
                                            float* __restrict__ exp_row, float& acc_out) {
@@ -336,7 +336,8 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
   const float nx_ = P.c1[1] * P.c2[2] - P.c1[2] * P.c2[1], ny_ = P.c1[2] * P.c2[0] - P.c1[0] * P.c2[2],
               nz_ = P.c1[0] * P.c2[1] - P.c1[1] * P.c2[0];
   const float pu = nx_ * res, pv = ny_ * res, pz = nz_, p0 = -(pu * ul + pv * vl + pz * oz);
-  const float su = sg * P.c1[0] * res, sv = sg * P.c1[1] * res, sz = sg * P.c1[2], s0 = -(su * ul + sv * vl + sz * oz);
+  const float su = sg * P.c1[0] * res, sv = sg * P.c1[1] * res, sz = sg * P.c1[2];
+  float s0 = -(su * ul + sv * vl + sz * oz);   // (the shared walk turns it into a NaN on a lane whose walk is over)
   const float tu = -P.c2[0] * res, tv = -P.c2[1] * res, tz = -c2z, t0 = -(tu * ul + tv * vl + tz * oz);
   auto node = [&](int Pk) {
     SweepNode N;
@@ -397,7 +398,8 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
   // ---- walk outward, merging the beam table against the polyline
   float acc = 0.f;
   bool ok = true;
-  const int max_steps = (int)(3.f * (s_stop + 4.f * res) * inv_res) + 16;
+  int max_steps = (int)(3.f * (s_stop + 4.f * res) * inv_res) + 16;
+  if (a.sweep_step_cap) max_steps = min(max_steps, a.sweep_step_cap);   // (MCL_SWEEP_STEP_CAP, tests: no sane walk reaches the limit itself)
   // the next beam to resolve stays in registers across segments (a vertex it passes beyond costs no LDS read), the one
   // after it is already on its way from LDS: the table is walked by pointer, one add per beam
   // (record b carries the tangent of the NEXT beam of its side in .x: the decision to leave the merge loop never waits
@@ -421,6 +423,37 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     bm.z = r.z;
     bm.w = r.w;
   }
+  // the beams of the segment (sp, tp) -> (sc, tc): dts, dss, num its constants (seg_tau)
+  const auto merge_segment = [&](float sp, float tp, float sc, float tc, float dts, float dss, float num) {
+    // (no end-of-table test: the record beyond the last beam has tan a = +inf and tc > 0, so e_cur = -inf.  The
+    //  loop is rotated: e_cur of the NEXT beam is formed at the end of the body, one compare decides)
+    float e_cur = fmaf(-tcur, tc, sc);
+    if (!EXPECT_ONLY && !SUB && !SWEEP_MERGE_CXX) {
+      sweep_merge_asm(msel, acc, bp, dss, num, tp, sc, tc, dts);   // (msel = side + 2 noclamp: wave-uniform)
+    } else {
+      // one beam on the segment (prev -> cur): the crossing of the half line s = t tan a with the chord (e changes
+      // sign: <= 0 at prev, >= 0 at cur); then on to the next beam of the table
+      while (e_cur >= 0.f && (!SUB || bp != bp_end)) {   // until the pending beam passes beyond this vertex
+        const float tau = seg_tau(num, fmaf(-tcur, dts, dss), tp, tc);
+        // range = t / cos a, beyond r_max (or NaN): r_max.  The table carries the residual's constants
+        // (mcl_host_update.h: upload_sweep_beams): (range_b - r) w = max(z w - t (w / cos a), (z - r_max) w)
+        if (EXPECT_ONLY) {
+          exp_row[(int)(bp - sb_off) >> 4] = fminf(tau * bm.y, a.r_max);
+        } else {
+          const float dd = hw_max(fmaf(-tau, bm.y, bm.z), bm.w);
+          acc = fmaf(dd, dd, acc);
+        }
+        tcur = bm.x;
+        bp += pstep16;
+        const float4 r = sbeam[(int)(bp - sb_off) >> 4];
+        bm.x = r.x;
+        bm.y = r.y;
+        bm.z = r.z;
+        bm.w = r.w;
+        e_cur = fmaf(-tcur, tc, sc);
+      }
+    }
+  };
   // one step of the walk: resolve the beams of the segment (sp, tp) -> (sc, tc), then cross into the next triangle.
   // Returns true when the walk is over (all beams resolved, stop distance, map border, failure).
   // (EXITS: the three tests that end a walk normally are made every SECOND step -- a step too many finds its beams
@@ -435,36 +468,7 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     const float hN = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, __mul24(ni, ny4) + ((nj << 2) + g0b), 0, 0));
     const float dts = tc - tp;
     const float dss = sc - sp, num = fmaf(tp, dss, -(sp * dts));   // (the segment's constants of seg_tau)
-    {
-      // (no end-of-table test: the record beyond the last beam has tan a = +inf and tc > 0, so e_cur = -inf.  The
-      //  loop is rotated: e_cur of the NEXT beam is formed at the end of the body, one compare decides)
-      float e_cur = fmaf(-tcur, tc, sc);
-      if (!EXPECT_ONLY && !SUB && !SWEEP_MERGE_CXX) {
-        sweep_merge_asm(msel, acc, bp, dss, num, tp, sc, tc, dts);   // (msel = side + 2 noclamp: wave-uniform)
-      } else {
-        // one beam on the segment (prev -> cur): the crossing of the half line s = t tan a with the chord (e changes
-        // sign: <= 0 at prev, >= 0 at cur); then on to the next beam of the table
-        while (e_cur >= 0.f && (!SUB || bp != bp_end)) {   // until the pending beam passes beyond this vertex
-          const float tau = seg_tau(num, fmaf(-tcur, dts, dss), tp, tc);
-          // range = t / cos a, beyond r_max (or NaN): r_max.  The table carries the residual's constants
-          // (mcl_host_update.h: upload_sweep_beams): (range_b - r) w = max(z w - t (w / cos a), (z - r_max) w)
-          if (EXPECT_ONLY) {
-            exp_row[(int)(bp - sb_off) >> 4] = fminf(tau * bm.y, a.r_max);
-          } else {
-            const float dd = hw_max(fmaf(-tau, bm.y, bm.z), bm.w);
-            acc = fmaf(dd, dd, acc);
-          }
-          tcur = bm.x;
-          bp += pstep16;
-          const float4 r = sbeam[(int)(bp - sb_off) >> 4];
-          bm.x = r.x;
-          bm.y = r.y;
-          bm.z = r.z;
-          bm.w = r.w;
-          e_cur = fmaf(-tcur, tc, sc);
-        }
-      }
-    }
+    merge_segment(sp, tp, sc, tc, dts, dss, num);
     if (decltype(EXITS)::value) {
       if (bp == bp_end) return true;
       if (sc > s_stop) return true;  // every beam left misses inside r_max (tail below)
@@ -505,9 +509,137 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     }
     return false;
   };
-  for (int step = 1;; step += 2) {
-    if (walk_step(s_prev, t_prev, s_cur, t_cur, step, std::true_type())) break;
-    if (walk_step(s_cur, t_cur, s_prev, t_prev, step + 1, std::false_type())) break;
+  // the per-lane loop, unrolled by two with the roles of (previous, current) swapped.  It can be entered at either parity:
+  // `mid` (wave-uniform: a scalar branch per iteration) skips the first half once -- ONE loop; two of them, one per parity,
+  // cost the kernel its register budget (the compiler keeps the state of either alive through the other).
+  // Returns the step a lane left at (WORK, the kernel that counts for MCL_DEBUG_WORK: read outside the loop the wave's
+  // count becomes every lane's own, a move per iteration).
+  const auto lane_walk = [&](int step, bool mid) -> int {
+    for (;; step += 2) {
+      if (!mid && walk_step(s_prev, t_prev, s_cur, t_cur, step, std::true_type())) break;
+      mid = false;
+      if (walk_step(s_cur, t_cur, s_prev, t_prev, step + 1, std::false_type())) return WORK ? step + 1 : 0;
+    }
+    return WORK ? step : 0;
+  };
+  if (!EXPECT_ONLY && !SUB) {
+    // ---- the shared walk.  A wave holds 64 spatial neighbours: on a converged cloud its lanes cross the same lattice
+    // edges in the same order and differ only in their plane coefficients -- which node comes next, where its height
+    // lies, the height itself are the same in all of them.  While that holds the triple (A, Bn, C) lives in scalar
+    // registers: the integer chain of a step (next node, unpack, byte offset, the selects on packed ids) is scalar
+    // arithmetic and costs no vector issue slot.  Every floating-point operation is walk_step's, on the same operands in
+    // the same order: which loop a lane walks in changes no bit of its result.
+    // Gate, once per wave: the lanes still here (a declined particle, an empty slot do not vote) stand in the same cell
+    // on the same triangle.  Only under MCL_SWEEP_UNIFORM=1 (a.sweep_uniform): measured on the MI355X the shared step is
+    // SLOWER than the per-lane one -- 31 vector instructions against 40, but three times the scalar ones, and one scalar
+    // unit serves the four SIMDs of a CU -- so by default every wave takes the per-lane loop.
+    int uA = __builtin_amdgcn_readfirstlane(A.P), uB = __builtin_amdgcn_readfirstlane(Bn.P), uC = __builtin_amdgcn_readfirstlane(C);
+    const int ug0b = __builtin_amdgcn_readfirstlane(g0b);
+    const bool same = (A.P == uA) & (Bn.P == uB) & (C == uC) & (g0b == ug0b);
+    const bool gate = a.sweep_uniform && __builtin_amdgcn_ballot_w64(same) == __builtin_amdgcn_ballot_w64(true);
+    // The loop itself leaves no lane behind: every branch in it is the wave's (the compiler keeps a value in scalar
+    // registers only where no lane's way through the loop can differ).  A lane whose walk is over (`fin`) stays and is
+    // made harmless instead: its s0 and its current vertex become NaN, so every vertex it forms from then on is one, the
+    // merge statement finds no beam on its segments (e_cur is a NaN) and acc and bp stay what they were; it does not vote
+    // and its verdict `ok` is closed.
+    // (fin and ok of the lanes as wave masks in scalar registers: updating them is scalar work too)
+    unsigned long long fin_m = 0ull, ok_m = ~0ull;
+    // one shared step; true (wave-uniform): the lanes part -- the step is complete, the triple written out per lane, the
+    // walk goes on in the per-lane loop.  (No way back: a wave parts once.)
+    const auto shared_step = [&](float& sp, float& tp, float& sc, float& tc, const int step, auto EXITS) -> bool {
+      const int Nk = (int)((unsigned)uA + (unsigned)uB - (unsigned)uC);
+      const int nj = (int)(short)Nk, ni = (Nk - nj) >> 16;
+      // (the offset goes through the load's range-checked vector operand like walk_step's -- one move --: the buffer's
+      //  range check is what ends a NaN-driven walk, and the scalar offset operand is outside it)
+      const float hN = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, ni * ny4 + ((nj << 2) + ug0b), 0, 0));
+      const float dts = tc - tp;
+      const float dss = sc - sp, num = fmaf(tp, dss, -(sp * dts));
+      merge_segment(sp, tp, sc, tc, dts, dss, num);
+      unsigned long long out_m = fin_m, over_m = 0ull;   // over before this step, or by its exit tests (walk_step's, in its order)
+      if (decltype(EXITS)::value) {
+        out_m |= __builtin_amdgcn_ballot_w64(bp == bp_end) | __builtin_amdgcn_ballot_w64(sc > s_stop);
+        over_m = __builtin_amdgcn_ballot_w64(step > max_steps) & ~out_m;   // (the step limit)
+#ifdef SWEEP_REASONS
+        if (__builtin_amdgcn_inverse_ballot_w64(over_m)) SWEEP_NOTE(11);
+#endif
+        out_m |= over_m;
+      }
+      const int uA_was = uA;
+      const float fi = (float)ni, fj = (float)nj;
+      const float dN = fmaf(pu, fi, fmaf(pv, fj, fmaf(pz, hN, p0)));
+      // which node stays is still each lane's own verdict; the wave follows it on the scalar side while it is unanimous
+      const bool keep_a = (__float_as_int(dN) ^ __float_as_int(A.d)) < 0;
+      const unsigned long long kb = __builtin_amdgcn_ballot_w64(keep_a) & ~out_m;
+      const bool part = kb != 0ull && kb != (__builtin_amdgcn_ballot_w64(true) & ~out_m);
+      // (the three selects on d, s and t stay per lane -- as moves under the wave's verdict they cost the same and the
+      //  compiler copies the registers around them; a lane that is out may vote otherwise: nothing reads what it keeps)
+      Bn.d = keep_a ? A.d : Bn.d;
+      Bn.s = keep_a ? A.s : Bn.s;
+      Bn.t = keep_a ? A.t : Bn.t;
+      if (part) {
+        C = keep_a ? uB : uA;
+        Bn.P = keep_a ? uA : uB;
+        A.P = Nk;
+      } else {
+        uC = kb != 0ull ? uB : uA;
+        uB = kb != 0ull ? uA : uB;
+      }
+      uA = Nk;
+      A.d = dN;
+      A.s = fmaf(su, fi, fmaf(sv, fj, fmaf(sz, hN, s0)));
+      A.t = fmaf(tu, fi, fmaf(tv, fj, fmaf(tz, hN, t0)));
+      const float lam = A.d * fast_rcp(A.d - Bn.d);
+      const float s_new = fmaf(lam, Bn.s - A.s, A.s), t_new = fmaf(lam, Bn.t - A.t, A.t);
+      sp = s_new;
+      tp = t_new;
+      // (t_new <= 0: the horizon; a NaN: the height was one, the map border -- decided after the loop)
+      const unsigned long long up_m = __builtin_amdgcn_ballot_w64(!(t_new > 0.f));
+      ok_m &= ~over_m & (out_m | ~up_m);   // (the step limit closes a verdict like walk_step's ok = false)
+      const unsigned long long now_m = (out_m | up_m) & ~fin_m;
+      if (now_m) {
+        // these lanes' walks end with this step: the node they found last (at the step limit the one before: it has a
+        // height, and the test after the loop hands the particle over as the per-lane loop does), and the NaNs.
+        // (selects under the wave's branch: with no lane's branch in it the loop's control flow is all scalar)
+        const bool now = __builtin_amdgcn_inverse_ballot_w64(now_m);
+        const int last = decltype(EXITS)::value && __builtin_amdgcn_inverse_ballot_w64(over_m) ? uA_was : Nk;
+        A.P = now ? last : A.P;
+        sp = now ? __builtin_nanf("") : sp;
+        s0 = now ? __builtin_nanf("") : s0;
+        fin_m |= now_m;
+      }
+      return part;
+    };
+    // how the wave leaves the shared loop: 1 / 3 every walk is over, 2 parted in an odd step, 4 in an even one (or the
+    // wave never shared: step -1)
+    int how = 4, step = -1;
+    if (gate) {
+      for (step = 1;; step += 2) {
+        how = 2;
+        if (shared_step(s_prev, t_prev, s_cur, t_cur, step, std::true_type())) break;
+        how = 1;
+        if ((__builtin_amdgcn_ballot_w64(true) & ~fin_m) == 0ull) break;
+        how = 4;
+        if (shared_step(s_cur, t_cur, s_prev, t_prev, step + 1, std::false_type())) break;
+        how = 3;
+        if ((__builtin_amdgcn_ballot_w64(true) & ~fin_m) == 0ull) break;
+      }
+    }
+    const int n_shared = gate ? step + (how > 2 ? 1 : 0) : 0;
+    const bool fin = __builtin_amdgcn_inverse_ballot_w64(fin_m);
+    ok = __builtin_amdgcn_inverse_ballot_w64(ok_m);
+    int n_steps = n_shared;
+    if ((how & 1) == 0 && !fin) n_steps = lane_walk(how == 2 ? step : step + 2, how == 2);
+    if (WORK && a.sweep_work) {
+      // MCL_DEBUG_WORK: (steps walked shared, steps walked) of this wave, one atomic per wave over 64 words
+      const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
+      int wn = n_shared;
+      for (unsigned long long m = act; m; m &= m - 1ull) wn = max(wn, __builtin_amdgcn_readlane(n_steps, (int)__builtin_ctzll(m)));
+      const unsigned wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+      if ((int)(threadIdx.x & 63) == (int)__builtin_ctzll(act))
+        atomicAdd(&a.sweep_work[wave & 63u], ((unsigned long long)n_shared << 32) | (unsigned long long)wn);
+    }
+  } else {
+    lane_walk(1, false);
   }
   if (!ok) {
     // a NaN height: the slice ends at the map border -- final if it cannot come back (the beams left get r_max through
@@ -1339,7 +1471,7 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
 
 // one (particle, side, run): cast; the (+ side, run 0) lane then combines the verdicts and sums in a fixed order, writes
 // lw or hands the particle over.  j0: the workgroup's first particle.
-template <int SURF, bool EXPECT_ONLY, bool SUB>
+template <int SURF, bool EXPECT_ONLY, bool SUB, bool WORK>
 __device__ __forceinline__ double sweep_lane(const MbesArgs& a, long long j0, long long n, const float4* sbeam,
                                              const float* stail, float* xacc, int* xok) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (wave-uniform: scalar registers)
@@ -1366,7 +1498,7 @@ __device__ __forceinline__ double sweep_lane(const MbesArgs& a, long long j0, lo
     else if (SURF == 0)
       ok = sweep_side_grid<EXPECT_ONLY, SUB>(a, P, sside, stail, side, sub, nsub, exp_row, acc);
     else
-      ok = sweep_side<(SURF == 3 ? 3 : 2), EXPECT_ONLY, SUB>(a, P, sside, stail, side, sub, nsub, exp_row, acc);
+      ok = sweep_side<(SURF == 3 ? 3 : 2), EXPECT_ONLY, SUB, WORK>(a, P, sside, stail, side, sub, nsub, exp_row, acc);
   }
   // the lanes of a particle agree on its fate: every lane but the first leaves its verdict and sum in LDS
   if (combo) {
@@ -1409,8 +1541,9 @@ __device__ __forceinline__ double sweep_lane(const MbesArgs& a, long long j0, lo
 // record in front of either side; B tail sums and the 4 tangents)
 inline size_t sweep_lds_bytes(int B) { return (size_t)(B + 7) * sizeof(float4) + (size_t)(B + 4) * sizeof(float); }
 
-template <int SURF, bool EXPECT_ONLY, bool SUB = false>
-__global__ void __launch_bounds__(SUB ? 64 * SWEEP_MAX_WAVES : SWEEP_THREADS, SURF == 0 ? (SUB ? SWEEP_MIN_WAVES_GRID - 1 : SWEEP_MIN_WAVES_GRID) : (SURF == 6 && !SUB && !EXPECT_ONLY ? 8 : (SURF == 5 || SURF == 6 ? SWEEP_MIN_WAVES_TIN : SWEEP_MIN_WAVES))) k_mbes_sweep(MbesArgs a) {
+// the body of the sweep kernels (WORK: the one that counts walk steps for MCL_DEBUG_WORK, k_mbes_sweep_work below)
+template <int SURF, bool EXPECT_ONLY, bool SUB, bool WORK>
+__device__ __forceinline__ void sweep_kernel(const MbesArgs& a) {
 #ifdef SWEEP_TIMELINE
   const unsigned long long tl0 = wall_clock64(), tc0 = __builtin_readcyclecounter();
 #endif
@@ -1435,7 +1568,7 @@ __global__ void __launch_bounds__(SUB ? 64 * SWEEP_MAX_WAVES : SWEEP_THREADS, SU
   // particles per workgroup: its waves divided by the (side, run) combinations of a particle; one lane per
   // (particle, side, run)
   const int per_block = (int)(blockDim.x >> 6) / (2 * (SUB ? a.sweep_nsub : 1)) * 64;
-  const double vmax = sweep_lane<SURF, EXPECT_ONLY, SUB>(a, blockIdx.x * (long long)per_block, a.n, sbeam, stail, xacc, xok);
+  const double vmax = sweep_lane<SURF, EXPECT_ONLY, SUB, WORK>(a, blockIdx.x * (long long)per_block, a.n, sbeam, stail, xacc, xok);
   if (!EXPECT_ONLY && a.max_slots) {
     // the normalisation needs max lw: one atomic per wave that wrote log-likelihoods, on an order-preserving key
     const double m = wave_max(vmax);
@@ -1456,4 +1589,16 @@ __global__ void __launch_bounds__(SUB ? 64 * SWEEP_MAX_WAVES : SWEEP_THREADS, SU
     }
   }
 #endif
+}
+
+template <int SURF, bool EXPECT_ONLY, bool SUB = false>
+__global__ void __launch_bounds__(SUB ? 64 * SWEEP_MAX_WAVES : SWEEP_THREADS, SURF == 0 ? (SUB ? SWEEP_MIN_WAVES_GRID - 1 : SWEEP_MIN_WAVES_GRID) : (SURF == 6 && !SUB && !EXPECT_ONLY ? 8 : (SURF == 5 || SURF == 6 ? SWEEP_MIN_WAVES_TIN : SWEEP_MIN_WAVES))) k_mbes_sweep(MbesArgs a) {
+  sweep_kernel<SURF, EXPECT_ONLY, SUB, false>(a);
+}
+// MCL_DEBUG_WORK: k_mbes_sweep<SURF, false> over a lattice (SURF 2 / 3) with the step counts of its waves (sweep_side: WORK).
+// A kernel of its own: read after the loop the wave's step count becomes every lane's (a move per iteration of the
+// per-lane loop and nine more scalar registers), which the main kernel should not carry for a diagnostic.  Same budget.
+template <int SURF>
+__global__ void __launch_bounds__(SWEEP_THREADS, SWEEP_MIN_WAVES) k_mbes_sweep_work(MbesArgs a) {
+  sweep_kernel<SURF, false, false, true>(a);
 }
