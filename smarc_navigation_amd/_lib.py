@@ -1,4 +1,5 @@
-"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h and mcl_modes.h).
+"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h and
+mcl_history.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -69,6 +70,12 @@ class Mode(C.Structure):
     """mcl_mode (include/mcl_modes.h)"""
     _fields_ = [('count', C.c_int64), ('score', C.c_int64), ('ix', C.c_int32), ('iy', C.c_int32), ('iyaw', C.c_int32),
                 ('reserved', C.c_int32), ('mean6', C.c_double * 6), ('cov_xy', C.c_double * 3), ('yaw_R', C.c_double)]
+
+
+class HistoryEst(C.Structure):
+    """mcl_history_est (include/mcl_history.h)"""
+    _fields_ = [('stamp', C.c_double), ('n_unique', C.c_int64), ('x', C.c_double), ('y', C.c_double), ('yaw', C.c_double),
+                ('yaw_R', C.c_double), ('cov_xy', C.c_double * 3)]
 
 
 # every symbol include/mcl.h, mcl_dr.h and mcl_map.h declare: name -> (restype, argtypes)
@@ -169,6 +176,19 @@ MODES_SYMBOLS = {
     'mcl_pose_modes': (C.c_int, [_vp, C.POINTER(ModeGrid), _i32, C.POINTER(Mode), C.POINTER(_i32), C.POINTER(C.c_int64)]),
 }
 
+# include/mcl_history.h: the particle genealogy (a table of its own, like MODES_SYMBOLS)
+HISTORY_SYMBOLS = {
+    'mcl_history_bytes': (C.c_int, [_i64, _i32, C.POINTER(C.c_int64)]),
+    'mcl_history_enable': (C.c_int, [_vp, _i32]),
+    'mcl_history_disable': (C.c_int, [_vp]),
+    'mcl_history_reset': (C.c_int, [_vp]),
+    'mcl_history_record': (C.c_int, [_vp, _d]),
+    'mcl_history_frames': (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_int64), _vp]),
+    'mcl_history_ancestors': (C.c_int, [_vp, _i32, _vp]),
+    'mcl_history_smooth': (C.c_int, [_vp, _i32, C.POINTER(HistoryEst)]),
+    'mcl_history_path': (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -181,7 +201,8 @@ def load():
         raise ImportError('libmcl_hip.so not built (%s): the MCL hot path has no fallback; run '
                           '__graft_entry__.build()' % SO_PATH)
     lib = C.CDLL(SO_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()):
+    for name, (res, args) in (list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()) +
+                              list(HISTORY_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -9,6 +9,7 @@
 #include "mcl_host_landmarks.h"
 #include "mcl_host_ranges.h"
 #include "mcl_host_step.h"
+#include "mcl_host_history.h"
 // global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
 #include "mcl_recovery.h"
 // (the kernels of mcl_pose_modes, include/mcl_modes.h, come with mcl_host.h: csrc/mcl_modes.h)
@@ -222,6 +223,7 @@ int mcl_init_particles(mcl_handle* h, const double* replay_normals) {
   HIPCHK(h, hipGetLastError());
   filter_restarted(h);
   h->have_state = true;
+  history_clear(h);
   return MCL_OK;
 }
 
@@ -563,6 +565,7 @@ int mcl_set_particles(mcl_handle* h, const double* soa) {
                            h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->have_state = true;
+  history_clear(h);
   return MCL_OK;
 }
 
@@ -1020,6 +1023,7 @@ int mcl_init_particles_uniform(mcl_handle* h, const mcl_box* box, const double* 
   HIPCHK(h, hipGetLastError());
   filter_restarted(h);
   h->have_state = true;
+  history_clear(h);
   return MCL_OK;
 }
 
@@ -1179,6 +1183,92 @@ int mcl_pose_modes(mcl_handle* h, const mcl_mode_grid* g, int32_t k_max, mcl_mod
   }
   *n_modes = found;
   return MCL_OK;
+}
+
+// ---- particle genealogy (include/mcl_history.h; host: mcl_host_history.h, kernels: csrc/mcl_history.h)
+int mcl_history_bytes(int64_t n, int32_t depth, int64_t* bytes) { return history_bytes_impl(n, depth, bytes); }
+
+int mcl_history_disable(mcl_handle* h) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!h->hist_on) return MCL_OK;
+  RET_IF(set_device(h));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // (a compose or a record in flight still writes the buffers)
+  history_free(h);
+  return MCL_OK;
+}
+
+int mcl_history_enable(mcl_handle* h, int32_t depth) {
+  if (!h) return MCL_ERR_INVALID;
+  if (depth < 1 || depth > MCL_HISTORY_MAX_DEPTH) return fail(h, MCL_ERR_INVALID, "history_enable: depth outside 1 ... 1024");
+  if (h->world > 1 || h->cfg.comm_mode != MCL_COMM_NONE || h->comm)
+    return fail(h, MCL_ERR_UNSUPPORTED, "history_enable: a sharded cloud is not supported");
+  RET_IF(set_device(h));   // (the ring is allocated on the handle's device, whichever is current in the caller's thread)
+  RET_IF(mcl_history_disable(h));
+  const int rc = history_alloc(h, depth);
+  if (rc != MCL_OK) {
+    const std::string keep = h->err;
+    history_free(h);
+    h->err = keep;
+    return rc;
+  }
+  h->hist_stamp.assign((size_t)depth, 0.0);
+  h->hist_depth = depth;
+  history_clear(h);
+  h->hist_on = true;
+  return MCL_OK;
+}
+
+int mcl_history_reset(mcl_handle* h) {
+  if (!h) return MCL_ERR_INVALID;
+  RET_IF(need_history(h, "history_reset"));
+  history_clear(h);
+  return MCL_OK;
+}
+
+int mcl_history_record(mcl_handle* h, double stamp) {
+  if (!h) return MCL_ERR_INVALID;
+  RET_IF(need_history(h, "history_record"));
+  if (!h->have_state) return fail(h, MCL_ERR_STATE, "history_record: no particles (call mcl_init_particles / mcl_set_particles first)");
+  RET_IF(set_device(h));
+  return history_record(h, stamp);
+}
+
+int mcl_history_frames(mcl_handle* h, int32_t* held, int64_t* recorded, double* stamps) {
+  if (!h) return MCL_ERR_INVALID;
+  RET_IF(need_history(h, "history_frames"));
+  if (held) *held = h->hist_held;
+  if (recorded) *recorded = h->hist_recorded;
+  if (stamps)
+    for (int k = 0; k < h->hist_held; ++k) stamps[k] = h->hist_stamp[(size_t)history_frame_index(h, k)];
+  return MCL_OK;
+}
+
+int mcl_history_ancestors(mcl_handle* h, int32_t lag, uint32_t* slots) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!slots) return fail(h, MCL_ERR_INVALID, "history_ancestors: null argument");
+  RET_IF(need_history(h, "history_ancestors"));
+  if (lag < 0 || lag >= h->hist_held) return fail(h, MCL_ERR_INVALID, "history_ancestors: lag outside the frames held");
+  RET_IF(set_device(h));
+  return history_ancestors(h, lag, slots);
+}
+
+int mcl_history_smooth(mcl_handle* h, int32_t lags, mcl_history_est* est) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!est) return fail(h, MCL_ERR_INVALID, "history_smooth: null argument");
+  RET_IF(need_history(h, "history_smooth"));
+  if (lags < 1 || lags > h->hist_held) return fail(h, MCL_ERR_INVALID, "history_smooth: lags outside the frames held");
+  RET_IF(set_device(h));
+  return history_smooth(h, lags, est);
+}
+
+int mcl_history_path(mcl_handle* h, int64_t slot, int32_t lags, double* xyyaw, uint32_t* slots) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!xyyaw) return fail(h, MCL_ERR_INVALID, "history_path: null argument");
+  RET_IF(need_history(h, "history_path"));
+  if (slot < 0 || slot >= h->n) return fail(h, MCL_ERR_INVALID, "history_path: slot outside the handle");
+  if (lags < 1 || lags > h->hist_held) return fail(h, MCL_ERR_INVALID, "history_path: lags outside the frames held");
+  RET_IF(set_device(h));
+  return history_path(h, slot, lags, xyyaw, slots);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

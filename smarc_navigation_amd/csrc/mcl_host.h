@@ -1,7 +1,7 @@
 // mcl_host.h -- host side of libmcl_hip.so, part 1: the handle (device buffers, streams, communicators, caches) and
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
-// mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h
+// mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,6 +30,7 @@
 #include "mcl_landmarks.h"
 #include "mcl_ranges.h"
 #include "mcl_modes.h"
+#include "mcl_history.h"
 
 #define MEAN_RING 4096
 #define RING_STRIDE 20  // doubles per mean/cov result: 16 payload + [16] format tag
@@ -216,6 +217,19 @@ struct mcl_handle {
   DevBuf<u64> modes_rec;       // per-workgroup records: MCL_MAX_GRID outside counts, then MCL_MAX_GRID selection keys
   DevBuf<double> modes_part;   // per-workgroup moment sums [k][MODES_SUMS][grid]
   DevBuf<double> modes_res;    // MODES_RES_WORDS: the summed moments, the peaks, the outside count
+  // particle genealogy (include/mcl_history.h; all allocated by mcl_history_enable, freed by mcl_history_disable)
+  bool hist_on = false;
+  int hist_depth = 0, hist_held = 0, hist_head = -1;   // ring: frames held, index of the newest (-1: none)
+  long long hist_recorded = 0;
+  bool hist_ident = true;      // the link is the identity (nothing is stored for it: enable, reset, every record)
+  int hist_cur = 0;            // which link buffer holds the link when it is not the identity
+  DevBuf<u32> hist_link[2];    // n each: link, and where the next compose writes link'
+  DevBuf<u32> hist_parent;     // depth x n: the frames' parent slots
+  DevBuf<double> hist_xyw;     // depth x 3 x n: the frames' x, y, yaw
+  DevBuf<u32> hist_cnt[2];     // n each: descendant counts of the frame the walk is at / of the one before it
+  DevBuf<double> hist_part;    // per-workgroup sums [HIST_SUMS][grid]
+  DevBuf<double> hist_res;     // depth x HIST_RES_WORDS: the smoother's sums per lag (and the path's records)
+  std::vector<double> hist_stamp;   // depth: the frames' stamps
   bool timing = false;
   std::vector<TimedRegion> regions;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -459,6 +473,10 @@ int state_overwritten(mcl_handle* h) {
   h->visit_ready = false;
   return MCL_OK;
 }
+// particle genealogy (mcl_host_history.h): the compose behind a resample's gather -- alt: the explicit-index schemes'
+// slot map -- and the clean start when the state is overwritten by an init call or mcl_set_particles
+int history_after_resample(mcl_handle* h, bool alt);
+void history_clear(mcl_handle* h);
 // The filter starts again from fresh particles (both init calls): the Philox steps count from 0, no weights, no CDF.
 void filter_restarted(mcl_handle* h) {
   h->step_predict = h->step_resample = h->step_inject = 0;

@@ -1,7 +1,8 @@
 // mcl_host_pure.h -- the host arithmetic of libmcl_hip.so that touches no device: tf.transformations' Euler /
 // quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
 // weight statistics, and the safety bounds kernels rely on unchecked (steepest patch gradient of a height grid, landmark
-// gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes).  No HIP header: the
+// gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes, the bytes of
+// mcl_history_enable).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -14,6 +15,7 @@
 #include "../../include/mcl.h"
 #include "../../include/mcl_recovery.h"
 #include "../../include/mcl_modes.h"
+#include "../../include/mcl_history.h"
 
 namespace {
 
@@ -267,6 +269,16 @@ int mode_grid_check_impl(const mcl_mode_grid* g, int64_t* n_cells, const char** 
   if (reason) *reason = why;
   if (why) return MCL_ERR_INVALID;
   if (n_cells) *n_cells = (int64_t)g->nx * (int64_t)g->ny * (int64_t)g->n_yaw;
+  return MCL_OK;
+}
+
+// the device bytes mcl_history_enable allocates (include/mcl_history.h): depth frames of n x (u32 parent + 3 doubles), two
+// link and two count buffers of n x u32, HISTORY_RES_WORDS result doubles per frame, HISTORY_PART_WORDS reduction records
+// (mcl_host_history.h checks both constants against the kernels').  n <= 2^31 - 1 and depth <= 1024 cannot overflow 64 bits.
+constexpr int64_t HISTORY_RES_WORDS = 10, HISTORY_PART_WORDS = 8 * 2048;
+int history_bytes_impl(int64_t n, int32_t depth, int64_t* bytes) {
+  if (!bytes || n < 1 || n > 0x7fffffffll || depth < 1 || depth > MCL_HISTORY_MAX_DEPTH) return MCL_ERR_INVALID;
+  *bytes = 28 * n * (int64_t)depth + 16 * n + 8 * HISTORY_RES_WORDS * (int64_t)depth + 8 * HISTORY_PART_WORDS;
   return MCL_OK;
 }
 

@@ -1,6 +1,7 @@
 """Thin Python wrapper over the C ABI handle (include/mcl.h).  numpy in / numpy out; all compute
 runs in libmcl_hip.so on the GPU."""
 import ctypes as C
+import dataclasses
 import math
 
 import numpy as np
@@ -68,6 +69,24 @@ class PoseMode(object):
 
     def __repr__(self):
         return 'PoseMode(%r)' % (self.as_dict(),)
+
+
+@dataclasses.dataclass
+class HistoryEstimate(object):
+    """mcl_history_est as a Python object: the smoothed estimate of one recorded frame (include/mcl_history.h)"""
+    lag: int
+    stamp: float
+    n_unique: int
+    x: float
+    y: float
+    yaw: float
+    yaw_R: float
+    cov_xy: np.ndarray   # xx, xy, yy
+
+    def as_dict(self):
+        d = dataclasses.asdict(self)
+        d['cov_xy'] = [float(v) for v in self.cov_xy]
+        return d
 
 
 def make_mode_grid(x0, y0, cell, nx, ny, n_yaw):
@@ -210,6 +229,58 @@ class Engine(object):
         nm, no = C.c_int32(0), C.c_int64(0)
         self._ck(self.lib.mcl_pose_modes(self.h, C.byref(g), k, out, C.byref(nm), C.byref(no)))
         return [PoseMode(out[j]) for j in range(nm.value)], int(no.value)
+
+    # ---- particle genealogy and the fixed-lag smoother (include/mcl_history.h)
+    def history_bytes(self, depth):
+        """device bytes history_enable(depth) allocates on this handle (mcl_history_bytes: host arithmetic)"""
+        b = C.c_int64(0)
+        self._ck(self.lib.mcl_history_bytes(self.n, int(depth), C.byref(b)))
+        return int(b.value)
+
+    def history_enable(self, depth):
+        """keep the ancestor link of every resample and a ring of `depth` recorded frames"""
+        self._ck(self.lib.mcl_history_enable(self.h, int(depth)))
+
+    def history_disable(self):
+        self._ck(self.lib.mcl_history_disable(self.h))
+
+    def history_reset(self):
+        """forget the frames, link = identity (a clean cut, e.g. after inject_uniform)"""
+        self._ck(self.lib.mcl_history_reset(self.h))
+
+    def history_record(self, stamp=0.0):
+        """append a frame: the link since the last record and x, y, yaw of every slot as they are now (asynchronous)"""
+        self._ck(self.lib.mcl_history_record(self.h, float(stamp)))
+
+    def history_frames(self):
+        """(held, recorded, stamps of the held frames, newest first)"""
+        held, rec = C.c_int32(0), C.c_int64(0)
+        self._ck(self.lib.mcl_history_frames(self.h, C.byref(held), C.byref(rec), None))
+        stamps = np.zeros(max(int(held.value), 1))
+        self._ck(self.lib.mcl_history_frames(self.h, None, None, _ptr(stamps)))
+        return int(held.value), int(rec.value), stamps[:held.value].copy()
+
+    def history_ancestors(self, lag=0):
+        """slots[i] = the slot of the frame at `lag` (0: the newest) that current slot i descends from (uint32)"""
+        out = np.zeros(self.n, np.uint32)
+        self._ck(self.lib.mcl_history_ancestors(self.h, int(lag), _ptr(out)))
+        return out
+
+    def history_smooth(self, lags):
+        """the smoothed estimates of the frames at lags 0 ... lags - 1: a list of HistoryEstimate"""
+        lags = int(lags)
+        out = (_lib.HistoryEst * max(lags, 1))()
+        self._ck(self.lib.mcl_history_smooth(self.h, lags, out))
+        return [HistoryEstimate(k, float(o.stamp), int(o.n_unique), float(o.x), float(o.y), float(o.yaw), float(o.yaw_R),
+                                np.array(o.cov_xy[:], dtype=np.float64)) for k, o in enumerate(out[:lags])]
+
+    def history_path(self, slot, lags):
+        """(xyyaw (lags, 3), slots (lags,)): the trajectory of current slot `slot` through the frames at lags 0 ... lags - 1
+        (a descendant of the best particle of weight_stats() gives the MAP path)"""
+        lags = int(lags)
+        xyw, sl = np.zeros((max(lags, 1), 3)), np.zeros(max(lags, 1), np.uint32)
+        self._ck(self.lib.mcl_history_path(self.h, int(slot), lags, _ptr(xyw), _ptr(sl)))
+        return xyw[:lags], sl[:lags]
 
     def predict(self, v, wz, q, z, dt, normals=None, stamp=0.0):
         nz = _f64(normals)

@@ -126,6 +126,79 @@ def pose_rmse(est_xy, ref_xy):
     return float(np.sqrt(np.mean(np.sum(d * d, axis=1))))
 
 
+class SmoothTrack(object):
+    """The fixed-lag smoothed track of a replay (include/mcl_history.h): history is enabled with depth lag + 1 and one
+    frame is recorded per resampled ping.  At every record the lag-0 estimate is the FILTERED pose of that ping (the mean of
+    the cloud the resample left); once lag + 1 frames are held, the estimate at lag `lag` -- that ping's pose given the
+    `lag` pings measured since -- leaves the window and is final.  finish() emits the tail: the frames still in the window,
+    smoothed by whatever followed them.  Every entry carries n_unique, the distinct ancestors the cloud had in its frame.
+
+    Cost: one mcl_history_smooth per record -- a walk over ONE frame while the window fills (the filtered pose alone), over
+    all lag + 1 frames once it is full (the walk that reaches lag `lag` passes every frame between) -- and one
+    synchronisation each: the smoother's price times the ping count, fine for an offline replay, not for a live node.
+
+    A re-initialisation of the particles in mid-stream (mcl_init_particles, mcl_set_particles) clears the ring: the pings
+    still in the window can no longer be smoothed.  They are emitted with their filtered pose and n_unique = -1."""
+
+    def __init__(self, engine, lag):
+        self.e, self.lag = engine, int(lag)
+        self.e.history_enable(self.lag + 1)
+        self.idx, self.stamp, self.filtered = [], [], []
+        self.smoothed, self.n_unique = [], []
+        self._recorded = 0
+
+    def record(self, idx, stamp):
+        """call right after a resample (ping `idx` of the stream, at `stamp`)"""
+        self.e.history_record(stamp)
+        held, recorded, _ = self.e.history_frames()
+        if recorded != self._recorded + 1:       # the ring was cleared under us: what was in the window stays unsmoothed
+            self._cut()
+        self._recorded = recorded
+        full = held == self.lag + 1
+        est = self.e.history_smooth(held if full else 1)
+        self.idx.append(int(idx))
+        self.stamp.append(float(stamp))
+        self.filtered.append([est[0].x, est[0].y, est[0].yaw])
+        if full:
+            self._emit(est[self.lag])
+
+    def _emit(self, est):
+        self.smoothed.append([est.x, est.y, est.yaw])
+        self.n_unique.append(est.n_unique)
+
+    def _cut(self):
+        for k in range(len(self.smoothed), len(self.filtered)):
+            self.smoothed.append(list(self.filtered[k]))
+            self.n_unique.append(-1)
+
+    def finish(self):
+        """the tail, then the arrays: dict(idx, stamp, filtered_xyyaw[m,3], smoothed_xyyaw[m,3], n_unique[m], lag)"""
+        held, recorded = self.e.history_frames()[:2] if self.idx else (0, 0)
+        if recorded != self._recorded:
+            self._cut()
+        elif held:
+            est = self.e.history_smooth(held)
+            first = held - 2 if held == self.lag + 1 else held - 1   # (a full window's oldest frame is out already)
+            for k in range(first, -1, -1):
+                self._emit(est[k])
+        return dict(idx=np.array(self.idx, dtype=np.int64), stamp=np.array(self.stamp),
+                    filtered_xyyaw=np.array(self.filtered).reshape(-1, 3), smoothed_xyyaw=np.array(self.smoothed).reshape(-1, 3),
+                    n_unique=np.array(self.n_unique, dtype=np.int64), lag=self.lag)
+
+
+def smooth_summary(track, stream, summary):
+    """what a smoothed track adds to a replay's summary: pings, the smallest n_unique and -- with truth in the stream --
+    the smoothed track's pose RMSE beside the filtered one's, both at the resampled pings"""
+    summary['smooth_lag'], summary['smooth_pings'] = int(track['lag']), int(len(track['idx']))
+    if len(track['idx']):
+        live = track['n_unique'][track['n_unique'] >= 0]      # (-1: a ping whose lineage a re-initialisation cut)
+        summary['smooth_n_unique_min'] = int(live.min()) if len(live) else 0
+        if 'truth_xyz' in stream:
+            ref = np.asarray(stream['truth_xyz'])[track['idx']][:, :2]
+            summary['filtered_rmse_vs_truth'] = pose_rmse(track['filtered_xyyaw'][:, :2], ref)
+            summary['smoothed_rmse_vs_truth'] = pose_rmse(track['smoothed_xyyaw'][:, :2], ref)
+
+
 def odom_stream_from_raw(t, kind, data, gps_map=None, pressure_tf=None, dvl_period=0.2, dr_period=0.02):
     """Raw IMU / DVL / depth / thruster events (synth.raw_sensor_events format) -> the odometry stream
     `replay` consumes, through the dead-reckoning integrator (dr.py): one sample
@@ -145,8 +218,10 @@ def odom_stream_from_raw(t, kind, data, gps_map=None, pressure_tf=None, dvl_peri
     return stream, m2o_mat
 
 
-def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5):
-    """Drive the node with a recorded stream; returns dict(pf_xyz[n_pub,3], pub_idx, summary)."""
+def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0):
+    """Drive the node with a recorded stream; returns dict(pf_xyz[n_pub,3], pub_idx, summary).  smooth_lag > 0: also
+    out['smooth'], the lag-smooth_lag smoothed track beside the filtered one, one entry per resample of the node
+    (SmoothTrack; the node's particle genealogy: include/mcl_history.h)."""
     from . import auv_pf as node
     from . import msgs
     tr = node.RecordingTransport(utm2map)
@@ -161,11 +236,22 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])} if 'mbes_idx' in stream else {}
     pub_idx, pf_xyz = [], []
     stats = DRStats() if ('gps_idx' in stream and 'dr_xyz' in stream) else None
+    smooth, at = None, [0]
+    if smooth_lag > 0:
+        # every resample of the node -- whichever callback asked for it -- is followed by a record
+        smooth = SmoothTrack(pf.particles, smooth_lag)
+        node_resample = pf.resample
+
+        def resample_and_record(weights):
+            node_resample(weights)
+            smooth.record(at[0], pf.time)
+        pf.resample = resample_and_record
     if stats is not None:
         # visual_tools transforms the fix into the odom frame: (map <- odom)^-1 (map <- utm)
         u2m = np.identity(4) if utm2map is None else np.asarray(utm2map, dtype=np.float64)
         stats.utm2odom = np.linalg.inv(np.identity(4) if m2o is None else np.asarray(m2o, dtype=np.float64)).dot(u2m)
     for k in range(n):
+        at[0] = k
         pf.odom_callback(msgs.odometry_from_stream(stream, k))
         if stats is not None:
             stats.add(1, stream['stamp'][k], stream['dr_xyz'][k])
@@ -200,6 +286,9 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
             summary[tag + '_distance'], summary[tag + '_final'] = track_metrics(ref.T)
             summary['pf_rmse_vs_' + tag] = pose_rmse(pf_xyz[:, :2], ref[:, :2])
     out = dict(pf_xyz=pf_xyz, pub_idx=np.array(pub_idx), summary=summary)
+    if smooth is not None:
+        out['smooth'] = smooth.finish()
+        smooth_summary(out['smooth'], stream, summary)
     if stats is not None:
         out['stats'] = stats
         out['err_gps_pf'], out['err_gps_dr'] = stats.error_series()
@@ -293,14 +382,16 @@ def replay_bag(path, params=None, m2o=None, utm2map=None, grid=None, mesh=None, 
 
 def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=1.0, m2o=None, yaw=(-np.pi, np.pi),
                    process_cov=(0.01, 0.01, 0, 0, 0, 1e-4), resample_cov=(0.04, 0.04, 0, 0, 0, 1e-3), alpha_slow=0.001,
-                   alpha_fast=0.1, max_fraction=0.1, inject=True, estimate='mean', mode_cell=1.0, mode_n_yaw=36):
+                   alpha_fast=0.1, max_fraction=0.1, inject=True, estimate='mean', mode_cell=1.0, mode_n_yaw=36,
+                   smooth_lag=0):
     """Global localisation with kidnap recovery on a recorded stream (--recover): the cloud starts uniform over the map's
     footprint, and every ping runs the separate calls  predict ... -> update_mbes -> weight_stats -> resample ->
     inject_uniform(fraction)  with the fraction of recovery.AugmentedMCL (the likelihood per valid beam, a short-term
     against a long-term average).  The node class is not involved.  estimate='mean' publishes mcl_mean_cov's pose;
     'mode' the heaviest cluster's (mode 0 of mcl_pose_modes on a lattice of mode_cell metres x mode_n_yaw bins over the
     map's footprint) when there is one, otherwise the mean.  Returns dict(pf_xyz[m,3] published pose after every ping,
-    pub_idx, fractions[m], injected[m], log_lik_per_beam[m], n_eff[m], summary)."""
+    pub_idx, fractions[m], injected[m], log_lik_per_beam[m], n_eff[m], summary).  smooth_lag > 0: also out['smooth'], the
+    lag-smooth_lag smoothed track (SmoothTrack), one entry per ping; an injected particle inherits its slot's past."""
     from . import engine as eng
     from . import recovery
     if 'mbes_idx' not in stream or (grid is None and mesh is None):
@@ -313,6 +404,7 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
     else:
         e.set_map_mesh(mesh['verts'], mesh['tris'])
     e.init_particles_uniform(yaw=yaw)
+    smooth = SmoothTrack(e, smooth_lag) if smooth_lag > 0 else None
     lattice = e.mode_grid(mode_cell, mode_n_yaw) if estimate == 'mode' else None
     aug = recovery.AugmentedMCL(alpha_slow, alpha_fast, max_fraction)
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])}
@@ -332,6 +424,8 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
         out['log_lik_per_beam'].append(aug.observe(st, int(np.count_nonzero(ranges > 0))))
         out['n_eff'].append(st.n_eff)
         e.resample()
+        if smooth is not None:
+            smooth.record(k, t)
         frac = aug.fraction() if inject else 0.0
         out['fractions'].append(frac)
         out['injected'].append(e.inject_uniform(frac, yaw=yaw) if frac > 0.0 else 0)
@@ -344,6 +438,7 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
                 pose = modes[0].mean[:3]
         out['pf_xyz'].append(pose)
         out['pub_idx'].append(k)
+    track = smooth.finish() if smooth is not None else None
     e.close()
     for name in out:
         out[name] = np.array(out[name])
@@ -353,8 +448,21 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
         if 'truth_xyz' in stream:
             ref = np.asarray(stream['truth_xyz'])[out['pub_idx']]
             summary['final_error_vs_truth'] = float(np.linalg.norm(out['pf_xyz'][-1, :2] - ref[-1, :2]))
+    if track is not None:
+        out['smooth'] = track
+        smooth_summary(track, stream, summary)
     out['summary'] = summary
     return out
+
+
+def save_smooth(out_path, res):
+    """--smooth with --out: the smoothed track as a CSV of its own beside the filtered one (OUT.smooth.csv)"""
+    tr = res.get('smooth')
+    if tr is None:
+        return
+    np.savetxt(out_path + '.smooth.csv',
+               np.column_stack([tr['idx'], tr['stamp'], tr['filtered_xyyaw'], tr['smoothed_xyyaw'], tr['n_unique']]).reshape(-1, 9),
+               delimiter=',', header='step,stamp,filtered_x,filtered_y,filtered_yaw,smoothed_x,smoothed_y,smoothed_yaw,n_unique')
 
 
 def main(argv=None):
@@ -376,7 +484,12 @@ def main(argv=None):
     ap.add_argument('--sigma', type=float, default=1.0, help='--recover: MBES range sigma')
     ap.add_argument('--estimate', choices=('mean', 'mode'), default='mean',
                     help='--recover: publish the mean pose, or the heaviest cluster of the cloud (mcl_pose_modes)')
+    ap.add_argument('--smooth', type=int, default=0, metavar='LAG',
+                    help='also emit the fixed-lag smoothed track: every resampled ping as the LAG pings after it correct it '
+                         '(particle genealogy, include/mcl_history.h); --out then writes it next to the filtered track')
     a = ap.parse_args(argv)
+    if a.smooth < 0 or a.smooth >= 1024:
+        ap.error('--smooth: LAG must be 0 ... 1023')
     if a.bag:
         grid = dict(np.load(a.map_grid)) if a.map_grid else None
         res = replay_bag(a.stream, dict(particle_count=a.particles, seed=a.seed), grid=grid, odom_topic=a.odom_topic,
@@ -396,15 +509,17 @@ def main(argv=None):
     grid = dict(np.load(a.map_grid)) if a.map_grid else None
     if a.recover:
         res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=a.sigma, m2o=m2o,
-                             estimate=a.estimate)
+                             estimate=a.estimate, smooth_lag=a.smooth)
         if a.out:
             np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz'], res['fractions']]), delimiter=',',
                        header='step,x,y,z,injected_fraction')
+            save_smooth(a.out, res)
         print(json.dumps(res['summary']))
         return
-    res = replay(stream, dict(particle_count=a.particles, seed=a.seed), m2o=m2o, grid=grid)
+    res = replay(stream, dict(particle_count=a.particles, seed=a.seed), m2o=m2o, grid=grid, smooth_lag=a.smooth)
     if a.out:
         np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz']]), delimiter=',', header='step,x,y,z')
+        save_smooth(a.out, res)
     print(json.dumps(res['summary']))
 
 

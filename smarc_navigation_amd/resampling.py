@@ -37,3 +37,20 @@ def residual_resample(weights):
     n = len(w)
     k = int(np.floor(n * w).astype(int).sum())
     return _engine.resample_indices(w, random(max(n - k, 0)) if n - k > 0 else np.zeros(1), _engine.RESIDUAL)
+
+
+def slot_ancestors(indices):
+    """The slot map A of a resample (include/mcl_history.h): slot i of the resampled state holds the pre-resample state of
+    slot A[i].  auv_pf.py:183-198 in one piece: a slot whose index occurs in `indices` keeps its state; the other (lost)
+    slots, ascending, receive dupes[0], dupes[1], ... -- `indices` with the first occurrence of each distinct value removed,
+    order preserved.  Pure numpy (no GPU); uint32, like mcl_history_ancestors."""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    n = idx.size
+    _, first = np.unique(idx, return_index=True)
+    later = np.ones(n, dtype=bool)
+    later[first] = False
+    kept = np.zeros(n, dtype=bool)
+    kept[idx] = True
+    a = np.arange(n, dtype=np.int64)
+    a[~kept] = idx[later]
+    return a.astype(np.uint32)
