@@ -1,5 +1,5 @@
-"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h and
-mcl_history.h).
+"""ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
+mcl_history.h and mcl_acoustic.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -189,6 +189,13 @@ HISTORY_SYMBOLS = {
     'mcl_history_path': (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
 }
 
+# include/mcl_acoustic.h: delayed acoustic position fixes and beacon ranges (a table of its own, like HISTORY_SYMBOLS)
+ACOUSTIC_SYMBOLS = {
+    'mcl_update_fix': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _d, _i32]),
+    'mcl_update_beacon_ranges': (C.c_int, [_vp, _vp, _vp, _i32, _d, _vp, _vp, _i32, _d, _i32]),
+    'mcl_history_bracket': (C.c_int, [_vp, _i32, _d, C.POINTER(_i32), C.POINTER(_d), C.POINTER(_i32)]),
+}
+
 _lib = None
 
 
@@ -202,7 +209,7 @@ def load():
                           '__graft_entry__.build()' % SO_PATH)
     lib = C.CDLL(SO_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()) +
-                              list(HISTORY_SYMBOLS.items())):
+                              list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -10,6 +10,8 @@ Divergences from the reference, all documented in INTEGRATION.md:
   * default resampling scheme on the GPU is systematic (resampling.py:135); pass
     resample_scheme='residual' for the node's literal behaviour (auv_pf.py:182).
 """
+import bisect
+import collections
 import math
 import threading
 
@@ -72,6 +74,17 @@ DEFAULT_PARAMS = {
     # measurement update of its own followed by the resampling, like a GPS fix.
     'dvl_topic': '', 'dvl_altitude_std': 0.2, 'dvl_range_max': 60.0,
     'dvl_sensor_offset': '[0.0, 0.0, 0.0, 0.0, 0.0, 0.0]',
+    # Acoustic position fixes (underwater GPS / USBL): nav_msgs/Odometry on `fix_topic` (the reference's
+    # /sam/external/uw_gps_odom, uw_gps/scripts/uw_gps_node.py:137,160-167; '' = not subscribed), position in the
+    # message's header.frame_id (map_frame, or anything the transport can take to it), isotropic `fix_std` metres.  A fix
+    # is OLD when it arrives.  `fix_history_depth` > 0 keeps the particle genealogy (include/mcl_history.h) in a ring of
+    # that many frames, one per resampling, and weights every particle by the pose its ancestor had at the fix's stamp
+    # (include/mcl_acoustic.h); a fix older than the ring or than `fix_max_age` seconds is dropped.  Depth 0: every fix is
+    # applied to the cloud as it is now (right only when the latency is small against fix_std / speed).  Each fix is a
+    # measurement update of its own followed by the resampling, like a GPS fix -- diving or not.
+    # Frames come with the resamplings; where nothing resamples for fix_max_age / fix_history_depth seconds the node
+    # records one on its own, so the ring spans fix_max_age.
+    'fix_topic': '', 'fix_std': 1.0, 'fix_history_depth': 0, 'fix_max_age': 10.0,
 }
 
 
@@ -90,6 +103,15 @@ def quaternion_from_euler(roll, pitch, yaw):
     cy, sy = math.cos(yaw / 2.0), math.sin(yaw / 2.0)
     return [cp * (sr * cy) - sp * (cr * sy), cp * (sr * sy) + sp * (cr * cy),
             cp * (cr * sy) - sp * (sr * cy), cp * (cr * cy) + sp * (sr * sy)]
+
+
+def euler_from_quaternion(q):
+    """tf.transformations.euler_from_quaternion, axes 'sxyz': (roll, pitch, yaw) of a quaternion (x, y, z, w)."""
+    m = matrix_from_tf((0.0, 0.0, 0.0), q)
+    cy = math.sqrt(m[0, 0] * m[0, 0] + m[1, 0] * m[1, 0])
+    if cy > np.finfo(float).eps * 4.0:
+        return math.atan2(m[2, 1], m[2, 2]), math.atan2(-m[2, 0], cy), math.atan2(m[1, 0], m[0, 0])
+    return math.atan2(-m[1, 2], m[1, 1]), math.atan2(-m[2, 0], cy), 0.0
 
 
 def load_map_file(path):
@@ -277,11 +299,21 @@ class auv_pf(object):
         self._last_ping_stamp = None
         if p['landmark_map_file']:
             self.set_landmarks(load_landmark_file(p['landmark_map_file'], float(p['rocks_depth'])))
+        # delayed acoustic fixes
+        self.fix_std, self.fix_max_age = float(p['fix_std']), float(p['fix_max_age'])
+        self.fix_history_depth = int(p['fix_history_depth'])
+        self.fixes_applied = self.fixes_dropped = 0
+        self.fix_lag_sum = 0.0      # summed age (filter clock - stamp) of the applied fixes
+        self._zrp_log = collections.deque(maxlen=4096)   # (stamp, z, roll, pitch) of the odometry, for the fix's stamp
+        self._fix_last_record = None   # stamp of the ring's newest frame (None: the ring is empty)
+        if self.fix_history_depth > 0:
+            self.particles.history_enable(self.fix_history_depth)
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
         self._replay = rs
         self.particles.init_particles(rs.randn(self.pc, 6))
+        self._fix_last_record = None   # (a re-initialisation clears the ring: include/mcl_history.h)
 
     def start_timing(self, stamp):
         """auv_pf.py:96-98: `Start timing now`."""
@@ -296,6 +328,8 @@ class auv_pf(object):
         with self.lock:
             self.time = odom_msg.header.stamp.to_sec()
             self.odom_latest = odom_msg
+            if self.fix_history_depth > 0:
+                self._log_zrp(odom_msg)
             if self.old_time and self.time > self.old_time:
                 self.predict(odom_msg)
             self.old_time = self.time
@@ -331,6 +365,14 @@ class auv_pf(object):
             self.particles.resample(u, self._replay.randn(self.pc, 6))
         else:
             self.particles.resample()
+        if self.fix_history_depth > 0 and (self._fix_last_record is None or self.time > self._fix_last_record):
+            # one frame per resampling: what a late fix is evaluated against.  The filter's clock moves with the odometry
+            # alone, so a second resampling before the next odometry message (a ping and a fix, a ping and a DVL altitude,
+            # two fixes) would record a second frame with the SAME stamp, which mcl_history_bracket refuses.  It is not
+            # recorded: the link carries both resamplings into the next frame, and the frame of this stamp stays the cloud
+            # its first resampling left.
+            self.particles.history_record(self.time)
+            self._fix_last_record = self.time
 
     def reassign_poses(self, lost, dupes):
         """Folded into resample() on the device (auv_pf.py:195-198 semantics)."""
@@ -455,6 +497,74 @@ class auv_pf(object):
             self.particles.update_ranges([alt], [[0.0, 0.0, -1.0]], self.dvl_altitude_std, self.dvl_range_max,
                                          self.dvl_sensor_offset)
             self.resample(self.particles)
+
+    # ---- delayed acoustic position fixes (include/mcl_acoustic.h)
+    def _log_zrp(self, odom_msg):
+        """Called under the lock with every odometry message, before its predict: z, roll, pitch by stamp, as long as a fix
+        may be old; and the particles as they are (at old_time) as a frame of the ring when it holds none yet or when
+        nothing has resampled for fix_max_age / fix_history_depth seconds -- frames come with the resamplings, and this
+        keeps the ring spanning fix_max_age where they are rare (no map, no pings): a fix taken in such a stretch still
+        finds the pose it belongs to."""
+        o = odom_msg.pose.pose.orientation
+        roll, pitch, _ = euler_from_quaternion([o.x, o.y, o.z, o.w])
+        if not self._zrp_log or self.time > self._zrp_log[-1][0]:
+            self._zrp_log.append((self.time, float(odom_msg.pose.pose.position.z), roll, pitch))
+        while self._zrp_log and self.time - self._zrp_log[0][0] > self.fix_max_age + 1.0:
+            self._zrp_log.popleft()
+        if self.old_time and (self._fix_last_record is None or
+                              self.old_time - self._fix_last_record >= self.fix_max_age / self.fix_history_depth):
+            self.particles.history_record(self.old_time)
+            self._fix_last_record = self.old_time
+
+    def _zrp_at(self, stamp):
+        """z, roll, pitch of the odometry message nearest `stamp` (None without one)"""
+        log = self._zrp_log
+        if not log:
+            return None
+        k = bisect.bisect_left(log, (stamp,))     # (the stamps were appended in order)
+        if k == len(log) or (k > 0 and stamp - log[k - 1][0] <= log[k][0] - stamp):
+            k -= 1
+        return [log[k][1], log[k][2], log[k][3]]
+
+    def fix_cb(self, fix_msg):
+        """nav_msgs/Odometry: an acoustic position fix, stamped when it was MEASURED.  With `fix_history_depth` > 0 the
+        stamp is bracketed among the recorded frames: inside the ring the update runs at that lag, with z, roll, pitch of
+        the odometry nearest the stamp; newer than the newest frame: against the cloud as it is; older than the ring or
+        than `fix_max_age`: dropped (fixes_dropped).  Depth 0: always against the cloud as it is.  Then the resampling."""
+        pos = fix_msg.pose.pose.position
+        xy = self._fix_in_map(fix_msg.header.frame_id, float(pos.x), float(pos.y), float(pos.z))
+        with self.lock:
+            if not self.old_time:
+                return
+            stamp = self._stamp_of(fix_msg)
+            age = self.time - stamp
+            if age > self.fix_max_age:
+                self.fixes_dropped += 1
+                return
+            lag, frac, zrp = -1, 0.0, None
+            if self.fix_history_depth > 0:
+                held, _, stamps = self.particles.history_frames()
+                zrp = self._zrp_at(stamp)
+                if held > 0 and zrp is not None and stamp <= stamps[0]:
+                    lag, frac, where = _engine.history_bracket(stamps, stamp)
+                    if where < 0 and stamp < stamps[-1]:
+                        self.fixes_dropped += 1
+                        return
+                else:
+                    zrp = None   # (newer than every frame: the cloud as it is, with its own z, roll, pitch)
+            self.particles.update_fix(xy, self.fix_std, zrp=zrp, lag=lag, frac=frac)
+            self.fixes_applied += 1
+            self.fix_lag_sum += age
+            self.resample(self.particles)
+
+    def _fix_in_map(self, frame_id, x, y, z):
+        if not frame_id or frame_id == self.map_frame:
+            return [x, y]
+        pt = _msgs.PointStamped()
+        pt.header.frame_id = frame_id
+        pt.point.x, pt.point.y, pt.point.z = x, y, z
+        out = self.transport.transformPoint(self.map_frame, pt)
+        return [float(out.point.x), float(out.point.y)]
 
     # ---- publishing, auv_pf.py:218-285
     def update_loc_pose(self, pose_list=None):

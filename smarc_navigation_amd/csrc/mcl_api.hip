@@ -10,6 +10,7 @@
 #include "mcl_host_ranges.h"
 #include "mcl_host_step.h"
 #include "mcl_host_history.h"
+#include "mcl_host_acoustic.h"
 // global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
 #include "mcl_recovery.h"
 // (the kernels of mcl_pose_modes, include/mcl_modes.h, come with mcl_host.h: csrc/mcl_modes.h)
@@ -1269,6 +1270,41 @@ int mcl_history_path(mcl_handle* h, int64_t slot, int32_t lags, double* xyyaw, u
   if (lags < 1 || lags > h->hist_held) return fail(h, MCL_ERR_INVALID, "history_path: lags outside the frames held");
   RET_IF(set_device(h));
   return history_path(h, slot, lags, xyyaw, slots);
+}
+
+// ---- delayed acoustic updates (include/mcl_acoustic.h; host: mcl_host_acoustic.h, kernels: csrc/mcl_acoustic.h)
+int mcl_update_fix(mcl_handle* h, const double xy_map[2], const double cov3[3], const double offset[3], const double zrp[3],
+                   int32_t lag, double frac, int32_t accumulate) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!xy_map || !cov3) return fail(h, MCL_ERR_INVALID, "update_fix: null argument");
+  if (!std::isfinite(xy_map[0]) || !std::isfinite(xy_map[1]) || !std::isfinite(cov3[0]) || !std::isfinite(cov3[1]) ||
+      !std::isfinite(cov3[2]) || !(cov3[0] > 0.0) || !(cov3[0] * cov3[2] - cov3[1] * cov3[1] > 0.0) ||
+      !std::isfinite(cov3[0] * cov3[2] - cov3[1] * cov3[1]))
+    return fail(h, MCL_ERR_INVALID, "update_fix: the fix must be finite and its covariance positive definite");
+  AcoArgs a;
+  bool arm = false;
+  RET_IF(acoustic_prepare(h, "update_fix", offset, zrp, lag, frac, accumulate != 0, a, &arm));
+  return fix_launch(h, a, arm, xy_map, cov3);
+}
+
+int mcl_update_beacon_ranges(mcl_handle* h, const double* beacons_xyz, const double* ranges, int32_t n_b, double sigma,
+                             const double offset[3], const double zrp[3], int32_t lag, double frac, int32_t accumulate) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!beacons_xyz || !ranges || n_b < 1 || n_b > MCL_ACOUSTIC_MAX_BEACONS || !(sigma > 0.0) || !std::isfinite(sigma))
+    return fail(h, MCL_ERR_INVALID, "update_beacon_ranges: bad argument (1 <= n_b <= 8, sigma > 0)");
+  for (int b = 0; b < n_b; ++b)
+    if (!std::isfinite(beacons_xyz[3 * b]) || !std::isfinite(beacons_xyz[3 * b + 1]) || !std::isfinite(beacons_xyz[3 * b + 2]) ||
+        std::isinf(ranges[b]))
+      return fail(h, MCL_ERR_INVALID, "update_beacon_ranges: a beacon is not finite or a range is infinite");
+  AcoArgs a;
+  bool arm = false;
+  RET_IF(acoustic_prepare(h, "update_beacon_ranges", offset, zrp, lag, frac, accumulate != 0, a, &arm));
+  return beacon_launch(h, a, arm, beacons_xyz, ranges, n_b, sigma);
+}
+
+int mcl_history_bracket(const double* stamps_newest_first, int32_t held, double stamp, int32_t* lag, double* frac,
+                        int32_t* where) {
+  return history_bracket_impl(stamps_newest_first, held, stamp, lag, frac, where);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

@@ -2,7 +2,7 @@
 // quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
 // weight statistics, and the safety bounds kernels rely on unchecked (steepest patch gradient of a height grid, landmark
 // gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes, the bytes of
-// mcl_history_enable).  No HIP header: the
+// mcl_history_enable, the pose arguments of the acoustic updates and mcl_history_bracket).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -16,6 +16,7 @@
 #include "../../include/mcl_recovery.h"
 #include "../../include/mcl_modes.h"
 #include "../../include/mcl_history.h"
+#include "../../include/mcl_acoustic.h"
 
 namespace {
 
@@ -279,6 +280,45 @@ constexpr int64_t HISTORY_RES_WORDS = 10, HISTORY_PART_WORDS = 8 * 2048;
 int history_bytes_impl(int64_t n, int32_t depth, int64_t* bytes) {
   if (!bytes || n < 1 || n > 0x7fffffffll || depth < 1 || depth > MCL_HISTORY_MAX_DEPTH) return MCL_ERR_INVALID;
   *bytes = 28 * n * (int64_t)depth + 16 * n + 8 * HISTORY_RES_WORDS * (int64_t)depth + 8 * HISTORY_PART_WORDS;
+  return MCL_OK;
+}
+
+// the pose arguments the acoustic updates share (include/mcl_acoustic.h), as far as they need no handle: nullptr, or the
+// rule that is broken
+const char* acoustic_pose_check(const double offset[3], const double zrp[3], int lag, double frac) {
+  if (lag < -1) return "lag below -1";
+  if (!(frac >= 0.0 && frac < 1.0)) return "frac outside [0, 1)";
+  if (lag < 0 && frac > 0.0) return "frac > 0 needs a lag";
+  if (lag >= 0 && !zrp) return "a lagged update needs zrp (frames hold x, y, yaw only)";
+  for (int k = 0; k < 3; ++k) {
+    if (offset && !std::isfinite(offset[k])) return "offset is not finite";
+    if (zrp && !std::isfinite(zrp[k])) return "zrp is not finite";
+  }
+  return nullptr;
+}
+
+// mcl_history_bracket (include/mcl_acoustic.h): where `stamp` falls among the frames' stamps, newest first
+int history_bracket_impl(const double* s, int32_t held, double stamp, int32_t* lag, double* frac, int32_t* where) {
+  if (!s || !lag || !frac || !where || held < 1 || !std::isfinite(stamp)) return MCL_ERR_INVALID;
+  for (int32_t k = 0; k < held; ++k)
+    if (!std::isfinite(s[k]) || (k > 0 && !(s[k - 1] > s[k]))) return MCL_ERR_INVALID;
+  *frac = 0.0;
+  if (stamp >= s[0]) {
+    *lag = 0;
+    *where = 1;
+    return MCL_OK;
+  }
+  if (stamp <= s[held - 1]) {
+    *lag = held - 1;
+    *where = -1;
+    return MCL_OK;
+  }
+  int32_t k = 0;
+  while (!(stamp > s[k + 1])) ++k;   // (s[held - 1] < stamp < s[0]: k + 1 <= held - 1)
+  const double f = (s[k] - stamp) / (s[k] - s[k + 1]);
+  *lag = k;
+  *frac = f < 1.0 ? f : std::nextafter(1.0, 0.0);   // (both differences may round to the same number)
+  *where = 0;
   return MCL_OK;
 }
 

@@ -282,6 +282,57 @@ class Engine(object):
         self._ck(self.lib.mcl_history_path(self.h, int(slot), lags, _ptr(xyw), _ptr(sl)))
         return xyw[:lags], sl[:lags]
 
+    # ---- delayed acoustic position fixes and beacon ranges (include/mcl_acoustic.h)
+    @staticmethod
+    def _cov3(cov):
+        """xx, xy, yy from a scalar std, three numbers (xx, xy, yy) or a 2 x 2 matrix"""
+        c = np.asarray(cov, dtype=np.float64)
+        if c.ndim == 0:
+            return np.array([float(c) ** 2, 0.0, float(c) ** 2])
+        if c.shape == (3,):
+            return np.ascontiguousarray(c)
+        if c.shape == (2, 2):
+            if c[0, 1] != c[1, 0]:
+                raise ValueError('update_fix: the covariance matrix is not symmetric')
+            return np.array([c[0, 0], c[0, 1], c[1, 1]])
+        raise ValueError('update_fix: cov is a scalar std, (xx, xy, yy) or a 2 x 2 matrix')
+
+    @staticmethod
+    def _vec3(a, name):
+        if a is None:
+            return None
+        v = _f64(a).reshape(-1)
+        if v.size != 3:
+            raise ValueError('%s: three numbers' % name)
+        return v
+
+    def update_fix(self, xy, cov, offset=None, zrp=None, lag=-1, frac=0.0, accumulate=False):
+        """position fix xy (map frame) with covariance `cov` (a scalar std, xx xy yy, or a 2 x 2 matrix), evaluated at the
+        pose each particle's ancestor had in the recorded frame at `lag` (moved `frac` of the way to the frame before it);
+        lag=-1: at the particle's pose now.  offset: the transponder in base_link; zrp: z, roll, pitch of the vehicle when
+        measured (needed with lag >= 0; None with lag=-1: the particles' own).  mcl_update_fix."""
+        p, c = _f64(xy).reshape(-1), self._cov3(cov)
+        if p.size != 2:
+            raise ValueError('update_fix: xy is two numbers')
+        off, z = self._vec3(offset, 'offset'), self._vec3(zrp, 'zrp')
+        self._ck(self.lib.mcl_update_fix(self.h, _ptr(p), _ptr(c), _ptr(off), _ptr(z), int(lag), float(frac),
+                                         1 if accumulate else 0))
+
+    def update_beacon_ranges(self, beacons, ranges, sigma, offset=None, zrp=None, lag=-1, frac=0.0, accumulate=False):
+        """slant ranges to fixed transponders at beacons (n_b x 3, map frame; n_b <= 8); a range <= 0 or NaN is skipped;
+        pose, offset, zrp, lag, frac, accumulate as in update_fix.  mcl_update_beacon_ranges."""
+        b, r = _f64(beacons).reshape(-1, 3), _f64(ranges).reshape(-1)
+        if r.size != b.shape[0]:
+            raise ValueError('update_beacon_ranges: %d ranges for %d beacons' % (r.size, b.shape[0]))
+        off, z = self._vec3(offset, 'offset'), self._vec3(zrp, 'zrp')
+        self._ck(self.lib.mcl_update_beacon_ranges(self.h, _ptr(b), _ptr(r), b.shape[0], float(sigma), _ptr(off), _ptr(z),
+                                                   int(lag), float(frac), 1 if accumulate else 0))
+
+    def history_bracket(self, stamp):
+        """(lag, frac, where) of `stamp` among the held frames' stamps (mcl_history_bracket over history_frames()): where 0:
+        between two frames, +1: not older than the newest, -1: not newer than the oldest.  MclError without a frame."""
+        return history_bracket(self.history_frames()[2], stamp)
+
     def predict(self, v, wz, q, z, dt, normals=None, stamp=0.0):
         nz = _f64(normals)
         od = make_odom(v, wz, q, z, stamp)
@@ -510,6 +561,15 @@ def comm_unique_id():
     buf = C.create_string_buffer(128)
     _lib.check(lib.mcl_comm_unique_id(buf))
     return buf.raw
+
+
+def history_bracket(stamps_newest_first, stamp):
+    """(lag, frac, where) of `stamp` among frame stamps, newest first (mcl_history_bracket: host arithmetic, no handle)"""
+    lib = _lib.load()
+    s = _f64(stamps_newest_first).reshape(-1)
+    lag, frac, where = C.c_int32(0), C.c_double(0.0), C.c_int32(0)
+    _lib.check(lib.mcl_history_bracket(_ptr(s), s.size, float(stamp), C.byref(lag), C.byref(frac), C.byref(where)))
+    return int(lag.value), float(frac.value), int(where.value)
 
 
 def merge_weight_stats(parts):

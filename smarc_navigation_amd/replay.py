@@ -218,12 +218,41 @@ def odom_stream_from_raw(t, kind, data, gps_map=None, pressure_tf=None, dvl_peri
     return stream, m2o_mat
 
 
-def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0):
+FIX_SMOOTH_CLASH = ('acoustic fixes (--fix-period) and the smoothed track (--smooth) both keep the particle genealogy, and one '
+                    'ring has one owner: run them separately')
+
+
+def make_fixes(stream, m2o, period, latency, std, seed=0):
+    """Synthetic acoustic fixes of a stream WITH TRUTH: every `period` seconds the truth position of that sample, taken
+    into the map frame, plus N(0, std^2 I) (seeded), stamped with the sample's time and delivered `latency` seconds later.
+    Returns a list of (deliver_at, stamp, x_map, y_map), in delivery order."""
+    if 'truth_xyz' not in stream:
+        raise ValueError('acoustic fixes are made from the truth track: the stream has no truth_xyz')
+    rs = np.random.RandomState(seed)
+    M = np.identity(4) if m2o is None else np.asarray(m2o, dtype=np.float64)
+    stamp, truth = np.asarray(stream['stamp'], dtype=np.float64), np.asarray(stream['truth_xyz'], dtype=np.float64)
+    out, due = [], float(stamp[0]) + float(period)
+    for k in range(len(stamp)):
+        if stamp[k] < due:
+            continue
+        due += float(period)
+        p = M.dot([truth[k, 0], truth[k, 1], truth[k, 2], 1.0])[:2] + float(std) * rs.randn(2)
+        out.append((float(stamp[k]) + float(latency), float(stamp[k]), float(p[0]), float(p[1])))
+    return out
+
+
+def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0,
+           fix_period=0.0, fix_latency=0.0, fix_seed=0):
     """Drive the node with a recorded stream; returns dict(pf_xyz[n_pub,3], pub_idx, summary).  smooth_lag > 0: also
     out['smooth'], the lag-smooth_lag smoothed track beside the filtered one, one entry per resample of the node
-    (SmoothTrack; the node's particle genealogy: include/mcl_history.h)."""
+    (SmoothTrack; the node's particle genealogy: include/mcl_history.h).  fix_period > 0 (a stream with truth_xyz): acoustic
+    fixes every fix_period seconds with the node's `fix_std` of noise, delivered fix_latency seconds late to fix_cb
+    (make_fixes); the node's `fix_history_depth` decides whether they are applied to the past or to the present; the
+    summary gains fixes_applied, fixes_dropped and fix_mean_lag (mean age of the applied fixes, seconds)."""
     from . import auv_pf as node
     from . import msgs
+    if smooth_lag > 0 and fix_period > 0:
+        raise ValueError(FIX_SMOOTH_CLASH)
     tr = node.RecordingTransport(utm2map)
     pf = node.auv_pf(params or {}, m2o_mat=m2o, transport=tr)
     if grid is not None:
@@ -236,6 +265,8 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])} if 'mbes_idx' in stream else {}
     pub_idx, pf_xyz = [], []
     stats = DRStats() if ('gps_idx' in stream and 'dr_xyz' in stream) else None
+    fixes = make_fixes(stream, m2o, fix_period, fix_latency, pf.fix_std, fix_seed) if fix_period > 0 else []
+    next_fix = 0
     smooth, at = None, [0]
     if smooth_lag > 0:
         # every resample of the node -- whichever callback asked for it -- is followed by a record
@@ -269,6 +300,12 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
                                   float(ang[1] - ang[0]) if ang.size > 1 else 0.0,
                                   float(stream['mbes_range_max']) if 'mbes_range_max' in stream else 100.0)
             pf.mbes_cb(scan)
+        while next_fix < len(fixes) and fixes[next_fix][0] <= stream['stamp'][k]:
+            f = msgs.Odometry()
+            f.header = msgs.Header(pf.map_frame, msgs.Time(fixes[next_fix][1]))
+            f.pose.pose.position.x, f.pose.pose.position.y = fixes[next_fix][2], fixes[next_fix][3]
+            pf.fix_cb(f)
+            next_fix += 1
         if (k + 1) % publish_every == 0 or k == n - 1:
             pf.loc_loop(None)
             p = tr.odom_corrected[-1].pose.pose.position
@@ -278,6 +315,9 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
                 stats.add(2, stream['stamp'][k], [p.x, p.y, p.z])
     pf_xyz = np.array(pf_xyz)
     summary = {}
+    if fix_period > 0:
+        summary['fixes_applied'], summary['fixes_dropped'] = int(pf.fixes_applied), int(pf.fixes_dropped)
+        summary['fix_mean_lag'] = float(pf.fix_lag_sum / pf.fixes_applied) if pf.fixes_applied else 0.0
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -487,9 +527,22 @@ def main(argv=None):
     ap.add_argument('--smooth', type=int, default=0, metavar='LAG',
                     help='also emit the fixed-lag smoothed track: every resampled ping as the LAG pings after it correct it '
                          '(particle genealogy, include/mcl_history.h); --out then writes it next to the filtered track')
+    ap.add_argument('--fix-period', type=float, default=0.0, metavar='S',
+                    help='make an acoustic position fix from the truth track every S seconds (a stream with truth_xyz)')
+    ap.add_argument('--fix-latency', type=float, default=0.0, metavar='S', help='deliver each fix S seconds after its stamp')
+    ap.add_argument('--fix-std', type=float, default=1.0, metavar='M', help='noise of the fixes and the std the node gives them')
+    ap.add_argument('--fix-history-depth', type=int, default=0, metavar='N',
+                    help='the node keeps N frames of the particles\' past and applies each fix at its stamp '
+                         '(include/mcl_acoustic.h); 0: to the cloud as it is when the fix arrives')
     a = ap.parse_args(argv)
     if a.smooth < 0 or a.smooth >= 1024:
         ap.error('--smooth: LAG must be 0 ... 1023')
+    if a.fix_period > 0 and a.smooth > 0:
+        ap.error(FIX_SMOOTH_CLASH)
+    if a.fix_period > 0 and (a.bag or a.recover):
+        ap.error('--fix-period: only with the plain stream replay')
+    if a.fix_period < 0 or a.fix_latency < 0 or not a.fix_std > 0 or not 0 <= a.fix_history_depth <= 1024:
+        ap.error('--fix-period / --fix-latency >= 0, --fix-std > 0, --fix-history-depth 0 ... 1024')
     if a.bag:
         grid = dict(np.load(a.map_grid)) if a.map_grid else None
         res = replay_bag(a.stream, dict(particle_count=a.particles, seed=a.seed), grid=grid, odom_topic=a.odom_topic,
@@ -516,7 +569,12 @@ def main(argv=None):
             save_smooth(a.out, res)
         print(json.dumps(res['summary']))
         return
-    res = replay(stream, dict(particle_count=a.particles, seed=a.seed), m2o=m2o, grid=grid, smooth_lag=a.smooth)
+    params = dict(particle_count=a.particles, seed=a.seed)
+    if a.fix_period > 0:
+        params.update(fix_topic='/sam/external/uw_gps_odom', fix_std=a.fix_std, fix_history_depth=a.fix_history_depth,
+                      fix_max_age=max(10.0, 2.0 * a.fix_latency))
+    res = replay(stream, params, m2o=m2o, grid=grid, smooth_lag=a.smooth, fix_period=a.fix_period,
+                 fix_latency=a.fix_latency, fix_seed=a.seed)
     if a.out:
         np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz']]), delimiter=',', header='step,x,y,z')
         save_smooth(a.out, res)

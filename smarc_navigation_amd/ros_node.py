@@ -4,7 +4,9 @@ auv_particle_filter/scripts/auv_pf.py; the numerics run in libm
 `~map_grid_file` / `~map_mesh_file` load the bathymetric map, `~mbes_topic` (sensor_msgs/LaserScan) and
 `~mbes_pointcloud_topic` (sensor_msgs/PointCloud2, the form mbes_mapper's receptor gives a ping) feed the MBES update;
 `~landmark_map_file` + `~lm_detect_topic` (geometry_msgs/PoseArray, toy_mbes_receptor.cpp:68-110) the landmark k-NN
-update of BASELINE config 5; `~dvl_topic` (smarc_msgs/DVL) the DVL altitude as a range against the map.
+update of BASELINE config 5; `~dvl_topic` (smarc_msgs/DVL) the DVL altitude as a range against the map; `~fix_topic`
+(nav_msgs/Odometry) delayed acoustic position fixes, evaluated against the particles' recorded past
+(`~fix_history_depth`).
 
 ROS is not installed in the build container: the module imports whatever `rospy` / `tf` / `tf2_ros` / `*_msgs` are on
 the path -- a ROS 1 installation, or the stand-ins of tests/ros_stubs that tests/test_ros_node_stub.py drives main()
@@ -118,6 +120,8 @@ def main():
     if params['dvl_topic']:   # DVL altitude against the map (smarc_msgs is needed only then)
         from smarc_msgs.msg import DVL
         rospy.Subscriber(params['dvl_topic'], DVL, pf.dvl_cb, queue_size=10)
+    if params['fix_topic']:   # acoustic position fixes (uw_gps_node.py publishes nav_msgs/Odometry)
+        rospy.Subscriber(params['fix_topic'], Odometry, pf.fix_cb, queue_size=10)
     rospy.Subscriber(params['odom_topic'], Odometry, pf.odom_callback, queue_size=100)
     rospy.Timer(rospy.Duration(0.1), pf.loc_loop)
     rospy.loginfo("Particle filter class successfully created")
