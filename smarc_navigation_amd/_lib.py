@@ -1,5 +1,5 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
-mcl_history.h and mcl_acoustic.h).
+mcl_history.h, mcl_acoustic.h and mcl_temper.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -76,6 +76,12 @@ class HistoryEst(C.Structure):
     """mcl_history_est (include/mcl_history.h)"""
     _fields_ = [('stamp', C.c_double), ('n_unique', C.c_int64), ('x', C.c_double), ('y', C.c_double), ('yaw', C.c_double),
                 ('yaw_R', C.c_double), ('cov_xy', C.c_double * 3)]
+
+
+class TemperRes(C.Structure):
+    """mcl_temper_result (include/mcl_temper.h)"""
+    _fields_ = [('j', C.c_int32), ('floor_hit', C.c_int32), ('levels_evaluated', C.c_int32), ('reserved', C.c_int32),
+                ('n_target', C.c_int64), ('n_live', C.c_int64), ('beta', C.c_double), ('max_lw', C.c_double)]
 
 
 # every symbol include/mcl.h, mcl_dr.h and mcl_map.h declare: name -> (restype, argtypes)
@@ -196,6 +202,17 @@ ACOUSTIC_SYMBOLS = {
     'mcl_history_bracket': (C.c_int, [_vp, _i32, _d, C.POINTER(_i32), C.POINTER(_d), C.POINTER(_i32)]),
 }
 
+# include/mcl_temper.h: ESS-targeted likelihood tempering
+TEMPER_SYMBOLS = {
+    'mcl_temper_beta': (C.c_int, [_i32, C.POINTER(_d)]),
+    'mcl_temper_pass': (C.c_int, [C.c_uint64, C.c_uint64, _i64, C.POINTER(_i32)]),
+    'mcl_temper_candidates': (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    'mcl_temper': (C.c_int, [_vp, _i64, _i32, C.POINTER(TemperRes)]),
+    'mcl_temper_sums': (C.c_int, [_vp, _d, _vp, _i32, _vp, _vp]),
+    'mcl_temper_apply': (C.c_int, [_vp, _i32]),
+    'mcl_group_temper': (C.c_int, [C.POINTER(_vp), _i32, _i64, _i32, C.POINTER(TemperRes)]),
+}
+
 _lib = None
 
 
@@ -209,7 +226,8 @@ def load():
                           '__graft_entry__.build()' % SO_PATH)
     lib = C.CDLL(SO_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()) +
-                              list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items())):
+                              list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items()) +
+                              list(TEMPER_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -85,6 +85,11 @@ DEFAULT_PARAMS = {
     # Frames come with the resamplings; where nothing resamples for fix_max_age / fix_history_depth seconds the node
     # records one on its own, so the ring spans fix_max_age.
     'fix_topic': '', 'fix_std': 1.0, 'fix_history_depth': 0, 'fix_max_age': 10.0,
+    # ESS-targeted likelihood tempering (include/mcl_temper.h): > 0: before EVERY resampling (GPS, MBES, DVL, landmarks,
+    # fix) the pending likelihood is raised to the largest power beta <= 1 of the library's lattice that leaves an
+    # effective sample size of at least this fraction of the cloud; a ping that leaves more is not touched (beta = 1).
+    # 0 = off: the call is never made and the node computes what it computed without the parameter.
+    'temper_ess_ratio': 0.0,
 }
 
 
@@ -308,6 +313,14 @@ class auv_pf(object):
         self._fix_last_record = None   # stamp of the ring's newest frame (None: the ring is empty)
         if self.fix_history_depth > 0:
             self.particles.history_enable(self.fix_history_depth)
+        # likelihood tempering
+        self.temper_ess_ratio = float(p['temper_ess_ratio'])
+        if not 0.0 <= self.temper_ess_ratio <= 1.0:
+            raise ValueError('temper_ess_ratio must lie in [0, 1], not %r' % self.temper_ess_ratio)
+        self.temper_last_beta = 1.0     # beta of the last resampling (1: not tempered)
+        self.temper_last = None         # its TemperResult
+        self.tempered_updates = 0       # resamplings whose likelihood was tempered (beta < 1)
+        self.temper_betas = []          # beta of every resampling since the start, in order
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
@@ -359,6 +372,13 @@ class auv_pf(object):
         return self.particles  # the weights stay in HBM; resample() consumes them there
 
     def resample(self, weights):
+        if self.temper_ess_ratio > 0.0:
+            # the one seam every update goes through: temper what it left, then resample
+            self.temper_last = self.particles.temper(self.temper_ess_ratio)
+            self.temper_last_beta = self.temper_last.beta
+            self.temper_betas.append(self.temper_last.beta)
+            if self.temper_last.j > 0:
+                self.tempered_updates += 1
         if self._replay is not None:
             need = self.particles.resample_prepare()
             u = self._replay.random_sample(need) if need != 1 else self._replay.random_sample()

@@ -11,6 +11,7 @@
 #include "mcl_host_step.h"
 #include "mcl_host_history.h"
 #include "mcl_host_acoustic.h"
+#include "mcl_host_temper.h"
 // global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
 #include "mcl_recovery.h"
 // (the kernels of mcl_pose_modes, include/mcl_modes.h, come with mcl_host.h: csrc/mcl_modes.h)
@@ -1305,6 +1306,37 @@ int mcl_update_beacon_ranges(mcl_handle* h, const double* beacons_xyz, const dou
 int mcl_history_bracket(const double* stamps_newest_first, int32_t held, double stamp, int32_t* lag, double* frac,
                         int32_t* where) {
   return history_bracket_impl(stamps_newest_first, held, stamp, lag, frac, where);
+}
+
+// ---- ESS-targeted tempering (include/mcl_temper.h; host: mcl_host_temper.h, kernels: csrc/mcl_temper.h)
+int mcl_temper_beta(int32_t j, double* beta) { return temper_beta_impl(j, beta); }
+
+int mcl_temper_pass(uint64_t s1, uint64_t s2, int64_t n_target, int32_t* pass) { return temper_pass_impl(s1, s2, n_target, pass); }
+
+int mcl_temper_candidates(int32_t round, int32_t j_prev, int32_t cand[MCL_TEMPER_MAX_CAND], int32_t* n_cand) {
+  return temper_candidates_impl(round, j_prev, cand, n_cand);
+}
+
+int mcl_temper(mcl_handle* h, int64_t n_target, int32_t apply, mcl_temper_result* out) {
+  if (!h) return MCL_ERR_INVALID;
+  return temper_run(h, n_target, apply != 0, out);
+}
+
+int mcl_temper_sums(mcl_handle* h, double max_lw, const int32_t* levels, int32_t n_levels, uint64_t* s1, uint64_t* s2) {
+  if (!h) return MCL_ERR_INVALID;
+  return temper_sums(h, max_lw, levels, n_levels, s1, s2);
+}
+
+int mcl_temper_apply(mcl_handle* h, int32_t j) {
+  if (!h) return MCL_ERR_INVALID;
+  return temper_apply(h, j);
+}
+
+int mcl_group_temper(mcl_handle** shards, int32_t ns, int64_t n_target, int32_t apply, mcl_temper_result* out) {
+  if (!shards || ns < 1) return MCL_ERR_INVALID;
+  for (int s = 0; s < ns; ++s)
+    if (!shards[s]) return MCL_ERR_INVALID;
+  return group_temper_run(shards, ns, n_target, apply != 0, out);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

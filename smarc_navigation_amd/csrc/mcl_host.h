@@ -1,7 +1,7 @@
 // mcl_host.h -- host side of libmcl_hip.so, part 1: the handle (device buffers, streams, communicators, caches) and
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
-// mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h
+// mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -209,6 +209,7 @@ struct mcl_handle {
   double map_xy[4] = {0, 0, 0, 0};  // footprint of the map (x_min, x_max, y_min, y_max; MAP frame), valid while map_kind >= 0
   DevBuf<double> wstats_dev;   // weight statistics: WS_OUT_WORDS result words, then one 32-byte record per tile (lazily)
   DevBuf<u64> inject_cnt;      // injection: the replaced-particle total, then one count per workgroup (lazily)
+  DevBuf<u64> temper_dev;      // tempering (include/mcl_temper.h): the state block of csrc/mcl_temper.h, TP_WORDS (lazily)
   // dominant modes (include/mcl_modes.h; all lazily)
   bool have_state = false;     // the particles were initialised (either init call, mcl_set_particles)
   DevBuf<u32> modes_hist;      // H: particles per cell of the caller's lattice

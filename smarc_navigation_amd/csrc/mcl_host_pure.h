@@ -2,7 +2,8 @@
 // quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
 // weight statistics, and the safety bounds kernels rely on unchecked (steepest patch gradient of a height grid, landmark
 // gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes, the bytes of
-// mcl_history_enable, the pose arguments of the acoustic updates and mcl_history_bracket).  No HIP header: the
+// mcl_history_enable, the pose arguments of the acoustic updates and mcl_history_bracket), and the lattice, predicate
+// and round plan of mcl_temper (also run by its pick kernel: MCL_HD).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -17,6 +18,7 @@
 #include "../../include/mcl_modes.h"
 #include "../../include/mcl_history.h"
 #include "../../include/mcl_acoustic.h"
+#include "../../include/mcl_temper.h"
 
 namespace {
 
@@ -334,6 +336,120 @@ int normalise_beams(const float* dirs, const float* ranges, int B, float* out) {
     out[4 * b + 2] = (float)(z / nrm);
     out[4 * b + 3] = ranges ? ranges[b] : 0.f;
   }
+  return MCL_OK;
+}
+
+// ---- ESS-targeted tempering (include/mcl_temper.h): the exponent lattice, the pass predicate and the round plan.  The
+// pick kernel (csrc/mcl_temper.h) runs these very functions on the device: one statement of each rule.
+#if defined(__HIPCC__)
+#define MCL_HD __host__ __device__
+#else
+#define MCL_HD
+#endif
+// beta_j = T[j mod 64] 2^-(j div 64), T[i] = the correctly rounded double of 2^(-i / 64), written with the 17 digits
+// that name one double (no hexadecimal literals: `make host-asan` compiles this file as C++14); 0 <= j <= 2048 (unchecked)
+MCL_HD inline double temper_beta(int j) {
+  constexpr double T[64] = {
+      1, 0.98922801319397546, 0.97857206208770009, 0.96803089674614717,
+      0.9576032806985737, 0.9472879907934828, 0.93708381705514998, 0.92698956254169274,
+      0.91700404320467122, 0.90712608775019943, 0.89735453750155358, 0.88768824626326059,
+      0.87812608018664973, 0.86866691763685311, 0.85930964906123897, 0.85005317685926174,
+      0.8408964152537145, 0.83183829016336819, 0.82287773907698247, 0.81401371092867392,
+      0.80524516597462714, 0.7965710756711335, 0.78799042255394325, 0.77950220011891846,
+      0.77110541270397037, 0.76279907537226921, 0.75458221379671142, 0.74645386414563242,
+      0.73841307296974967, 0.73045889709032352, 0.72259040348852333, 0.71480666919598501,
+      0.70710678118654757, 0.69948983626915562, 0.69195494098191601, 0.68450121148729526,
+      0.67712777346844633, 0.66983376202665146, 0.66261832157987066, 0.65548060576238221,
+      0.64841977732550482, 0.64143500803938913, 0.63452547859586661, 0.62769037851234555,
+      0.620928906036742, 0.61424026805343501, 0.60762367999023448, 0.60107836572635154,
+      0.59460355750136051, 0.58819849582514061, 0.58186242938878874, 0.57559461497649134,
+      0.56939431737834578, 0.56326080930412092, 0.55719337129794622, 0.55119129165392045,
+      0.54525386633262884, 0.53938039887855993, 0.53357020033841185, 0.52782258918027858,
+      0.52213689121370688, 0.51651243951061421, 0.51094857432705831, 0.50544464302585024};
+  // (T[i] in (1/2, 1] and j div 64 <= 32: the product with a power of two >= 2^-32 is exact)
+  return T[j & 63] * (1.0 / (double)(1ull << (j >> 6)));
+}
+// s1^2 >= n_t s2 2^32 in 128 bits, for every s1, s2 and n_t >= 1: a right side of 2^128 or more cannot pass
+MCL_HD inline bool temper_pass(unsigned long long s1, unsigned long long s2, unsigned long long n_t) {
+  typedef unsigned __int128 u128;
+  const u128 lhs = (u128)s1 * s1;
+  const u128 p = (u128)n_t * s2;
+  if ((unsigned long long)(p >> 96) != 0ull) return false;
+  return lhs >= (p << 32);
+}
+// the candidates of a round (include/mcl_temper.h) are base + step k, k < count; count -1: bad argument
+struct TemperPlan {
+  int base, step, count;
+};
+MCL_HD inline TemperPlan temper_plan(int round, int j_prev) {
+  const TemperPlan bad = {0, 0, -1}, none = {0, 0, 0};
+  if (round == 1) return TemperPlan{0, 128, 17};
+  if (j_prev < 0 || j_prev > MCL_TEMPER_LEVELS) return bad;
+  if (round == 2) return j_prev % 128 != 0 ? bad : (j_prev == 0 ? none : TemperPlan{j_prev - 120, 8, 15});
+  if (round == 3) return j_prev % 8 != 0 ? bad : (j_prev == 0 ? none : TemperPlan{j_prev - 7, 1, 7});
+  return bad;
+}
+// what a round's outcome means: first = the level of its first passing candidate (-1: none passed)
+struct TemperStep {
+  int j, done, floor_hit;
+};
+MCL_HD inline TemperStep temper_next(int round, int j_prev, int first) {
+  TemperStep r;
+  r.floor_hit = 0;
+  if (round == 1) {
+    r.j = first < 0 ? MCL_TEMPER_LEVELS : first;
+    r.floor_hit = first < 0 ? 1 : 0;
+    r.done = (first < 0 || r.j == 0) ? 1 : 0;
+  } else {
+    r.j = first < 0 ? j_prev : first;
+    r.done = round == 3 ? 1 : 0;
+  }
+  return r;
+}
+int temper_beta_impl(int32_t j, double* beta) {
+  if (!beta || j < 0 || j > MCL_TEMPER_LEVELS) return MCL_ERR_INVALID;
+  *beta = temper_beta(j);
+  return MCL_OK;
+}
+int temper_pass_impl(uint64_t s1, uint64_t s2, int64_t n_target, int32_t* pass) {
+  if (!pass || n_target < 1) return MCL_ERR_INVALID;
+  *pass = temper_pass(s1, s2, (unsigned long long)n_target) ? 1 : 0;
+  return MCL_OK;
+}
+int temper_candidates_impl(int32_t round, int32_t j_prev, int32_t* cand, int32_t* n_cand) {
+  if (!cand || !n_cand) return MCL_ERR_INVALID;
+  const TemperPlan p = temper_plan(round, j_prev);
+  if (p.count < 0) return MCL_ERR_INVALID;
+  for (int k = 0; k < p.count; ++k) cand[k] = p.base + p.step * k;
+  *n_cand = p.count;
+  return MCL_OK;
+}
+// the search over sums somebody else forms (mcl_group_temper): sums(cand, nc, s1, s2) fills the CLOUD's sums at the
+// candidates; the rounds, the first pass and temper_next exactly as the pick kernel runs them
+template <class Sums>
+int temper_search(long long n_target, Sums&& sums, int* j_out, int* floor_hit, int* levels) {
+  int j = 0;
+  *levels = 0;
+  *floor_hit = 0;
+  for (int round = 1; round <= 3; ++round) {
+    const TemperPlan p = temper_plan(round, j);
+    int32_t cand[MCL_TEMPER_MAX_CAND];
+    uint64_t s1[MCL_TEMPER_MAX_CAND], s2[MCL_TEMPER_MAX_CAND];
+    for (int k = 0; k < p.count; ++k) cand[k] = p.base + p.step * k;
+    if (p.count > 0) {
+      const int rc = sums(cand, p.count, s1, s2);
+      if (rc != MCL_OK) return rc;
+    }
+    int first = -1;
+    for (int k = p.count - 1; k >= 0; --k)
+      if (temper_pass(s1[k], s2[k], (unsigned long long)n_target)) first = cand[k];
+    const TemperStep st = temper_next(round, j, first);
+    j = st.j;
+    *levels += p.count;
+    *floor_hit |= st.floor_hit;
+    if (st.done) break;
+  }
+  *j_out = j;
   return MCL_OK;
 }
 

@@ -89,6 +89,32 @@ class HistoryEstimate(object):
         return d
 
 
+@dataclasses.dataclass
+class TemperResult(object):
+    """mcl_temper_result as a Python object (include/mcl_temper.h): the level j of the exponent lattice, beta = 2^(-j / 64),
+    the target count, whether not even the floor reached it, finite log-weights, their maximum, candidates evaluated"""
+    j: int
+    beta: float
+    n_target: int
+    floor_hit: bool
+    n_live: int
+    max_lw: float
+    levels_evaluated: int
+
+    @staticmethod
+    def from_c(c):
+        return TemperResult(int(c.j), float(c.beta), int(c.n_target), bool(c.floor_hit), int(c.n_live), float(c.max_lw),
+                            int(c.levels_evaluated))
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+
+def temper_target(ess_ratio, n_global):
+    """n_target of an effective-sample-size ratio: ceil(ratio n_global), at least 1"""
+    return max(1, int(math.ceil(float(ess_ratio) * int(n_global))))
+
+
 def make_mode_grid(x0, y0, cell, nx, ny, n_yaw):
     g = _lib.ModeGrid()
     g.x0, g.y0, g.cell = float(x0), float(y0), float(cell)
@@ -333,6 +359,28 @@ class Engine(object):
         between two frames, +1: not older than the newest, -1: not newer than the oldest.  MclError without a frame."""
         return history_bracket(self.history_frames()[2], stamp)
 
+    # ---- ESS-targeted likelihood tempering (include/mcl_temper.h)
+    def temper(self, ess_ratio=0.5, apply=True, n_target=None, wait=True):
+        """raise the pending likelihood to the largest power beta = 2^(-j / 64) <= 1 that leaves an effective sample size of
+        at least n_target = ceil(ess_ratio n_global) (or n_target itself when given); apply=True scales the log-weights.
+        Returns a TemperResult, or None with wait=False (the call then does not wait for the GPU).  mcl_temper."""
+        nt = temper_target(ess_ratio, self.n_global) if n_target is None else int(n_target)
+        c = _lib.TemperRes()
+        self._ck(self.lib.mcl_temper(self.h, nt, 1 if apply else 0, C.byref(c) if wait else None))
+        return TemperResult.from_c(c) if wait else None
+
+    def temper_sums(self, max_lw, levels):
+        """(S1, S2): this shard's integer sums at the levels (at most 17) relative to the CLOUD's maximum max_lw, as lists of
+        Python integers (mcl_temper_sums)"""
+        lv = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        s1, s2 = np.zeros(max(lv.size, 1), np.uint64), np.zeros(max(lv.size, 1), np.uint64)
+        self._ck(self.lib.mcl_temper_sums(self.h, float(max_lw), _ptr(lv), lv.size, _ptr(s1), _ptr(s2)))
+        return [int(v) for v in s1[:lv.size]], [int(v) for v in s2[:lv.size]]
+
+    def temper_apply(self, j):
+        """lw <- beta_j lw on this shard (mcl_temper_apply); j = 0 changes nothing"""
+        self._ck(self.lib.mcl_temper_apply(self.h, int(j)))
+
     def predict(self, v, wz, q, z, dt, normals=None, stamp=0.0):
         nz = _f64(normals)
         od = make_odom(v, wz, q, z, stamp)
@@ -570,6 +618,39 @@ def history_bracket(stamps_newest_first, stamp):
     lag, frac, where = C.c_int32(0), C.c_double(0.0), C.c_int32(0)
     _lib.check(lib.mcl_history_bracket(_ptr(s), s.size, float(stamp), C.byref(lag), C.byref(frac), C.byref(where)))
     return int(lag.value), float(frac.value), int(where.value)
+
+
+def temper_beta(j):
+    """beta_j = 2^(-j / 64) of the tempering lattice, 0 <= j <= 2048 (mcl_temper_beta: host arithmetic)"""
+    b = C.c_double(0.0)
+    _lib.check(_lib.load().mcl_temper_beta(int(j), C.byref(b)))
+    return float(b.value)
+
+
+def temper_pass(s1, s2, n_target):
+    """s1^2 >= n_target s2 2^32 in 128-bit integers (mcl_temper_pass: host arithmetic)"""
+    p = C.c_int32(0)
+    _lib.check(_lib.load().mcl_temper_pass(int(s1), int(s2), int(n_target), C.byref(p)))
+    return bool(p.value)
+
+
+def temper_candidates(round_, j_prev=0):
+    """the candidate levels of a round of the search, ascending (mcl_temper_candidates: host arithmetic)"""
+    cand, nc = (C.c_int32 * 17)(), C.c_int32(0)
+    _lib.check(_lib.load().mcl_temper_candidates(int(round_), int(j_prev), cand, C.byref(nc)))
+    return [int(cand[k]) for k in range(nc.value)]
+
+
+def group_temper(engines, ess_ratio=0.5, apply=True, n_target=None):
+    """Engine.temper over shards that together hold the cloud (mcl_group_temper): n_global = the sum of their sizes; level
+    and log-weights equal the unsharded call's bit for bit.  Returns a TemperResult."""
+    lib = _lib.load()
+    ns = len(engines)
+    hs = (C.c_void_p * ns)(*[e.h for e in engines])
+    nt = temper_target(ess_ratio, sum(e.n for e in engines)) if n_target is None else int(n_target)
+    c = _lib.TemperRes()
+    _lib.check(lib.mcl_group_temper(hs, ns, nt, 1 if apply else 0, C.byref(c)), engines[0].h)
+    return TemperResult.from_c(c)
 
 
 def merge_weight_stats(parts):

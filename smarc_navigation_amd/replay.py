@@ -318,6 +318,13 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
     if fix_period > 0:
         summary['fixes_applied'], summary['fixes_dropped'] = int(pf.fixes_applied), int(pf.fixes_dropped)
         summary['fix_mean_lag'] = float(pf.fix_lag_sum / pf.fixes_applied) if pf.fixes_applied else 0.0
+    if pf.temper_ess_ratio > 0.0:
+        # likelihood tempering (include/mcl_temper.h): the exponents the resamplings of this run were given
+        b = pf.temper_betas
+        summary['temper_ess_ratio'], summary['temper_resamplings'] = float(pf.temper_ess_ratio), int(len(b))
+        summary['tempered_updates'] = int(pf.tempered_updates)
+        summary['temper_beta_mean'] = float(np.mean(b)) if b else 1.0
+        summary['temper_beta_min'] = float(np.min(b)) if b else 1.0
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -534,7 +541,15 @@ def main(argv=None):
     ap.add_argument('--fix-history-depth', type=int, default=0, metavar='N',
                     help='the node keeps N frames of the particles\' past and applies each fix at its stamp '
                          '(include/mcl_acoustic.h); 0: to the cloud as it is when the fix arrives')
+    ap.add_argument('--temper-ess', type=float, default=0.0, metavar='RATIO',
+                    help='temper every likelihood to an effective sample size of at least RATIO x particles before its '
+                         'resampling (the node\'s temper_ess_ratio, include/mcl_temper.h); the summary reports the mean and '
+                         'the minimum exponent; 0: off')
     a = ap.parse_args(argv)
+    if not 0.0 <= a.temper_ess <= 1.0:
+        ap.error('--temper-ess: RATIO must lie in [0, 1]')
+    if a.temper_ess > 0 and (a.bag or a.recover):
+        ap.error('--temper-ess: only with the plain stream replay')
     if a.smooth < 0 or a.smooth >= 1024:
         ap.error('--smooth: LAG must be 0 ... 1023')
     if a.fix_period > 0 and a.smooth > 0:
@@ -570,6 +585,8 @@ def main(argv=None):
         print(json.dumps(res['summary']))
         return
     params = dict(particle_count=a.particles, seed=a.seed)
+    if a.temper_ess > 0:
+        params.update(temper_ess_ratio=a.temper_ess)
     if a.fix_period > 0:
         params.update(fix_topic='/sam/external/uw_gps_odom', fix_std=a.fix_std, fix_history_depth=a.fix_history_depth,
                       fix_max_age=max(10.0, 2.0 * a.fix_latency))
