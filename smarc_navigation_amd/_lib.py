@@ -1,5 +1,5 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
-mcl_history.h, mcl_acoustic.h and mcl_temper.h).
+mcl_history.h, mcl_acoustic.h, mcl_temper.h and mcl_drift.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -76,6 +76,11 @@ class HistoryEst(C.Structure):
     """mcl_history_est (include/mcl_history.h)"""
     _fields_ = [('stamp', C.c_double), ('n_unique', C.c_int64), ('x', C.c_double), ('y', C.c_double), ('yaw', C.c_double),
                 ('yaw_R', C.c_double), ('cov_xy', C.c_double * 3)]
+
+
+class DriftConfig(C.Structure):
+    """mcl_drift_config (include/mcl_drift.h)"""
+    _fields_ = [('init_std', C.c_double * 3), ('walk_std', C.c_double * 3)]
 
 
 class TemperRes(C.Structure):
@@ -213,6 +218,19 @@ TEMPER_SYMBOLS = {
     'mcl_group_temper': (C.c_int, [C.POINTER(_vp), _i32, _i64, _i32, C.POINTER(TemperRes)]),
 }
 
+# include/mcl_drift.h: per-particle drift states (water current, yaw-rate bias)
+DRIFT_SYMBOLS = {
+    'mcl_drift_bytes': (C.c_int, [_i64, C.POINTER(C.c_int64)]),
+    'mcl_drift_config_check': (C.c_int, [C.POINTER(DriftConfig), C.POINTER(C.c_char_p)]),
+    'mcl_drift_enable': (C.c_int, [_vp, C.POINTER(DriftConfig), _vp]),
+    'mcl_drift_reset': (C.c_int, [_vp, _vp]),
+    'mcl_drift_disable': (C.c_int, [_vp]),
+    'mcl_drift_advance': (C.c_int, [_vp, _d, _vp]),
+    'mcl_drift_get': (C.c_int, [_vp, _vp]),
+    'mcl_drift_set': (C.c_int, [_vp, _vp]),
+    'mcl_drift_mean_cov': (C.c_int, [_vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -227,7 +245,7 @@ def load():
     lib = C.CDLL(SO_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()) +
                               list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items()) +
-                              list(TEMPER_SYMBOLS.items())):
+                              list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -90,7 +90,21 @@ DEFAULT_PARAMS = {
     # effective sample size of at least this fraction of the cloud; a ping that leaves more is not touched (beta = 1).
     # 0 = off: the call is never made and the node computes what it computed without the parameter.
     'temper_ess_ratio': 0.0,
+    # Per-particle drift states (include/mcl_drift.h): true: every particle carries its own water current (cx, cy [m/s],
+    # odom_frame) and yaw-rate bias (bw [rad/s]), drawn from N(0, drift_init_std^2), random-walking with drift_walk_std per
+    # sqrt(second); every predict is preceded by drift_advance(dt), every resampling takes the drift along, and
+    # `drift_mean` / `drift_cov` are refreshed with the mean pose.  The two strings hold three numbers (cx, cy, bw) and
+    # are parsed like the covariance strings.  false = off: the call is never made and the node computes what it
+    # computed without the parameters.
+    'estimate_drift': False, 'drift_init_std': '[0.2, 0.2, 0.0]', 'drift_walk_std': '[0.005, 0.005, 0.0]',
 }
+
+
+def _as_bool(v):
+    """a ROS bool parameter: a bool, a number, or the strings roslaunch may leave ('true', 'False', '1')"""
+    if isinstance(v, str):
+        return v.strip().lower() in ('true', '1', 'yes', 'on')
+    return bool(v)
 
 
 def parse_cov_string(cov_string):
@@ -321,12 +335,33 @@ class auv_pf(object):
         self.temper_last = None         # its TemperResult
         self.tempered_updates = 0       # resamplings whose likelihood was tempered (beta < 1)
         self.temper_betas = []          # beta of every resampling since the start, in order
+        # per-particle drift states
+        self.estimate_drift = _as_bool(p['estimate_drift'])
+        self.drift_mean, self.drift_cov = np.zeros(3), np.zeros((3, 3))   # of (cx, cy, bw): refreshed by update_loc_pose
+        if self.estimate_drift:
+            self.drift_init_std = parse_cov_string(p['drift_init_std'])
+            self.drift_walk_std = parse_cov_string(p['drift_walk_std'])
+            if len(self.drift_init_std) != 3 or len(self.drift_walk_std) != 3:
+                raise ValueError('drift_init_std and drift_walk_std hold three numbers (cx, cy, bw)')
+            why = _engine.drift_config_check(self.drift_init_std, self.drift_walk_std)
+            if why:
+                raise ValueError('estimate_drift: ' + why)
+            if rng_mode == _engine.RNG_NATIVE:
+                self.particles.drift_enable(self.drift_init_std, self.drift_walk_std)
+        self._drift_enabled = self.estimate_drift and rng_mode == _engine.RNG_NATIVE
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
         self._replay = rs
         self.particles.init_particles(rs.randn(self.pc, 6))
         self._fix_last_record = None   # (a re-initialisation clears the ring: include/mcl_history.h)
+        if self.estimate_drift:
+            # (the drift does not follow a re-initialisation on its own: include/mcl_drift.h)
+            if self._drift_enabled:
+                self.particles.drift_reset(rs.randn(self.pc, 3))
+            else:
+                self.particles.drift_enable(self.drift_init_std, self.drift_walk_std, rs.randn(self.pc, 3))
+                self._drift_enabled = True
 
     def start_timing(self, stamp):
         """auv_pf.py:96-98: `Start timing now`."""
@@ -350,6 +385,9 @@ class auv_pf(object):
     def predict(self, odom_t):
         dt = self.time - self.old_time
         tw, po = odom_t.twist.twist, odom_t.pose.pose
+        if self.estimate_drift:
+            # the current and the rate bias move the particles before the odometry does (include/mcl_drift.h)
+            self.particles.drift_advance(dt, self._replay.randn(self.pc, 3) if self._replay is not None else None)
         nz = self._replay.randn(self.pc, 6) if self._replay is not None else None
         self.particles.predict([tw.linear.x, tw.linear.y, tw.linear.z], tw.angular.z,
                                [po.orientation.x, po.orientation.y, po.orientation.z, po.orientation.w],
@@ -589,6 +627,8 @@ class auv_pf(object):
     # ---- publishing, auv_pf.py:218-285
     def update_loc_pose(self, pose_list=None):
         mean, yaw, cov9 = self.particles.mean_cov()
+        if self.estimate_drift:
+            self.drift_mean, self.drift_cov = self.particles.drift_mean_cov()
         lp = self.loc_pose
         lp.pose.pose.position.x, lp.pose.pose.position.y, lp.pose.pose.position.z = mean[0], mean[1], mean[2]
         quat_t = quaternion_from_euler(mean[3], mean[4], yaw)

@@ -12,6 +12,7 @@
 #include "mcl_host_history.h"
 #include "mcl_host_acoustic.h"
 #include "mcl_host_temper.h"
+#include "mcl_host_drift.h"
 // global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
 #include "mcl_recovery.h"
 // (the kernels of mcl_pose_modes, include/mcl_modes.h, come with mcl_host.h: csrc/mcl_modes.h)
@@ -1337,6 +1338,85 @@ int mcl_group_temper(mcl_handle** shards, int32_t ns, int64_t n_target, int32_t 
   for (int s = 0; s < ns; ++s)
     if (!shards[s]) return MCL_ERR_INVALID;
   return group_temper_run(shards, ns, n_target, apply != 0, out);
+}
+
+// ---- per-particle drift states (include/mcl_drift.h; host: mcl_host_drift.h, kernels: csrc/mcl_drift.h)
+int mcl_drift_bytes(int64_t n, int64_t* bytes) { return drift_bytes_impl(n, bytes); }
+
+int mcl_drift_config_check(const mcl_drift_config* cfg, const char** reason) { return drift_config_check_impl(cfg, reason); }
+
+int mcl_drift_disable(mcl_handle* h) {
+  if (!h) return MCL_ERR_INVALID;
+  RET_IF(need_drift(h, "drift_disable"));
+  RET_IF(set_device(h));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // (an advance or a gather in flight still writes the buffers)
+  drift_free(h);
+  return MCL_OK;
+}
+
+int mcl_drift_enable(mcl_handle* h, const mcl_drift_config* cfg, const double* replay_normals) {
+  if (!h) return MCL_ERR_INVALID;
+  const char* why = nullptr;
+  if (drift_config_check_impl(cfg, &why) != MCL_OK) return fail(h, MCL_ERR_INVALID, std::string("drift_enable: ") + why);
+  if (h->drift_on) return fail(h, MCL_ERR_STATE, "drift_enable: already enabled (call mcl_drift_disable first)");
+  if (h->world > 1 || h->cfg.comm_mode != MCL_COMM_NONE || h->comm)
+    return fail(h, MCL_ERR_UNSUPPORTED, "drift_enable: a sharded cloud is not supported");
+  RET_IF(set_device(h));
+  h->drift_cfg = *cfg;
+  int rc = drift_alloc(h);
+  if (rc == MCL_OK) rc = drift_prior(h, replay_normals, "drift_enable");
+  if (rc != MCL_OK) {
+    const std::string keep = h->err;
+    (void)hipStreamSynchronize(h->stream);
+    drift_free(h);
+    h->err = keep;
+    return rc;
+  }
+  h->drift_on = true;
+  return MCL_OK;
+}
+
+int mcl_drift_reset(mcl_handle* h, const double* replay_normals) {
+  if (!h) return MCL_ERR_INVALID;
+  RET_IF(need_drift(h, "drift_reset"));
+  RET_IF(set_device(h));
+  return drift_prior(h, replay_normals, "drift_reset");
+}
+
+int mcl_drift_advance(mcl_handle* h, double dt, const double* replay_normals) {
+  if (!h) return MCL_ERR_INVALID;
+  RET_IF(need_drift(h, "drift_advance"));
+  if (!std::isfinite(dt)) return fail(h, MCL_ERR_INVALID, "drift_advance: dt is not finite");
+  if (!(dt > 0.0)) return MCL_OK;   // (the predict's gate: nothing moves, nothing is counted)
+  RET_IF(set_device(h));
+  return drift_advance(h, dt, replay_normals);
+}
+
+int mcl_drift_get(mcl_handle* h, double* soa3n) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!soa3n) return fail(h, MCL_ERR_INVALID, "drift_get: null argument");
+  RET_IF(need_drift(h, "drift_get"));
+  RET_IF(set_device(h));
+  HIPCHK(h, hipMemcpyAsync(soa3n, h->drift_state, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MCL_OK;
+}
+
+int mcl_drift_set(mcl_handle* h, const double* soa3n) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!soa3n) return fail(h, MCL_ERR_INVALID, "drift_set: null argument");
+  RET_IF(need_drift(h, "drift_set"));
+  RET_IF(set_device(h));
+  HIPCHK(h, hipMemcpyAsync(h->drift_state, soa3n, sizeof(double) * 3 * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MCL_OK;
+}
+
+int mcl_drift_mean_cov(mcl_handle* h, double mean3[3], double cov6[6]) {
+  if (!h) return MCL_ERR_INVALID;
+  RET_IF(need_drift(h, "drift_mean_cov"));
+  RET_IF(set_device(h));
+  return drift_mean_cov(h, mean3, cov6);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

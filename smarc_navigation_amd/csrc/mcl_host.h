@@ -1,7 +1,8 @@
 // mcl_host.h -- host side of libmcl_hip.so, part 1: the handle (device buffers, streams, communicators, caches) and
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
-// mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h
+// mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h,
+// mcl_host_drift.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +32,7 @@
 #include "mcl_ranges.h"
 #include "mcl_modes.h"
 #include "mcl_history.h"
+#include "mcl_drift.h"
 
 #define MEAN_RING 4096
 #define RING_STRIDE 20  // doubles per mean/cov result: 16 payload + [16] format tag
@@ -231,6 +233,13 @@ struct mcl_handle {
   DevBuf<double> hist_part;    // per-workgroup sums [HIST_SUMS][grid]
   DevBuf<double> hist_res;     // depth x HIST_RES_WORDS: the smoother's sums per lag (and the path's records)
   std::vector<double> hist_stamp;   // depth: the frames' stamps
+  // per-particle drift states (include/mcl_drift.h; all allocated by mcl_drift_enable, freed by mcl_drift_disable)
+  bool drift_on = false;
+  mcl_drift_config drift_cfg = {};
+  uint32_t drift_step = 0;     // advances since enable / reset: the Philox step of the last one (0: the prior's)
+  DevBuf<double> drift_state;  // 3 x n: cx, cy, bw
+  DevBuf<double> drift_part;   // per-workgroup sums [DRIFT_SUMS][grid]
+  DevBuf<double> drift_res;    // DRIFT_RES_WORDS: the summed moments, the shift
   bool timing = false;
   std::vector<TimedRegion> regions;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -478,6 +487,8 @@ int state_overwritten(mcl_handle* h) {
 // slot map -- and the clean start when the state is overwritten by an init call or mcl_set_particles
 int history_after_resample(mcl_handle* h, bool alt);
 void history_clear(mcl_handle* h);
+// per-particle drift (mcl_host_drift.h): d'[i] = d[A(i)] behind the same gather, by the same slot map
+int drift_after_resample(mcl_handle* h, bool alt);
 // The filter starts again from fresh particles (both init calls): the Philox steps count from 0, no weights, no CDF.
 void filter_restarted(mcl_handle* h) {
   h->step_predict = h->step_resample = h->step_inject = 0;

@@ -2,7 +2,8 @@
 // quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
 // weight statistics, and the safety bounds kernels rely on unchecked (steepest patch gradient of a height grid, landmark
 // gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes, the bytes of
-// mcl_history_enable, the pose arguments of the acoustic updates and mcl_history_bracket), and the lattice, predicate
+// mcl_history_enable and mcl_drift_enable, the stds of mcl_drift_config, the pose arguments of the acoustic updates and
+// mcl_history_bracket), and the lattice, predicate
 // and round plan of mcl_temper (also run by its pick kernel: MCL_HD).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
@@ -19,6 +20,7 @@
 #include "../../include/mcl_history.h"
 #include "../../include/mcl_acoustic.h"
 #include "../../include/mcl_temper.h"
+#include "../../include/mcl_drift.h"
 
 namespace {
 
@@ -283,6 +285,29 @@ int history_bytes_impl(int64_t n, int32_t depth, int64_t* bytes) {
   if (!bytes || n < 1 || n > 0x7fffffffll || depth < 1 || depth > MCL_HISTORY_MAX_DEPTH) return MCL_ERR_INVALID;
   *bytes = 28 * n * (int64_t)depth + 16 * n + 8 * HISTORY_RES_WORDS * (int64_t)depth + 8 * HISTORY_PART_WORDS;
   return MCL_OK;
+}
+
+// the device bytes mcl_drift_enable allocates (include/mcl_drift.h): three doubles per particle, DRIFT_PART_WORDS reduction
+// records and DRIFT_RESULT_WORDS result words (mcl_host_drift.h checks both constants against the kernels')
+constexpr int64_t DRIFT_RESULT_WORDS = 12, DRIFT_PART_WORDS = 9 * 2048;
+int drift_bytes_impl(int64_t n, int64_t* bytes) {
+  if (!bytes || n < 1 || n > 0x7fffffffll) return MCL_ERR_INVALID;
+  *bytes = 24 * n + 8 * DRIFT_PART_WORDS + 8 * DRIFT_RESULT_WORDS;
+  return MCL_OK;
+}
+// the stds of a drift configuration: every one finite and >= 0; *reason names the first that is not
+int drift_config_check_impl(const mcl_drift_config* cfg, const char** reason) {
+  static const char* const bad[6] = {"init_std[0] (cx) must be finite and >= 0", "init_std[1] (cy) must be finite and >= 0",
+                                     "init_std[2] (bw) must be finite and >= 0", "walk_std[0] (cx) must be finite and >= 0",
+                                     "walk_std[1] (cy) must be finite and >= 0", "walk_std[2] (bw) must be finite and >= 0"};
+  const char* why = nullptr;
+  if (!cfg) why = "null config";
+  for (int c = 0; c < 6 && !why; ++c) {
+    const double s = c < 3 ? cfg->init_std[c] : cfg->walk_std[c - 3];
+    if (!std::isfinite(s) || !(s >= 0.0)) why = bad[c];
+  }
+  if (reason) *reason = why;
+  return why ? MCL_ERR_INVALID : MCL_OK;
 }
 
 // the pose arguments the acoustic updates share (include/mcl_acoustic.h), as far as they need no handle: nullptr, or the

@@ -853,6 +853,7 @@ int run_resample_alt(mcl_handle* h, const double* uniforms, long long nu, const 
   HIPCHK(h, hipGetLastError());
   finish_resample(h, false);
   if (h->hist_on) RET_IF(history_after_resample(h, true));
+  if (h->drift_on) RET_IF(drift_after_resample(h, true));
   return MCL_OK;
 }
 
@@ -984,6 +985,7 @@ int run_resample(mcl_handle** sh, int ns, const double* uniforms, long long nu,
   }
   for (int s = 0; s < ns; ++s) RET_IF(phase_gather(sh[s], replay_normals_of(sh[s], replay_normals, s), p.with_moments));
   if (h0->hist_on) RET_IF(history_after_resample(h0, false));   // (single shard: mcl_history_enable refuses the others)
+  if (h0->drift_on) RET_IF(drift_after_resample(h0, false));    // (likewise mcl_drift_enable)
   return MCL_OK;
 }
 

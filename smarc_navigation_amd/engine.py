@@ -381,6 +381,55 @@ class Engine(object):
         """lw <- beta_j lw on this shard (mcl_temper_apply); j = 0 changes nothing"""
         self._ck(self.lib.mcl_temper_apply(self.h, int(j)))
 
+    # ---- per-particle drift states: water current and yaw-rate bias (include/mcl_drift.h)
+    def drift_bytes(self):
+        """device bytes drift_enable allocates on this handle (mcl_drift_bytes: host arithmetic)"""
+        return drift_bytes(self.n)
+
+    def _normals3(self, normals):
+        nz = _f64(normals)
+        if nz is not None and nz.size != 3 * self.n:
+            raise ValueError('drift: normals are n x 3, particle-major')
+        return nz
+
+    def drift_enable(self, init_std, walk_std, normals=None):
+        """give every particle its own (cx, cy [m/s, odom frame], bw [rad/s]) drawn from N(0, init_std^2), random-walking
+        with walk_std per sqrt(second); it follows its particle through every resample.  normals: n x 3 (REPLAY mode)."""
+        cfg, nz = make_drift_config(init_std, walk_std), self._normals3(normals)
+        self._ck(self.lib.mcl_drift_enable(self.h, C.byref(cfg), _ptr(nz)))
+
+    def drift_reset(self, normals=None):
+        """redraw the prior and restart the advance count (after re-initialising the filter)"""
+        nz = self._normals3(normals)
+        self._ck(self.lib.mcl_drift_reset(self.h, _ptr(nz)))
+
+    def drift_disable(self):
+        self._ck(self.lib.mcl_drift_disable(self.h))
+
+    def drift_advance(self, dt, normals=None):
+        """x, y += current dt, yaw += bias dt, then the drift's random walk: call it BEFORE the predict (or fused step) of
+        the same dt; dt <= 0 does nothing (asynchronous)"""
+        nz = self._normals3(normals)
+        self._ck(self.lib.mcl_drift_advance(self.h, float(dt), _ptr(nz)))
+
+    def drift_get(self):
+        """the drift, (3, n): rows cx, cy, bw"""
+        out = np.zeros((3, self.n))
+        self._ck(self.lib.mcl_drift_get(self.h, _ptr(out)))
+        return out
+
+    def drift_set(self, soa):
+        s = _f64(soa)
+        if s.shape != (3, self.n):
+            raise ValueError('drift_set: a (3, n) array')
+        self._ck(self.lib.mcl_drift_set(self.h, _ptr(s)))
+
+    def drift_mean_cov(self):
+        """(mean (3,), cov (3, 3)) of (cx, cy, bw) over the slots, every slot counting once: read it after a resample"""
+        mean, c = np.zeros(3), np.zeros(6)
+        self._ck(self.lib.mcl_drift_mean_cov(self.h, _ptr(mean), _ptr(c)))
+        return mean, np.array([[c[0], c[1], c[2]], [c[1], c[3], c[4]], [c[2], c[4], c[5]]])
+
     def predict(self, v, wz, q, z, dt, normals=None, stamp=0.0):
         nz = _f64(normals)
         od = make_odom(v, wz, q, z, stamp)
@@ -618,6 +667,30 @@ def history_bracket(stamps_newest_first, stamp):
     lag, frac, where = C.c_int32(0), C.c_double(0.0), C.c_int32(0)
     _lib.check(lib.mcl_history_bracket(_ptr(s), s.size, float(stamp), C.byref(lag), C.byref(frac), C.byref(where)))
     return int(lag.value), float(frac.value), int(where.value)
+
+
+def make_drift_config(init_std, walk_std):
+    cfg = _lib.DriftConfig()
+    for name, v in (('init_std', init_std), ('walk_std', walk_std)):
+        a = _f64(v).reshape(-1)
+        if a.size != 3:
+            raise ValueError('drift: %s is three numbers (cx, cy, bw)' % name)
+        getattr(cfg, name)[:] = [float(x) for x in a]
+    return cfg
+
+
+def drift_config_check(init_std, walk_std):
+    """None, or the sentence saying which std is negative or not finite (mcl_drift_config_check: no device)"""
+    cfg, why = make_drift_config(init_std, walk_std), C.c_char_p()
+    st = _lib.load().mcl_drift_config_check(C.byref(cfg), C.byref(why))
+    return None if st == 0 else (why.value or b'').decode()
+
+
+def drift_bytes(n):
+    """device bytes mcl_drift_enable allocates on a handle of n particles (mcl_drift_bytes: no device)"""
+    b = C.c_int64(0)
+    _lib.check(_lib.load().mcl_drift_bytes(int(n), C.byref(b)))
+    return int(b.value)
 
 
 def temper_beta(j):

@@ -241,6 +241,26 @@ def make_fixes(stream, m2o, period, latency, std, seed=0):
     return out
 
 
+# the node parameters a synthetic stream is replayed with (`synth[:N]`): the noise the stream was made with -- fixes of
+# 0.5 m, a tight start, little process noise and no resampling noise -- instead of the reference's launch defaults (a fix
+# of 1 cm and a metre of resampling noise, under which no drift can be told from the jitter)
+SYNTH_PARAMS = dict(measurement_std=0.5, init_covariance='[0.01, 0.01, 0.0, 0.0, 0.0, 0.0001]',
+                    motion_covariance='[0.0001, 0.0001, 0.0, 0.0, 0.0, 0.000001]',
+                    resampling_noise_covariance='[0.0, 0.0, 0.0, 0.0, 0.0, 0.0]')
+
+
+def synthetic_stream(n_steps=3000, current=(0.0, 0.0), yaw_rate_bias=0.0, gps_every=50, gps_sigma=0.5, seed=0):
+    """A stream made here instead of read from a file (`synth` / `synth:N` on the command line): synth.odom_stream with a
+    water current and a yaw-rate bias the odometry does not see, the truth track, and a GPS fix of gps_sigma metres every
+    gps_every samples (identity frames: utm = map = odom).  drift_truth = (cx, cy, bw) is what drift states should find."""
+    from . import synth
+    st = synth.odom_stream(int(n_steps), current=current, yaw_rate_bias=yaw_rate_bias)
+    idx, xy = synth.gps_fixes(st['truth'], np.identity(4), every=int(gps_every), sigma=float(gps_sigma), seed=int(seed) + 2)
+    st.update(truth_xyz=st['truth'][:, :3].copy(), gps_idx=idx, gps_xy_utm=xy,
+              drift_truth=np.array([float(current[0]), float(current[1]), float(yaw_rate_bias)]))
+    return st
+
+
 def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0,
            fix_period=0.0, fix_latency=0.0, fix_seed=0):
     """Drive the node with a recorded stream; returns dict(pf_xyz[n_pub,3], pub_idx, summary).  smooth_lag > 0: also
@@ -325,6 +345,14 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
         summary['tempered_updates'] = int(pf.tempered_updates)
         summary['temper_beta_mean'] = float(np.mean(b)) if b else 1.0
         summary['temper_beta_min'] = float(np.min(b)) if b else 1.0
+    if pf.estimate_drift:
+        # drift states (include/mcl_drift.h): the cloud's mean (cx, cy, bw) at the last published pose, and how far its
+        # current is from the one the stream was made with
+        summary['drift_mean'] = [float(x) for x in pf.drift_mean]
+        if 'drift_truth' in stream:
+            t = np.asarray(stream['drift_truth'], dtype=np.float64)
+            summary['drift_error'] = float(np.hypot(pf.drift_mean[0] - t[0], pf.drift_mean[1] - t[1]))
+            summary['drift_bias_error'] = float(abs(pf.drift_mean[2] - t[2]))
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -514,7 +542,8 @@ def save_smooth(out_path, res):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('stream')
+    ap.add_argument('stream', help='a stream file (npz), or synth[:N]: a synthetic stream of N samples (3000) with the truth '
+                                   'and a GPS fix of 0.5 m every second (synthetic_stream), replayed with SYNTH_PARAMS')
     ap.add_argument('--particles', type=int, default=4096)
     ap.add_argument('--map-grid', help='npz with z, origin, res')
     ap.add_argument('--out', help='CSV of the published mean pose')
@@ -545,7 +574,27 @@ def main(argv=None):
                     help='temper every likelihood to an effective sample size of at least RATIO x particles before its '
                          'resampling (the node\'s temper_ess_ratio, include/mcl_temper.h); the summary reports the mean and '
                          'the minimum exponent; 0: off')
+    ap.add_argument('--estimate-drift', action='store_true',
+                    help='every particle carries a water current and a yaw-rate bias (the node\'s estimate_drift, '
+                         'include/mcl_drift.h); the summary gains drift_mean, and drift_error against a synthetic stream')
+    ap.add_argument('--drift-init-std', type=float, nargs=3, default=None, metavar=('CX', 'CY', 'BW'),
+                    help='the prior\'s standard deviations [m/s, m/s, rad/s] (the node\'s drift_init_std)')
+    ap.add_argument('--drift-walk-std', type=float, nargs=3, default=None, metavar=('CX', 'CY', 'BW'),
+                    help='the random walk\'s, per sqrt(second) (the node\'s drift_walk_std)')
+    ap.add_argument('--current', type=float, nargs=2, default=(0.0, 0.0), metavar=('CX', 'CY'),
+                    help='synthetic streams: a water current [m/s, odom frame] the odometry does not see')
+    ap.add_argument('--yaw-rate-bias', type=float, default=0.0, metavar='B',
+                    help='synthetic streams: a yaw-rate bias [rad/s] the odometry does not see')
     a = ap.parse_args(argv)
+    synthetic = a.stream == 'synth' or a.stream.startswith('synth:')
+    if (tuple(a.current) != (0.0, 0.0) or a.yaw_rate_bias != 0.0) and not synthetic:
+        ap.error('--current / --yaw-rate-bias: only with a synthetic stream (synth[:N])')
+    if synthetic and (a.bag or a.raw or a.recover):
+        ap.error('synth[:N]: only with the plain stream replay')
+    if (a.estimate_drift or a.drift_init_std or a.drift_walk_std) and (a.bag or a.recover):
+        ap.error('--estimate-drift: only with the plain stream replay')
+    if (a.drift_init_std or a.drift_walk_std) and not a.estimate_drift:
+        ap.error('--drift-init-std / --drift-walk-std need --estimate-drift')
     if not 0.0 <= a.temper_ess <= 1.0:
         ap.error('--temper-ess: RATIO must lie in [0, 1]')
     if a.temper_ess > 0 and (a.bag or a.recover):
@@ -566,7 +615,10 @@ def main(argv=None):
             np.savetxt(a.out, np.column_stack([res['pf_stamp'], res['pf_xyz']]), delimiter=',', header='stamp,x,y,z')
         print(json.dumps(res['summary']))
         return
-    stream = dict(np.load(a.stream, allow_pickle=False))
+    if synthetic:
+        stream = synthetic_stream(int(a.stream[6:]) if a.stream[5:6] == ':' else 3000, a.current, a.yaw_rate_bias, seed=a.seed)
+    else:
+        stream = dict(np.load(a.stream, allow_pickle=False))
     m2o = None
     if a.raw:
         ptf = stream.get('pressure_tf')
@@ -585,8 +637,16 @@ def main(argv=None):
         print(json.dumps(res['summary']))
         return
     params = dict(particle_count=a.particles, seed=a.seed)
+    if synthetic:
+        params.update(SYNTH_PARAMS)
     if a.temper_ess > 0:
         params.update(temper_ess_ratio=a.temper_ess)
+    if a.estimate_drift:
+        params.update(estimate_drift=True)
+        if a.drift_init_std:
+            params.update(drift_init_std=str([float(x) for x in a.drift_init_std]))
+        if a.drift_walk_std:
+            params.update(drift_walk_std=str([float(x) for x in a.drift_walk_std]))
     if a.fix_period > 0:
         params.update(fix_topic='/sam/external/uw_gps_odom', fix_std=a.fix_std, fix_history_depth=a.fix_history_depth,
                       fix_max_age=max(10.0, 2.0 * a.fix_latency))

@@ -25,10 +25,17 @@ def wrap_pi(a):
     return (a + np.pi) % (2 * np.pi) - np.pi
 
 
-def odom_stream(n_steps=3000, dt=0.02, t0=100.0, x0=0.0, y0=0.0, yaw0=0.0, z_mean=-2.0):
+def odom_stream(n_steps=3000, dt=0.02, t0=100.0, x0=0.0, y0=0.0, yaw0=0.0, z_mean=-2.0, current=(0.0, 0.0),
+                yaw_rate_bias=0.0):
     """Lawn-mower-ish track.  Returns dict of arrays:
     stamp[n], v[n,3] (body frame), wz[n], q[n,4], z[n], rpy[n,3], truth[n,6] (pose in the
-    odom frame after integrating sample k with the noise-free motion model)."""
+    odom frame after integrating sample k with the noise-free motion model).
+    current (cx, cy [m/s], odom frame) and yaw_rate_bias [rad/s] are errors the odometry does not see: the truth's x, y
+    gain current * t, t = (k + 1) dt the time integrated up to sample k, and the truth turns with wz + yaw_rate_bias (so
+    its yaw gains yaw_rate_bias * t, and its path bends with it); v, wz, q, z, rpy are what they are without them.  With
+    the defaults nothing is added: every array is bit for bit the stream's without the keywords."""
+    current = (float(current[0]), float(current[1]))
+    yaw_rate_bias = float(yaw_rate_bias)
     k = np.arange(n_steps)
     t = k * dt
     stamp = t0 + (k + 1) * dt
@@ -42,17 +49,24 @@ def odom_stream(n_steps=3000, dt=0.02, t0=100.0, x0=0.0, y0=0.0, yaw0=0.0, z_mea
     z = z_mean - 0.5 * np.sin(0.05 * t)
     truth = np.zeros((n_steps, 6))
     x, y, yaw = x0, y0, yaw0
+    yaw_true = yaw0     # (only followed with a yaw-rate bias)
     dr_yaw = np.zeros(n_steps)
     for i in range(n_steps):
         yaw = float(wrap_pi(yaw + wz[i] * dt))
+        if yaw_rate_bias != 0.0:
+            yaw_true = float(wrap_pi(yaw_true + (wz[i] + yaw_rate_bias) * dt))
+        head = yaw_true if yaw_rate_bias != 0.0 else yaw
         cr, sr = math.cos(roll[i]), math.sin(roll[i])
         cp, sp = math.cos(pitch[i]), math.sin(pitch[i])
-        cy, sy = math.cos(yaw), math.sin(yaw)
+        cy, sy = math.cos(head), math.sin(head)
         vx, vy, vz = v[i] * dt
         x += cy * cp * vx + (cy * sp * sr - sy * cr) * vy + (cy * sp * cr + sy * sr) * vz
         y += sy * cp * vx + (sy * sp * sr + cy * cr) * vy + (sy * sp * cr - cy * sr) * vz
-        truth[i] = (x, y, z[i], roll[i], pitch[i], yaw)
+        truth[i] = (x, y, z[i], roll[i], pitch[i], head)
         dr_yaw[i] = yaw
+    if current != (0.0, 0.0):
+        truth[:, 0] += current[0] * ((k + 1) * dt)
+        truth[:, 1] += current[1] * ((k + 1) * dt)
     q = quat_from_rpy(roll, pitch, dr_yaw)
     return dict(stamp=stamp, dt=dt, t0=t0, v=v, wz=wz, q=q, z=z,
                 rpy=np.stack([roll, pitch, dr_yaw], axis=1), truth=truth)
