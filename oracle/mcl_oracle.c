@@ -392,35 +392,46 @@ void orc_reassign(int n, double* state, int n_lost, const int32_t* lost, const i
 }
 
 /* ------------------------------------------------------------------ a13 mean / cov */
+/* mean pose, mean wrapped yaw, covariance (auv_pf.py:218-252).  Where the reference's own arithmetic runs out of digits this
+ * departs from it, so that the oracle stays a usable yardstick for a centimetre-wide cloud at survey coordinates (the GPU's
+ * two-pass kernels take the same form; tests/test_moments_predict_reference.py holds both to the same bound):
+ *  - x, y, z are summed about particle 0 (the reference adds the coordinates themselves): a cloud of equal particles
+ *    has exactly that mean and exactly no covariance;
+ *  - every sum is numpy's pairwise one (ndarray.mean(axis=0) accumulates row by row, A.9: n roundings in a chain);
+ *  - auv_pf.py:238-245 centres on the fp64 mean, which is off the true mean by a rounding d of the coordinate's size,
+ *    so its sums carry d d' on top of the covariance: the first moments about that mean are summed too and taken out
+ *    (the corrected two-pass form).
+ * The results agree with the reference's to rounding wherever its form has digits to spare (golden fixtures: 1e-9). */
 void orc_mean_cov(int n, const double* state, double mean6[6], double* yaw_mean, double cov9[9]) {
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < n; ++i) /* ndarray.mean(axis=0): row-by-row accumulation (A.9) */
-    for (int c = 0; c < 6; ++c) acc[c] += ST(c, i);
-  for (int c = 0; c < 6; ++c) mean6[c] = acc[c] / (double)n;
-  double* wy = (double*)malloc(sizeof(double) * (size_t)n);
-  for (int i = 0; i < n; ++i) wy[i] = orc_wrap_pi(ST(5, i));
-  *yaw_mean = orc_numpy_pairwise_sum(wy, n, 1) / (double)n; /* np.mean of the column (auv_pf.py:231) */
-  free(wy);
-  double c00 = 0, c11 = 0, c22 = 0, c01 = 0, c02 = 0, c12 = 0;
-  for (int i = 0; i < n; ++i) {
-    double dx = ST(0, i) - mean6[0], dy = ST(1, i) - mean6[1], dz = ST(2, i) - mean6[2];
-    c00 += dx * dx;
-    c11 += dy * dy;
-    c22 += dz * dz;
-    c01 += dx * dy;
-    c02 += dx * dz;
-    c12 += dy * dz;
-  }
+  double* t = (double*)malloc(sizeof(double) * (size_t)n);
   const double N = (double)n;
-  cov9[0] = c00 / N;
-  cov9[1] = c01 / N;
-  cov9[2] = c02 / N;
-  cov9[3] = c01 / N; /* only [1,0] is mirrored (auv_pf.py:246) */
-  cov9[4] = c11 / N;
-  cov9[5] = c12 / N;
+  const double x0[6] = {ST(0, 0), ST(1, 0), ST(2, 0), 0.0, 0.0, 0.0};
+  for (int c = 0; c < 6; ++c) {
+    for (int i = 0; i < n; ++i) t[i] = ST(c, i) - x0[c];
+    mean6[c] = x0[c] + orc_numpy_pairwise_sum(t, n, 1) / N;
+  }
+  for (int i = 0; i < n; ++i) t[i] = orc_wrap_pi(ST(5, i));
+  *yaw_mean = orc_numpy_pairwise_sum(t, n, 1) / N; /* np.mean of the column (auv_pf.py:231) */
+  double e[3], cc[6];
+  for (int c = 0; c < 3; ++c) {
+    for (int i = 0; i < n; ++i) t[i] = ST(c, i) - mean6[c];
+    e[c] = orc_numpy_pairwise_sum(t, n, 1) / N;
+  }
+  static const int pa[6] = {0, 1, 2, 0, 0, 1}, pb[6] = {0, 1, 2, 1, 2, 2};
+  for (int k = 0; k < 6; ++k) {
+    for (int i = 0; i < n; ++i) t[i] = (ST(pa[k], i) - mean6[pa[k]]) * (ST(pb[k], i) - mean6[pb[k]]);
+    cc[k] = orc_numpy_pairwise_sum(t, n, 1) / N - e[pa[k]] * e[pb[k]];
+  }
+  free(t);
+  cov9[0] = cc[0];
+  cov9[1] = cc[3];
+  cov9[2] = cc[4];
+  cov9[3] = cc[3]; /* only [1,0] is mirrored (auv_pf.py:246) */
+  cov9[4] = cc[1];
+  cov9[5] = cc[5];
   cov9[6] = 0.0;
   cov9[7] = 0.0;
-  cov9[8] = c22 / N;
+  cov9[8] = cc[2];
 }
 
 /* ================================================================== fixed-point spec */

@@ -35,7 +35,7 @@
 #include "mcl_drift.h"
 
 #define MEAN_RING 4096
-#define RING_STRIDE 20  // doubles per mean/cov result: 16 payload + [16] format tag
+#define RING_STRIDE 20  // doubles per mean/cov result: 16 payload + [16] format tag + [17..19] the two-pass form's shift
 // control block layout (bytes)
 #define CTRL_SLOTS 0                       // MCL_MAX_SLOTS u64
 #define CTRL_WORK (8 * MCL_MAX_SLOTS)      // int: groups deferred by the fast MBES kernel
@@ -95,14 +95,14 @@ struct mcl_handle {
   DevBuf<u32> tile32;
   long long ntiles_loc = 0, ntiles_glob = 0;
   DevBuf<double> part;     // reduction partials [7][MCL_MAX_GRID]
-  DevBuf<double> scal;     // device scalars: [0] max lw, [8..14] sums7, [16..21] cov6
+  DevBuf<double> scal;     // device scalars: [0] max lw, [8..27] the two-pass ring entry (sums7, [15] sum ez, [16..21] cov6, [22..23] sum ex, ey, [24] tag 0, [25..27] shift), [32..47] the fused sums
   DevBuf<u64> totals;      // device, world entries (+1 scratch)
   DevBuf<int> idx;         // n (lazily)
   DevBuf<double> replay_dev;
   DevBuf<double> pose7;
   double* host_pin_dev = nullptr;  // device-side address of host_pin (kernels write results into the ring directly)
   MomentsDest moments_dest = MOMENTS_SCAL;   // of the last gather
-  PinBuf<double> host_pin;  // pinned ring: MEAN_RING entries of 16 doubles (sums7, pad, cov-sums6, pad2)
+  PinBuf<double> host_pin;  // pinned ring: MEAN_RING entries of RING_STRIDE doubles (run_mean_cov_async / k_resample_gather say what lies where)
   long long mean_count = 0;     // number of mean/cov results produced so far
   // MBES
   DevBuf<float2> beam_sc;

@@ -10,7 +10,9 @@ int phase_mean_partial(mcl_handle* h) {
   RET_IF(set_device(h));
   t_begin(h, MCL_K_MEAN_COV);
   const int g = grid_for(h->n);
-  k_mean_partial<<<g, MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, h->part);
+  // (a single shard shifts by its slot 0; the tail of the ring entry -- format tag, shift -- goes to scal[24..27])
+  const int shifted = (h->world == 1 && !h->comm) ? 1 : 0;
+  k_mean_partial<<<g, MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, shifted, h->part, h->scal + 24);
   k_sum_final<<<7, MCL_BLOCK, 0, h->stream>>>(h->part, g, h->scal + 8);
   t_end(h);
   HIPCHK(h, hipGetLastError());
@@ -20,9 +22,9 @@ int phase_cov_partial(mcl_handle* h) {
   RET_IF(set_device(h));
   t_begin(h, MCL_K_MEAN_COV);
   const int g = grid_for(h->n);
-  k_cov_partial<<<g, MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, h->scal + 8,
+  k_cov_partial<<<g, MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, h->scal + 8, h->scal + 24,
                                                 1.0 / (double)h->ng, h->part);
-  k_sum_final<<<6, MCL_BLOCK, 0, h->stream>>>(h->part, g, h->scal + 16);
+  k_sum_final<<<COV_PART_ROWS, MCL_BLOCK, 0, h->stream>>>(h->part, g, h->scal + 15);
   t_end(h);
   HIPCHK(h, hipGetLastError());
   return MCL_OK;
@@ -51,13 +53,16 @@ int run_mean_cov_async(mcl_handle** sh, int ns) {
   for (int s = 0; s < ns; ++s) RET_IF(phase_mean_partial(sh[s]));
   RET_IF(sum_over_shards(sh, ns, 8, 7));
   for (int s = 0; s < ns; ++s) RET_IF(phase_cov_partial(sh[s]));
-  RET_IF(sum_over_shards(sh, ns, 16, 6));
+  RET_IF(sum_over_shards(sh, ns, 15, COV_PART_ROWS));
   for (int s = 0; s < ns; ++s) {
     mcl_handle* h = sh[s];
     RET_IF(set_device(h));
     double* slot = h->host_pin + RING_STRIDE * (h->mean_count % MEAN_RING);
-    slot[16] = 0.0;  // format 0: [0..6] sums of the 6 components + wrapped yaw, [8..13] centred second-moment sums
-    HIPCHK(h, hipMemcpyAsync(slot, h->scal + 8, sizeof(double) * 14, hipMemcpyDeviceToHost, h->stream));
+    // format 0: [0..6] sums of the 6 components (x, y, z about the shift in [17..19]) + wrapped yaw, [8..13] second-moment
+    // sums about the fp64 mean, [14], [15], [7] the sums of x, y, z about that mean, [16] the tag (k_mean_partial left
+    // tag and shift behind the sums: scal[8..27] is the entry)
+    slot[16] = 0.0;
+    HIPCHK(h, hipMemcpyAsync(slot, h->scal + 8, sizeof(double) * RING_STRIDE, hipMemcpyDeviceToHost, h->stream));
     h->mean_count++;
     h->have_meancov = true;
   }
@@ -130,8 +135,16 @@ void finish_mean_cov(const mcl_handle* h, double mean6[6], double* yaw_mean, dou
   const double* p = h->host_pin + RING_STRIDE * (which % MEAN_RING);
   double c[6];
   if (p[16] == 0.0) {
-    for (int k = 0; k < 6; ++k) mean6[k] = p[k] / N;
-    for (int k = 0; k < 6; ++k) c[k] = p[8 + k] / N;
+    // d = x - shift:  mean = shift + sum(d)/N ;  e = x - fl(mean):  cov_ab = sum(e_a e_b)/N - (sum e_a / N)(sum e_b / N)
+    for (int k = 0; k < 3; ++k) mean6[k] = p[17 + k] + p[k] / N;
+    for (int k = 3; k < 6; ++k) mean6[k] = p[k] / N;
+    const double e0 = p[14] / N, e1 = p[15] / N, e2 = p[7] / N;
+    c[0] = p[8] / N - e0 * e0;
+    c[1] = p[9] / N - e1 * e1;
+    c[2] = p[10] / N - e2 * e2;
+    c[3] = p[11] / N - e0 * e1;
+    c[4] = p[12] / N - e0 * e2;
+    c[5] = p[13] / N - e1 * e2;
   } else {
     // d = x - shift:  mean = shift + sum(d)/N ;  cov_ab = sum(d_a d_b)/N - (sum d_a / N)(sum d_b / N)
     const double m0 = p[0] / N, m1 = p[1] / N, m2 = p[2] / N;

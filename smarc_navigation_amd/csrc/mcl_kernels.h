@@ -423,14 +423,36 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_normalised_weights(const u64* __r
 
 // ------------------------------------------------------------------ K6: mean / covariance
 // (auv_pf.py:218-252).  pass 1: sums of the 6 components + wrapped yaw; pass 2: centred moments.
-__global__ void __launch_bounds__(MCL_BLOCK) k_mean_partial(StatePtrs s, long long n,
-                                                            double* __restrict__ part /*[7][grid]*/) {
+// Both passes are taken about a shift, like the one-pass sums of the resample gather (mcl_resample.h): x, y, z enter
+// pass 1 as d = v - shift, so the mean is shift + sum(d) / N and a cloud that is small against its coordinates loses
+// nothing to the size of n * coordinate -- a cloud of equal particles has exactly the mean it should and exactly no
+// covariance.  shifted != 0: the shift is slot 0 of this state (a single shard); 0: no shift (the shards of a cloud
+// have no common particle at hand, their sums must add up).  Pass 2 centres on the fp64 mean m~ of pass 1, which is
+// off the true mean by a rounding delta of the coordinate's size: sum (v - m~)(v - m~)' / N carries delta delta' on
+// top of the covariance -- more than a rounding of the covariance once |mean| / sigma reaches 1e8 (a centimetre cloud at
+// survey coordinates).  Pass 2 therefore also sums e = v - m~ itself and the host subtracts (sum e / N)(sum e / N)'
+// (the corrected two-pass form; finish_mean_cov).
+// tail (pass 1, block 0): the words of the ring entry behind the sums -- format tag 0 and the shift -- so that ONE copy
+// of scal[8..27] is the entry
+__global__ void __launch_bounds__(MCL_BLOCK) k_mean_partial(StatePtrs s, long long n, int shifted,
+                                                            double* __restrict__ part /*[7][grid]*/,
+                                                            double* __restrict__ tail /*[4]*/) {
   __shared__ double sh[16];
+  double shift[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) shift[c] = shifted ? s.c[c][0] : 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    tail[0] = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tail[1 + c] = shift[c];
+  }
   double acc[7] = {0, 0, 0, 0, 0, 0, 0};
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
 #pragma unroll
-    for (int c = 0; c < 6; ++c) acc[c] += s.c[c][i];
+    for (int c = 0; c < 3; ++c) acc[c] += s.c[c][i] - shift[c];
+#pragma unroll
+    for (int c = 3; c < 6; ++c) acc[c] += s.c[c][i];
     acc[6] += wrap_pi(s.c[5][i]);
   }
 #pragma unroll
@@ -439,24 +461,30 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_mean_partial(StatePtrs s, long lo
     if (threadIdx.x == 0) part[(size_t)c * gridDim.x + blockIdx.x] = r;
   }
 }
+// part rows: 0 = sum ez, 1..6 = sums of ex ex, ey ey, ez ez, ex ey, ex ez, ey ez, 7 = sum ex, 8 = sum ey (the order in
+// which k_sum_final leaves them in scal[15..23]: the six products stay where format 0 of the ring has always had them)
+#define COV_PART_ROWS 9
 __global__ void __launch_bounds__(MCL_BLOCK) k_cov_partial(StatePtrs s, long long n,
-                                                           const double* __restrict__ sums, double inv_n,
-                                                           double* __restrict__ part /*[6][grid]*/) {
+                                                           const double* __restrict__ sums, const double* __restrict__ tail,
+                                                           double inv_n, double* __restrict__ part /*[9][grid]*/) {
   __shared__ double sh[16];
-  const double mx = sums[0] * inv_n, my = sums[1] * inv_n, mz = sums[2] * inv_n;
-  double acc[6] = {0, 0, 0, 0, 0, 0};
+  const double mx = tail[1] + sums[0] * inv_n, my = tail[2] + sums[1] * inv_n, mz = tail[3] + sums[2] * inv_n;
+  double acc[COV_PART_ROWS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
     const double dx = s.c[0][i] - mx, dy = s.c[1][i] - my, dz = s.c[2][i] - mz;
-    acc[0] += dx * dx;
-    acc[1] += dy * dy;
-    acc[2] += dz * dz;
-    acc[3] += dx * dy;
-    acc[4] += dx * dz;
-    acc[5] += dy * dz;
+    acc[0] += dz;
+    acc[1] += dx * dx;
+    acc[2] += dy * dy;
+    acc[3] += dz * dz;
+    acc[4] += dx * dy;
+    acc[5] += dx * dz;
+    acc[6] += dy * dz;
+    acc[7] += dx;
+    acc[8] += dy;
   }
 #pragma unroll
-  for (int c = 0; c < 6; ++c) {
+  for (int c = 0; c < COV_PART_ROWS; ++c) {
     double r = block_sum(acc[c], sh);
     if (threadIdx.x == 0) part[(size_t)c * gridDim.x + blockIdx.x] = r;
   }

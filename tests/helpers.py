@@ -5,6 +5,7 @@ The replay driver re-enacts what oracle/ref_harness/gen_golden.py did to the ref
 `backend` object, regenerating the reference's RNG draws from the recorded seed
 (numpy legacy RandomState stream, consumption order SURVEY.md A.1)."""
 import bisect
+import fractions
 import os
 
 import numpy as np
@@ -326,3 +327,250 @@ def _exact_sides(q, U, scheme):
     if scheme in ('systematic', 'naive'):
         return rhs, [(int(U[0]) + (i << 53)) * T for i in range(n)], scheme == 'systematic'
     raise ValueError(scheme)
+
+
+# ------------------------------------------------------------------ mean / covariance and motion step: extended precision
+# The reference the moments and predict edge tests measure the kernels against.  x87 long double (64-bit significand) where
+# numpy has it; elsewhere exact rationals, which is why callers cap n at MOMENTS_N_CAP there.
+LONGDOUBLE_OK = bool(np.finfo(np.longdouble).eps < 1e-18)
+MOMENTS_N_CAP = None if LONGDOUBLE_OK else 5000
+TWO_PI = 2.0 * np.pi
+EPS53 = 2.0 ** -53
+
+# the kernels' launch constants (mcl_kernels.h, mcl_resample.h), restated: the rounding count below follows from them
+MCL_BLOCK, MCL_MAX_GRID = 256, 2048        # k_mean_partial / k_cov_partial / k_sum_final
+RS_BLOCK, GATHER_MAX_GRID = 1024, 256      # k_resample_gather
+
+
+def wrap(a):
+    """(a + pi) % (2 pi) - pi in fp64 with Python's floored modulo (auv_particle.py:48, auv_pf.py:229); numpy's mod on
+    doubles is fmod plus the sign fix-up: exact"""
+    return np.mod(np.asarray(a, dtype=np.float64) + np.pi, TWO_PI) - np.pi
+
+
+def sum_roundings(n, block, max_grid):
+    """K: roundings on the longest path from a particle to a published moment -- the per-thread chain of the grid-stride
+    loop, the wave tree, the waves of a block, the blocks (64 per lane, then a wave tree), and 8 for the products, the
+    subtraction, the division and the un-shift."""
+    grid = min(-(-n // block), max_grid)
+    return -(-n // (grid * block)) + 6 + block // 64 + -(-grid // 64) + 6 + 8
+
+
+def two_pass_roundings(n):
+    return sum_roundings(n, MCL_BLOCK, MCL_MAX_GRID)
+
+
+def gather_roundings(n):
+    return sum_roundings(n, RS_BLOCK, GATHER_MAX_GRID)
+
+
+COV_PAIRS = ((0, 0, 0), (4, 1, 1), (8, 2, 2), (1, 0, 1), (2, 0, 2), (5, 1, 2))   # (slot of cov9, a, b); [3] mirrors [1]
+
+
+def _lay_cov(c):
+    """six moments keyed by slot -> the 9 numbers as auv_pf.py:238-252 lays them out: [1,0] mirrored, [2,0], [2,1] zero"""
+    out = np.zeros(9, dtype=np.result_type(*[np.asarray(v).dtype for v in c.values()]))
+    for k, v in c.items():
+        out[k] = v
+    out[3] = out[1]
+    return out
+
+
+def moments_reference(soa, shift):
+    """Mean pose, mean wrapped yaw and centred second moments of a (6, n) fp64 cloud in extended precision, and the error
+    units U the assertions scale by (d = v - shift, taken in extended precision):
+
+        mean of x, y, z                    U = |shift_a| + mean |d_a|
+        mean of roll, pitch, yaw, wrap     U = mean |v|
+        cov_ab                             U = mean |d_a d_b| + |mean d_a| |mean d_b|
+
+    shift: three numbers (the one-pass form's shift, or the mean itself for the two-pass form).  Returns a dict of
+    mean (6), yaw, cov (9), u_mean (6), u_yaw, u_cov (9), all np.longdouble (or floats rounded from exact rationals)."""
+    soa = np.asarray(soa, dtype=np.float64)
+    assert soa.ndim == 2 and soa.shape[0] == 6
+    if not LONGDOUBLE_OK:
+        return _moments_exact(soa, shift, as_float=True)
+    n = soa.shape[1]
+    L = np.longdouble
+    v = soa.astype(L)
+    sh = np.array([L(s) for s in shift], dtype=L)
+    d = v[:3] - sh[:, None]
+    md = d.sum(axis=1) / L(n)
+    mean = np.concatenate([sh + md, v[3:].sum(axis=1) / L(n)])
+    wy = wrap(soa[5]).astype(L)
+    c = v[:3] - mean[:3, None]                                   # centred on the extended-precision mean: no cancellation
+    cov, u_cov = {}, {}
+    for k, a, b in COV_PAIRS:
+        cov[k] = (c[a] * c[b]).sum() / L(n)
+        u_cov[k] = np.abs(d[a] * d[b]).sum() / L(n) + abs(md[a]) * abs(md[b])
+    u_mean = np.concatenate([np.abs(sh) + np.abs(d).sum(axis=1) / L(n), np.abs(v[3:]).sum(axis=1) / L(n)])
+    return dict(mean=mean, yaw=wy.sum() / L(n), cov=_lay_cov(cov), u_mean=u_mean, u_yaw=np.abs(wy).sum() / L(n),
+                u_cov=_lay_cov(u_cov))
+
+
+def _moments_exact(soa, shift, as_float=False):
+    """moments_reference in exact rationals (every double is one)"""
+    F = fractions.Fraction
+    n = soa.shape[1]
+    v = [[F(float(x)) for x in row] for row in soa]
+    sh = [F(float(s)) if not isinstance(s, F) else s for s in shift]
+    d = [[x - sh[a] for x in v[a]] for a in range(3)]
+    md = [sum(r) / n for r in d]
+    mean = [sh[a] + md[a] for a in range(3)] + [sum(v[a]) / n for a in range(3, 6)]
+    wy = [F(float(x)) for x in wrap(soa[5])]
+    c = [[x - mean[a] for x in v[a]] for a in range(3)]
+    cov, u_cov = {}, {}
+    for k, a, b in COV_PAIRS:
+        cov[k] = sum(p * q for p, q in zip(c[a], c[b])) / n
+        u_cov[k] = sum(abs(p * q) for p, q in zip(d[a], d[b])) / n + abs(md[a]) * abs(md[b])
+    u_mean = [abs(sh[a]) + sum(abs(x) for x in d[a]) / n for a in range(3)] + [sum(abs(x) for x in v[a]) / n for a in range(3, 6)]
+    out = dict(mean=mean, yaw=sum(wy) / n, cov=cov, u_mean=u_mean, u_yaw=sum(abs(x) for x in wy) / n, u_cov=u_cov)
+    if not as_float:
+        return out
+    f = lambda seq: np.array([float(x) for x in seq])  # noqa: E731
+    lay = lambda m: _lay_cov({k: np.float64(float(x)) for k, x in m.items()})  # noqa: E731
+    return dict(mean=f(mean), yaw=float(out['yaw']), cov=lay(cov), u_mean=f(u_mean), u_yaw=float(out['u_yaw']), u_cov=lay(u_cov))
+
+
+def moments_errors(got, ref):
+    """|got - ref| of (mean6, yaw, cov9) as mcl_mean_cov returns them, in units of 2^-53 U: three arrays (6, 1, 9); an
+    entry whose unit is zero is 0 where the values agree exactly and inf where they do not"""
+    L = np.longdouble if LONGDOUBLE_OK else np.float64
+
+    def ratio(g, r, u):
+        g, r, u = np.atleast_1d(np.asarray(g, dtype=L)), np.atleast_1d(np.asarray(r, dtype=L)), np.atleast_1d(np.asarray(u, dtype=L))
+        err = np.abs(g - r)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            q = err / (L(EPS53) * u)
+        return np.where(u > 0, q, np.where(err == 0, 0.0, np.inf)).astype(np.float64)
+    return ratio(got[0], ref['mean'], ref['u_mean']), ratio(got[1], ref['yaw'], ref['u_yaw']), ratio(got[2], ref['cov'], ref['u_cov'])
+
+
+MOMENT_FAMILIES = ('origin', 'survey', 'outlier0', 'seam', 'one', 'identical')
+SURVEY_XY = (6.5e5, 6.4e6)
+
+
+def moments_family(name, n, seed=0):
+    """The input families of the moments tests, (6, n) fp64:
+    origin     sigma = (1, 0.7) m with xy correlation 0.6, a few metres from the origin
+    survey     sigma = 1 cm at (6.5e5, 6.4e6): projected survey coordinates
+    outlier0   survey, but particle 0 lies 1000 m away in x and -1000 m in y: a one-pass shift outside the cloud
+    seam       origin, with yaw = wrap(N(pi, 0.2)) + N(0, 0.1): a cloud across +-pi whose stored yaw leaves [-pi, pi)
+    one        the first particle of survey (n must be 1)
+    identical  n copies of one survey particle"""
+    rs = np.random.RandomState(1000 + seed)
+    g = rs.randn(8, n)
+    soa = np.zeros((6, n))
+    if name in ('origin', 'seam'):
+        soa[0] = 3.0 + g[0]
+        soa[1] = -2.0 + 0.7 * (0.6 * g[0] + 0.8 * g[1])
+        soa[2] = -5.0 + 0.3 * g[2]
+        soa[3], soa[4] = 0.02 + 0.05 * g[3], -0.01 + 0.05 * g[4]
+        soa[5] = 0.4 + 0.3 * g[5] if name == 'origin' else wrap(np.pi + 0.2 * g[5]) + 0.1 * g[6]
+    elif name in ('survey', 'outlier0', 'one', 'identical'):
+        soa[0] = SURVEY_XY[0] + 0.01 * g[0]
+        soa[1] = SURVEY_XY[1] + 0.01 * g[1]
+        soa[2] = -20.0 + 0.01 * g[2]
+        soa[3], soa[4] = 0.02 + 0.01 * g[3], -0.01 + 0.01 * g[4]
+        soa[5] = 1.0 + 0.05 * g[5]
+        if name == 'outlier0':
+            soa[0, 0] += 1000.0
+            soa[1, 0] -= 1000.0
+        elif name == 'one':
+            assert n == 1
+        elif name == 'identical':
+            soa[:] = soa[:, :1]
+    else:
+        raise ValueError(name)
+    return np.ascontiguousarray(soa)
+
+
+def quat_from_euler_ld(roll, pitch, yaw):
+    """tf.transformations.quaternion_from_euler (sxyz) -> (x, y, z, w), np.longdouble, arrays of angles"""
+    L = np.longdouble
+    r, p, y = [np.asarray(a, dtype=np.float64).astype(L) * L(0.5) for a in (roll, pitch, yaw)]
+    sr, cr, sp, cp, sy, cy = np.sin(r), np.cos(r), np.sin(p), np.cos(p), np.sin(y), np.cos(y)
+    return np.stack([cp * sr * cy - sp * cr * sy, cp * sr * sy + sp * cr * cy, cp * cr * sy - sp * sr * cy,
+                     cp * cr * cy + sp * sr * sy], axis=-1)
+
+
+def predict_reference(soa, v, wz, q, z, dt, process_cov, normals=None, yaw_t=None):
+    """Particle.motion_pred (auv_particle.py:38-70) of a (6, n) fp64 cloud, x and y in np.longdouble.  Roll and pitch are
+    the fp64 Euler angles of q (oracle.euler_from_quat: the reference evaluates them in fp64 too), z the odometry's.
+    Yaw: with a zero yaw process variance the statement is fp64 and exact, wrap(fl(yaw + fl(wz dt))) -- returned as `yaw`
+    (fp64, bit-comparable); otherwise `yaw` is the wrap of the extended-precision sum rounded to fp64 and `yaw_unwrapped`
+    that sum.  Returns x, y (longdouble), z, roll, pitch (floats), yaw, yaw_unwrapped, and u_x, u_y =
+    |x'| + |m0| + |m1| + |sigma n|, the unit of the position bound (m = (Ry' Rx)(v dt), rows 0 and 1).  yaw_t: evaluate
+    x and y at this fp64 yaw instead (the yaw under test, where it carries noise: the position bound then does not
+    inherit the yaw's rounding)."""
+    from oracle import oracle as orc
+    L = np.longdouble
+    soa = np.asarray(soa, dtype=np.float64)
+    n = soa.shape[1]
+    sq = np.sqrt(np.asarray(process_cov, dtype=np.float64))
+    nz = np.zeros((n, 6)) if normals is None else np.asarray(normals, dtype=np.float64).reshape(n, 6)
+    roll, pitch, _ = [float(a) for a in orc.euler_from_quat(q)]
+    wzdt = np.float64(wz) * np.float64(dt)
+    if sq[5] == 0.0:
+        yaw = wrap(soa[5] + wzdt)
+        unwrapped = (soa[5] + wzdt).astype(L)
+        yaw_l = yaw.astype(L)
+    else:
+        unwrapped = soa[5].astype(L) + L(wzdt) + L(sq[5]) * nz[:, 5].astype(L)
+        two_pi_l, pi_l = L(2.0 * np.pi), L(np.pi)      # the fp64 constants the statement uses
+        yaw_l = np.mod(unwrapped + pi_l, two_pi_l) - pi_l
+        yaw = yaw_l.astype(np.float64)
+    # fullRotation (auv_particle.py:84-100): Rz(yaw_t) (Ry' Rx), with the reference's own Ry' = [[cp,0,sp],[0,1,0],[-sp,cp,0]]
+    cp, sp, cr, sr = np.cos(L(pitch)), np.sin(L(pitch)), np.cos(L(roll)), np.sin(L(roll))
+    vdt = [L(float(c)) * L(float(dt)) for c in v]
+    m0 = cp * vdt[0] + sp * sr * vdt[1] + sp * cr * vdt[2]
+    m1 = cr * vdt[1] - sr * vdt[2]
+    if yaw_t is not None:
+        yaw_l = np.asarray(yaw_t, dtype=np.float64).astype(L)
+    cy, sy = np.cos(yaw_l), np.sin(yaw_l)
+    n0, n1 = L(sq[0]) * nz[:, 0].astype(L), L(sq[1]) * nz[:, 1].astype(L)
+    x = soa[0].astype(L) + (cy * m0 - sy * m1) + n0
+    y = soa[1].astype(L) + (sy * m0 + cy * m1) + n1
+    return dict(x=x, y=y, z=float(z), roll=roll, pitch=pitch, yaw=yaw, yaw_unwrapped=unwrapped,
+                u_x=np.abs(x) + abs(m0) + abs(m1) + np.abs(n0), u_y=np.abs(y) + abs(m0) + abs(m1) + np.abs(n1))
+
+
+PREDICT_EDGE_YAWS = np.array(
+    [np.pi, -np.pi, np.nextafter(np.pi, 4.0), np.nextafter(np.nextafter(np.pi, 4.0), 4.0), np.nextafter(np.pi, 0.0),
+     np.nextafter(np.nextafter(np.pi, 0.0), 0.0), np.nextafter(-np.pi, -4.0), np.nextafter(np.nextafter(-np.pi, -4.0), -4.0),
+     np.nextafter(-np.pi, 0.0), np.nextafter(np.nextafter(-np.pi, 0.0), 0.0), 0.0, -0.0, np.pi - 1e-3] +
+    [TWO_PI * k for k in (1, -1, 7, -7, 1000, -1000)] + [1e6, -1e6, 1e9, -1e9])
+PREDICT_EDGE_WZDT = (0.0, 1e-3, -1e-3, 0.5, -0.5)
+
+
+def predict_family(n, where, seed=0):
+    """(6, n) fp64 for the predict edge tests: the edge yaws first (as many as fit), then yaw uniform in [-4 pi, 4 pi];
+    x, y metre-wide near the origin or at the survey coordinates"""
+    rs = np.random.RandomState(2000 + seed)
+    soa = np.zeros((6, n))
+    cx, cy = (3.0, -2.0) if where == 'origin' else SURVEY_XY
+    soa[0] = cx + rs.randn(n)
+    soa[1] = cy + rs.randn(n)
+    soa[2] = -4.0 + rs.randn(n)          # z, roll, pitch: overwritten by the odometry's
+    soa[3], soa[4] = 0.1 * rs.randn(n), 0.1 * rs.randn(n)
+    soa[5] = rs.uniform(-4.0 * np.pi, 4.0 * np.pi, n)
+    k = min(n, PREDICT_EDGE_YAWS.size)
+    soa[5, :k] = PREDICT_EDGE_YAWS[:k]
+    return np.ascontiguousarray(soa)
+
+
+ULP_PI = 2.0 ** -51          # spacing of the doubles in [2, 4)
+
+
+def yaw_noise_check(got_yaw, ref):
+    """yaw with process noise: |got - ref| modulo 2 pi in units of ulp(pi), and the samples that landed on the other
+    side of the seam (those may only be ones whose unwrapped reference lies within 4 ulp of +-pi)"""
+    L = np.longdouble
+    two_pi = L(TWO_PI)
+    diff = np.asarray(got_yaw, dtype=np.float64).astype(L) - ref['yaw'].astype(L)
+    turns = np.rint(diff / two_pi)
+    err = np.abs(diff - turns * two_pi) / L(ULP_PI)
+    crossed = turns != 0
+    s = ref['yaw_unwrapped'] + L(np.pi)
+    to_seam = np.abs(s - np.rint(s / two_pi) * two_pi) / L(ULP_PI)
+    return err.astype(np.float64), crossed, to_seam.astype(np.float64)
