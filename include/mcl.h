@@ -207,7 +207,17 @@ int mcl_ranges_expected(mcl_handle* h, int64_t first, int64_t count, const float
  * landmark, auv_ekf_slam/src/ekf_slam.cpp:100-103 chi-square gate).  Landmarks in the MAP frame
  * (n x 3 doubles); detections in the SENSOR frame (n_det x 3 doubles, NaN row = invalid);
  * 1 <= k <= 4; gate = chi-square threshold on |p - l|^2 / sigma^2; accumulate != 0 adds the
- * log-likelihood to the one an earlier update left (e.g. MBES ranges + landmarks of one ping). */
+ * log-likelihood to the one an earlier update left (e.g. MBES ranges + landmarks of one ping).
+ * On the gate: this update's gate is CLOSED -- a landmark with maha == gate counts (the cell grid the landmarks are
+ * binned in is built a relative 2^-30 wider than the gate radius, so that it holds such a landmark whichever way the
+ * cell arithmetic rounds); mcl_update_landmarks_assign's gate is OPEN (maha < gate, as in the reference's table).  The
+ * library evaluates maha as |p - l|^2 * (1 / sigma^2): within an ulp of the gate the side a landmark falls on is that
+ * product's, not the quotient's.
+ * Non-finite poses (both updates): a particle with a NaN or infinite state component has no landmark inside any gate --
+ * every comparison with a NaN or infinite distance is false.  Each valid detection then contributes -gate / 2 (k-NN) or
+ * the new-landmark hypothesis, -new_mh_dist / 2 and assignment -1 (assignment update), minus its lognorm: the
+ * log-likelihood of such a particle is FINITE and the same as that of a pose far from every landmark.  (Its query cell
+ * is clamped onto the empty ring around the grid before the conversion to an integer; the oracle says the same.) */
 int mcl_set_landmarks(mcl_handle* h, const double* xyz, int64_t n_landmarks);
 /* Mahalanobis association as in the reference's EKF-SLAM (auv_ekf_slam/src/ekf_slam_core.cpp:160-178,
  * correspondence_obj_mbes.cpp:26-35,110-120): innovation nu = z - R^T (l - o) in the SENSOR frame,
@@ -224,13 +234,20 @@ int mcl_update_landmarks(mcl_handle* h, const double* det_xyz, int32_t n_det, do
  * of the reference's batch association (auv_ekf_slam/src/ekf_slam_core.cpp:172-178: distance if < gate,
  * else 10000; :269-281: one new-landmark hypothesis per detection at cost new_mh_dist; :298-312: Munkres
  * assignment) solved exactly for every particle; lw = -1/2 * optimal total - n_valid * lognorm.  A
- * landmark explains at most one detection.  n_det <= 16; 1 <= k_cand <= 8 = nearest gated landmarks
+ * landmark explains at most one detection.  new_mh_dist < 10000 is presumed: then the optimum never uses a 10000 entry
+ * and the table reduces to the gated pairs, which is what the library solves; at or above 10000 the reference's table
+ * would pair a detection with a landmark OUTSIDE its gate rather than open a new one, the library still opens a new one
+ * (and the oracle, which keeps the 10000 entries, differs).  n_det <= 16; 1 <= k_cand <= 8 = nearest gated landmarks
  * kept as candidates of a detection: when MORE than k_cand landmarks lie inside a detection's gate the farther
  * ones are dropped before the assignment, so on maps that dense the optimum can differ from the one over the
  * full table (part of the definition: the oracle applies the same rule; tests/test_gpu_landmark_assign.py
- * ::test_dense_cluster...).  With mcl_set_landmark_noise the table entries are the reference's Mahalanobis
- * distances.  assign_out (optional, host): n_keep x n_det int32 for the first
- * n_keep particles -- landmark index, -1 = new-landmark hypothesis, -2 = invalid (NaN) detection. */
+ * ::test_dense_cluster...).  A TIE exactly at the cut -- the k_cand-th and the (k_cand + 1)-th nearest gated landmark
+ * of a detection at bit-identical distances, e.g. duplicate landmarks -- is outside the definition: the library keeps
+ * k_cand candidates (which of the tied ones is unspecified), the oracle every landmark with distance <= the cut.  Ties
+ * anywhere else (duplicate landmarks inside the cut, bit-identical detections) leave the optimal total, hence lw,
+ * defined; only which of the equal-cost optima assign_out reports is unspecified.  With mcl_set_landmark_noise the
+ * table entries are the reference's Mahalanobis distances.  assign_out (optional, host): n_keep x n_det int32 for the
+ * first n_keep particles -- landmark index, -1 = new-landmark hypothesis, -2 = invalid (NaN) detection. */
 int mcl_update_landmarks_assign(mcl_handle* h, const double* det_xyz, int32_t n_det, double sigma, int32_t k_cand,
                                 double gate, double new_mh_dist, const double sensor_offset[6], int32_t accumulate,
                                 int32_t* assign_out, int64_t n_keep);

@@ -9,8 +9,8 @@
 // mapped into the map frame with the particle's sensor pose; maha_j = |p_d - l_j|^2 / sigma^2; over
 // the k nearest landmarks with maha_j <= gate:  lw_d = log sum_j exp(-maha_j/2), or -gate/2 if none;
 // lw = sum_d lw_d - D (3/2 log 2pi + 3 log sigma).
-// Landmarks are binned in a uniform xy grid with cell >= gate radius, so the 3x3 neighbourhood
-// holds every landmark inside the gate: exact, ~9 cell probes per (particle, detection).
+// Landmarks are binned in a uniform xy grid with cell > gate radius (by a relative 2^-30: landmarks_build), so the 3x3
+// neighbourhood holds every landmark inside and ON the gate: exact, ~9 cell probes per (particle, detection).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -331,7 +331,11 @@ __global__ void __launch_bounds__(LA_PER_BLOCK * LM_SUB) k_landmark_assign(Landm
         const double pz = o[2] + Rs[6] * zx + Rs[7] * zy + Rs[8] * zz;
         double Qm[6] = {0, 0, 0, 0, 0, 0};
         if (a.maha) landmark_qm(a, Rs, Qm);
-        const int cx = (int)floor((px - a.x0) * a.inv_cs), cyi = (int)floor((py - a.y0) * a.inv_cs);
+        // the query cell, clamped in double before the conversion like k_landmark_update's (an infinite or very distant
+        // pose is out of int's range, and cx +- 1 must not wrap); [-2, g + 1] is enough, the loops below intersect with
+        // [0, g - 1].  A NaN coordinate lands on -2 (fmax returns the other operand): no cell, no candidate
+        const int cx = (int)fmin(fmax(floor((px - a.x0) * a.inv_cs), -2.0), (double)(a.gx + 1));
+        const int cyi = (int)fmin(fmax(floor((py - a.y0) * a.inv_cs), -2.0), (double)(a.gy + 1));
         // (the three cells of a grid row are neighbours in the cell-ordered landmark array: one range per row)
         const int iy0 = max(cyi - 1, 0), iy1 = min(cyi + 1, a.gy - 1);
         for (int ix = max(cx - 1, 0); ix <= min(cx + 1, a.gx - 1) && iy0 <= iy1; ++ix)
@@ -540,7 +544,18 @@ struct LandmarkDev {
 
 inline void landmarks_free(LandmarkDev* L) { delete L; }
 
-// (re)build the xy cell grid for a gate radius r (cells >= r, at most 2048 x 2048)
+// (re)build the xy cell grid for a gate radius r (cells > r by a relative margin, at most 2048 x 2048).
+// Why the margin: the 3 x 3 neighbourhood has to hold every landmark on the CLOSED gate, |p - l| <= r, whichever way the
+// roundings fall.  The landmark's cell is floor((l - x0) / cs) here, the query's cell is floor((p - x0) * inv_cs) in the
+// kernels, inv_cs the rounded reciprocal.  Each subtraction is off by at most half an ulp of a number <= g cs (g <= 2050
+// cells a side), the quotient and the two products by a relative 2^-53 each, and r itself (sigma sqrt(gate), or the
+// Gershgorin radius) by a few ulp: the two unfloored cell coordinates differ by at most
+//     r / cs + (a few) g 2^-53  <=  1 / (1 + 2^-30) + 2^-39  <  1      with cs >= r (1 + 2^-30),
+// and two numbers less than one apart have floors at most one apart.  With cs = r exactly the bound was 1 + 2^-39: a
+// landmark ON the gate could sit two cells from the query (sigma 7, gate 49: 49 * (1 / 49) = 0.99999999999999989, the
+// query at p - x0 = 49 falls in cell 0, the landmark at 98 in cell 2) -- tests/test_gpu_landmark_edges.py.  The margin
+// is 1e-9 of a cell: no cost.  built_for keeps caching on r.
+#define LM_CELL_MARGIN (1.0 + 9.313225746154785e-10)   // 1 + 2^-30
 inline int landmarks_build(LandmarkDev* L, double r, std::string* err) {
   if (L->built_for == r && L->lm) return MCL_OK;
   L->built_for = -1.0;
@@ -552,7 +567,7 @@ inline int landmarks_build(LandmarkDev* L, double r, std::string* err) {
     ymin = std::min(ymin, L->host_xyz[3 * i + 1]);
     ymax = std::max(ymax, L->host_xyz[3 * i + 1]);
   }
-  double cs = std::max(r, 1e-6);
+  double cs = std::max(r, 1e-6) * LM_CELL_MARGIN;
   cs = std::max(cs, std::max(xmax - xmin, ymax - ymin) / 2048.0);
   L->cs = cs;
   // one cell of padding so that a query just outside the bbox still sees its 3x3 neighbourhood
