@@ -1,5 +1,5 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
-mcl_history.h, mcl_acoustic.h, mcl_temper.h and mcl_drift.h).
+mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h and mcl_regularise.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -81,6 +81,17 @@ class HistoryEst(C.Structure):
 class DriftConfig(C.Structure):
     """mcl_drift_config (include/mcl_drift.h)"""
     _fields_ = [('init_std', C.c_double * 3), ('walk_std', C.c_double * 3)]
+
+
+class RegulariseConfig(C.Structure):
+    """mcl_regularise_config (include/mcl_regularise.h)"""
+    _fields_ = [('scale', C.c_double), ('shrink', C.c_int32), ('dims', C.c_int32)]
+
+
+class RegulariseResult(C.Structure):
+    """mcl_regularise_result (include/mcl_regularise.h)"""
+    _fields_ = [('n', C.c_int64), ('dims', C.c_int32), ('dead', C.c_int32), ('h', C.c_double), ('a', C.c_double),
+                ('shift', C.c_double * 6), ('dmean', C.c_double * 6), ('cov', C.c_double * 21), ('chol', C.c_double * 21)]
 
 
 class TemperRes(C.Structure):
@@ -231,6 +242,15 @@ DRIFT_SYMBOLS = {
     'mcl_drift_mean_cov': (C.c_int, [_vp, _vp, _vp]),
 }
 
+# include/mcl_regularise.h: regularised resampling (jitter from the cloud's own covariance)
+REGULARISE_SYMBOLS = {
+    'mcl_regularise_config_check': (C.c_int, [C.POINTER(RegulariseConfig), C.POINTER(C.c_char_p)]),
+    'mcl_regularise_bandwidth': (C.c_int, [_i64, _i32, _d, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'mcl_regularise_factor': (C.c_int, [_vp, _i32, _vp, C.POINTER(C.c_int32)]),
+    'mcl_regularise': (C.c_int, [_vp, C.POINTER(RegulariseConfig), _vp]),
+    'mcl_regularise_last': (C.c_int, [_vp, C.POINTER(RegulariseResult)]),
+}
+
 _lib = None
 
 
@@ -245,7 +265,8 @@ def load():
     lib = C.CDLL(SO_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()) +
                               list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items()) +
-                              list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items())):
+                              list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
+                              list(REGULARISE_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

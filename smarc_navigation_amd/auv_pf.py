@@ -97,6 +97,13 @@ DEFAULT_PARAMS = {
     # are parsed like the covariance strings.  false = off: the call is never made and the node computes what it
     # computed without the parameters.
     'estimate_drift': False, 'drift_init_std': '[0.2, 0.2, 0.0]', 'drift_walk_std': '[0.005, 0.005, 0.0]',
+    # Regularised resampling (include/mcl_regularise.h): > 0: right after every resampling each particle is jittered with
+    # h^2 times the cloud's own sample covariance of (x, y, yaw) -- with estimate_drift, of (x, y, yaw, cx, cy, bw) jointly
+    # -- h = regularise_scale x the kernel-density bandwidth for the particle count (1.0 is the textbook value);
+    # regularise_shrink: shrink towards the mean first (Liu-West), so that the cloud's mean and covariance stay what they
+    # were.  It comes on top of resampling_noise_covariance, which may then be zero.  0 = off: the call is never made and
+    # the node computes what it computed without the parameters.
+    'regularise_scale': 0.0, 'regularise_shrink': True,
 }
 
 
@@ -349,6 +356,16 @@ class auv_pf(object):
             if rng_mode == _engine.RNG_NATIVE:
                 self.particles.drift_enable(self.drift_init_std, self.drift_walk_std)
         self._drift_enabled = self.estimate_drift and rng_mode == _engine.RNG_NATIVE
+        # regularised resampling
+        self.regularise_scale = float(p['regularise_scale'])
+        self.regularise_shrink = _as_bool(p['regularise_shrink'])
+        if self.regularise_scale != 0.0:
+            why = _engine.regularise_config_check(self.regularise_scale, self.regularise_shrink,
+                                                  6 if self.estimate_drift else 3)
+            if why:
+                raise ValueError('regularise_scale: ' + why)
+        self.regularise_calls = 0       # resamplings that were regularised
+        self.regularise_hs = []         # the bandwidth h of each, in order (host arithmetic: regularise_bandwidth)
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
@@ -423,6 +440,14 @@ class auv_pf(object):
             self.particles.resample(u, self._replay.randn(self.pc, 6))
         else:
             self.particles.resample()
+        if self.regularise_scale > 0.0:
+            # jitter from the cloud the resampling left, pose and drift jointly (include/mcl_regularise.h)
+            dims = 6 if self.estimate_drift else 3
+            self.particles.regularise(self.regularise_scale, self.regularise_shrink, self.estimate_drift,
+                                      self._replay.randn(self.pc, dims) if self._replay is not None else None)
+            self.regularise_calls += 1
+            self.regularise_hs.append(_engine.regularise_bandwidth(self.pc, dims, self.regularise_scale,
+                                                                   self.regularise_shrink)[0])
         if self.fix_history_depth > 0 and (self._fix_last_record is None or self.time > self._fix_last_record):
             # one frame per resampling: what a late fix is evaluated against.  The filter's clock moves with the odometry
             # alone, so a second resampling before the next odometry message (a ping and a fix, a ping and a DVL altitude,

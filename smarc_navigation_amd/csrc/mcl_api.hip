@@ -13,6 +13,7 @@
 #include "mcl_host_acoustic.h"
 #include "mcl_host_temper.h"
 #include "mcl_host_drift.h"
+#include "mcl_host_regularise.h"
 // global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
 #include "mcl_recovery.h"
 // (the kernels of mcl_pose_modes, include/mcl_modes.h, come with mcl_host.h: csrc/mcl_modes.h)
@@ -1417,6 +1418,40 @@ int mcl_drift_mean_cov(mcl_handle* h, double mean3[3], double cov6[6]) {
   RET_IF(need_drift(h, "drift_mean_cov"));
   RET_IF(set_device(h));
   return drift_mean_cov(h, mean3, cov6);
+}
+
+// ---- regularised resampling (include/mcl_regularise.h; host: mcl_host_regularise.h, kernels: csrc/mcl_regularise.h)
+int mcl_regularise_config_check(const mcl_regularise_config* cfg, const char** reason) {
+  return regularise_config_check_impl(cfg, reason);
+}
+
+int mcl_regularise_bandwidth(int64_t n, int32_t dims, double scale, int32_t shrink, double* h, double* a) {
+  return regularise_bandwidth_impl(n, dims, scale, shrink, h, a);
+}
+
+int mcl_regularise_factor(const double* cov_packed, int32_t dims, double* chol_packed, int32_t* dead) {
+  return regularise_factor_impl(cov_packed, dims, chol_packed, dead);
+}
+
+int mcl_regularise(mcl_handle* h, const mcl_regularise_config* cfg, const double* replay_normals) {
+  if (!h) return MCL_ERR_INVALID;
+  if (const char* why = regularise_config_why(cfg)) return fail(h, MCL_ERR_INVALID, std::string("regularise: ") + why);
+  if (h->world > 1 || h->cfg.comm_mode != MCL_COMM_NONE || h->comm)
+    return fail(h, MCL_ERR_UNSUPPORTED, "regularise: a sharded cloud is not supported");
+  if (cfg->dims == 6 && !h->drift_on)
+    return fail(h, MCL_ERR_STATE, "regularise: dims = 6 needs the drift (call mcl_drift_enable first, or pass dims = 3)");
+  if (h->cfg.rng_mode == MCL_RNG_REPLAY && !replay_normals)
+    return fail(h, MCL_ERR_INVALID, "regularise: REPLAY mode needs n x dims normals");
+  RET_IF(set_device(h));
+  return regularise_run(h, cfg, replay_normals);
+}
+
+int mcl_regularise_last(mcl_handle* h, mcl_regularise_result* result) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!result) return fail(h, MCL_ERR_INVALID, "regularise_last: null argument");
+  if (h->reg_dims == 0) return fail(h, MCL_ERR_STATE, "regularise_last: no mcl_regularise call yet");
+  RET_IF(set_device(h));
+  return regularise_last(h, result);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

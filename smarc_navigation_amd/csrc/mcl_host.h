@@ -2,7 +2,7 @@
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
 // mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h,
-// mcl_host_drift.h
+// mcl_host_drift.h, mcl_host_regularise.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,7 @@
 #include "mcl_modes.h"
 #include "mcl_history.h"
 #include "mcl_drift.h"
+#include "mcl_regularise.h"
 
 #define MEAN_RING 4096
 #define RING_STRIDE 20  // doubles per mean/cov result: 16 payload + [16] format tag + [17..19] the two-pass form's shift
@@ -240,6 +241,12 @@ struct mcl_handle {
   DevBuf<double> drift_state;  // 3 x n: cx, cy, bw
   DevBuf<double> drift_part;   // per-workgroup sums [DRIFT_SUMS][grid]
   DevBuf<double> drift_res;    // DRIFT_RES_WORDS: the summed moments, the shift
+  // regularised resampling (include/mcl_regularise.h; both buffers reserved by the first mcl_regularise)
+  uint32_t reg_calls = 0;      // regularise calls so far: the Philox step of the next one
+  int32_t reg_dims = 0;        // of the last call (0: there was none)
+  double reg_h = 0.0, reg_a = 0.0;   // ... its bandwidth and shrink factor
+  DevBuf<double> reg_part;     // per-workgroup sums [REG_SUMS_MAX][grid]
+  DevBuf<double> reg_res;      // REG_RES_WORDS: the record of the last call (sums, shift, mean, cov, factor, dead mask)
   bool timing = false;
   std::vector<TimedRegion> regions;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

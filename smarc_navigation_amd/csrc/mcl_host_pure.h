@@ -4,7 +4,8 @@
 // gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes, the bytes of
 // mcl_history_enable and mcl_drift_enable, the stds of mcl_drift_config, the pose arguments of the acoustic updates and
 // mcl_history_bracket), and the lattice, predicate
-// and round plan of mcl_temper (also run by its pick kernel: MCL_HD).  No HIP header: the
+// and round plan of mcl_temper (also run by its pick kernel: MCL_HD), and the rules, bandwidth and factor of
+// mcl_regularise (the factor also run by its kernel).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -21,6 +22,7 @@
 #include "../../include/mcl_acoustic.h"
 #include "../../include/mcl_temper.h"
 #include "../../include/mcl_drift.h"
+#include "../../include/mcl_regularise.h"
 
 namespace {
 
@@ -475,6 +477,80 @@ int temper_search(long long n_target, Sums&& sums, int* j_out, int* floor_hit, i
     if (st.done) break;
   }
   *j_out = j;
+  return MCL_OK;
+}
+
+// ---- regularised resampling (include/mcl_regularise.h): the configuration's rules, the bandwidth, and the factor of the
+// cloud's covariance.  The factor kernel (csrc/mcl_regularise.h) runs reg_factor itself: one statement of the rule.
+constexpr int REG_MAX_DIMS = 6, REG_MAX_PACKED = 21;
+MCL_HD inline int reg_packed(int r, int c) { return r * (r + 1) / 2 + c; }   // (r >= c)
+MCL_HD inline bool reg_dims_ok(int dims) { return dims == 3 || dims == 6; }
+// C, L packed lower-triangular, D (D + 1) / 2 words; returns the dead mask.  Every product, sum, quotient and root is an
+// operation of its own (no contraction), k increasing: a restatement in any language gives the same bits.
+MCL_HD inline int reg_factor(const double* C, int D, double* L) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  int dead = 0;
+  for (int j = 0; j < D; ++j) {
+    const double cjj = C[reg_packed(j, j)];
+    double p = cjj;
+    for (int k = 0; k < j; ++k) {
+      const double l = L[reg_packed(j, k)];
+      const double q = l * l;
+      p = p - q;
+    }
+    const double floor_ = cjj * (1.0 / 67108864.0);   // 2^-26, exact
+    if (p > floor_) {                                 // (false for NaN and for C_jj <= 0)
+      const double d = sqrt(p);
+      L[reg_packed(j, j)] = d;
+      for (int i = j + 1; i < D; ++i) {
+        double t = C[reg_packed(i, j)];
+        for (int k = 0; k < j; ++k) {
+          const double q = L[reg_packed(i, k)] * L[reg_packed(j, k)];
+          t = t - q;
+        }
+        L[reg_packed(i, j)] = t / d;
+      }
+    } else {
+      dead |= 1 << j;
+      for (int i = j; i < D; ++i) L[reg_packed(i, j)] = 0.0;
+    }
+  }
+  return dead;
+}
+int regularise_factor_impl(const double* cov, int32_t dims, double* chol, int32_t* dead) {
+  if (!cov || !chol || !dead || !reg_dims_ok(dims)) return MCL_ERR_INVALID;
+  double c[REG_MAX_PACKED], l[REG_MAX_PACKED];   // (cov and chol may be the same array)
+  const int np = dims * (dims + 1) / 2;
+  for (int k = 0; k < np; ++k) c[k] = cov[k];
+  *dead = reg_factor(c, dims, l);
+  for (int k = 0; k < np; ++k) chol[k] = l[k];
+  return MCL_OK;
+}
+const char* regularise_config_why(const mcl_regularise_config* cfg) {
+  if (!cfg) return "null config";
+  if (!std::isfinite(cfg->scale) || !(cfg->scale > 0.0)) return "scale must be finite and > 0";
+  if (!reg_dims_ok(cfg->dims)) return "dims must be 3 (x, y, yaw) or 6 (x, y, yaw, cx, cy, bw)";
+  return nullptr;
+}
+int regularise_config_check_impl(const mcl_regularise_config* cfg, const char** reason) {
+  const char* why = regularise_config_why(cfg);
+  if (reason) *reason = why;
+  return why ? MCL_ERR_INVALID : MCL_OK;
+}
+// h0 = scale (4 / ((D + 2) n))^(1 / (D + 4)); shrink: h = min(h0, 1), a = sqrt(1 - h h)
+int regularise_bandwidth_impl(int64_t n, int32_t dims, double scale, int32_t shrink, double* h, double* a) {
+  if (!h || !a || n < 1 || !reg_dims_ok(dims) || !std::isfinite(scale) || !(scale > 0.0)) return MCL_ERR_INVALID;
+  const double D = (double)dims;
+  const double h0 = scale * std::pow(4.0 / ((D + 2.0) * (double)n), 1.0 / (D + 4.0));
+  if (shrink) {
+    *h = h0 < 1.0 ? h0 : 1.0;
+    *a = std::sqrt(1.0 - *h * *h);
+  } else {
+    *h = h0;
+    *a = 1.0;
+  }
   return MCL_OK;
 }
 

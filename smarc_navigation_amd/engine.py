@@ -430,6 +430,31 @@ class Engine(object):
         self._ck(self.lib.mcl_drift_mean_cov(self.h, _ptr(mean), _ptr(c)))
         return mean, np.array([[c[0], c[1], c[2]], [c[1], c[3], c[4]], [c[2], c[4], c[5]]])
 
+    # ---- regularised resampling: jitter from the cloud's own covariance (include/mcl_regularise.h)
+    def regularise(self, scale=1.0, shrink=True, with_drift=False, normals=None):
+        """call it right after a resample: every particle is jittered with h^2 times the cloud's own covariance of
+        (x, y, yaw) -- with_drift: of (x, y, yaw, cx, cy, bw), jointly -- h = scale x the kernel-density bandwidth;
+        shrink: towards the mean first, so that mean and covariance stay what they were.  normals: n x 3 or n x 6
+        (REPLAY mode).  Asynchronous."""
+        cfg = make_regularise_config(scale, shrink, 6 if with_drift else 3)
+        nz = _f64(normals)
+        if nz is not None and nz.size != cfg.dims * self.n:
+            raise ValueError('regularise: normals are n x %d, particle-major' % cfg.dims)
+        self._ck(self.lib.mcl_regularise(self.h, C.byref(cfg), _ptr(nz)))
+
+    def regularise_last(self):
+        """what the last regularise measured and used: dict(n, dims, dead, h, a, shift (D,), dmean (D,), mean (D,),
+        cov (D, D), chol (D, D) lower-triangular)"""
+        r = _lib.RegulariseResult()
+        self._ck(self.lib.mcl_regularise_last(self.h, C.byref(r)))
+        d = int(r.dims)
+        shift, dmean = np.array(r.shift[:d]), np.array(r.dmean[:d])
+        chol = _unpack_lower(r.chol, d)
+        cov = _unpack_lower(r.cov, d)
+        cov = cov + np.tril(cov, -1).T
+        return dict(n=int(r.n), dims=d, dead=int(r.dead), h=float(r.h), a=float(r.a), shift=shift, dmean=dmean,
+                    mean=shift + dmean, cov=cov, chol=chol)
+
     def predict(self, v, wz, q, z, dt, normals=None, stamp=0.0):
         nz = _f64(normals)
         od = make_odom(v, wz, q, z, stamp)
@@ -691,6 +716,53 @@ def drift_bytes(n):
     b = C.c_int64(0)
     _lib.check(_lib.load().mcl_drift_bytes(int(n), C.byref(b)))
     return int(b.value)
+
+
+def _unpack_lower(packed, d):
+    """(d, d) lower-triangular from the packed order (0,0), (1,0), (1,1), (2,0), ..."""
+    m = np.zeros((d, d))
+    m[np.tril_indices(d)] = np.array(packed[:d * (d + 1) // 2])
+    return m
+
+
+def _pack_lower(m):
+    m = _f64(m)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError('regularise: a square matrix')
+    return np.ascontiguousarray(m[np.tril_indices(m.shape[0])])
+
+
+def make_regularise_config(scale, shrink, dims):
+    cfg = _lib.RegulariseConfig()
+    cfg.scale, cfg.shrink, cfg.dims = float(scale), 1 if shrink else 0, int(dims)
+    return cfg
+
+
+def regularise_config_check(scale, shrink=True, dims=3):
+    """None, or the sentence saying what mcl_regularise refuses about (scale, dims) (mcl_regularise_config_check: no device)"""
+    cfg, why = make_regularise_config(scale, shrink, dims), C.c_char_p()
+    st = _lib.load().mcl_regularise_config_check(C.byref(cfg), C.byref(why))
+    return None if st == 0 else (why.value or b'').decode()
+
+
+def regularise_bandwidth(n, dims, scale=1.0, shrink=True):
+    """(h, a): h0 = scale (4 / ((dims + 2) n))^(1 / (dims + 4)); shrink: h = min(h0, 1), a = sqrt(1 - h^2), else h = h0,
+    a = 1 (mcl_regularise_bandwidth: host arithmetic)"""
+    h, a = C.c_double(0.0), C.c_double(0.0)
+    _lib.check(_lib.load().mcl_regularise_bandwidth(int(n), int(dims), float(scale), 1 if shrink else 0, C.byref(h),
+                                                    C.byref(a)))
+    return float(h.value), float(a.value)
+
+
+def regularise_factor(cov):
+    """(chol, dead): the lower-triangular factor of a (3, 3) or (6, 6) covariance (its lower triangle is read) by the rule
+    of include/mcl_regularise.h, and the mask of the columns it left zero (mcl_regularise_factor: the very function the
+    device runs)"""
+    c = _pack_lower(cov)
+    d = np.asarray(cov).shape[0]
+    out, dead = np.zeros(c.size), C.c_int32(0)
+    _lib.check(_lib.load().mcl_regularise_factor(_ptr(c), int(d), _ptr(out), C.byref(dead)))
+    return _unpack_lower(out, d), int(dead.value)
 
 
 def temper_beta(j):

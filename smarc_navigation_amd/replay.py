@@ -353,6 +353,11 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
             t = np.asarray(stream['drift_truth'], dtype=np.float64)
             summary['drift_error'] = float(np.hypot(pf.drift_mean[0] - t[0], pf.drift_mean[1] - t[1]))
             summary['drift_bias_error'] = float(abs(pf.drift_mean[2] - t[2]))
+    if pf.regularise_scale > 0.0:
+        # regularised resampling (include/mcl_regularise.h): how many resamplings were jittered, with which bandwidth
+        summary['regularise_scale'], summary['regularise_shrink'] = float(pf.regularise_scale), bool(pf.regularise_shrink)
+        summary['regularise_calls'] = int(pf.regularise_calls)
+        summary['regularise_h_mean'] = float(np.mean(pf.regularise_hs)) if pf.regularise_hs else 0.0
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -581,6 +586,12 @@ def main(argv=None):
                     help='the prior\'s standard deviations [m/s, m/s, rad/s] (the node\'s drift_init_std)')
     ap.add_argument('--drift-walk-std', type=float, nargs=3, default=None, metavar=('CX', 'CY', 'BW'),
                     help='the random walk\'s, per sqrt(second) (the node\'s drift_walk_std)')
+    ap.add_argument('--regularise', type=float, default=0.0, metavar='SCALE',
+                    help='after every resampling jitter each particle with h^2 x the cloud\'s own covariance, h = SCALE x the '
+                         'kernel-density bandwidth (the node\'s regularise_scale, include/mcl_regularise.h; 1.0 is the '
+                         'textbook value); the summary gains regularise_scale and the mean h; 0: off')
+    ap.add_argument('--no-regularise-shrink', action='store_true',
+                    help='plain jitter: do not shrink towards the mean first (the node\'s regularise_shrink = false)')
     ap.add_argument('--current', type=float, nargs=2, default=(0.0, 0.0), metavar=('CX', 'CY'),
                     help='synthetic streams: a water current [m/s, odom frame] the odometry does not see')
     ap.add_argument('--yaw-rate-bias', type=float, default=0.0, metavar='B',
@@ -595,6 +606,12 @@ def main(argv=None):
         ap.error('--estimate-drift: only with the plain stream replay')
     if (a.drift_init_std or a.drift_walk_std) and not a.estimate_drift:
         ap.error('--drift-init-std / --drift-walk-std need --estimate-drift')
+    if not (a.regularise >= 0.0 and np.isfinite(a.regularise)):
+        ap.error('--regularise: SCALE must be finite and >= 0')
+    if (a.regularise > 0 or a.no_regularise_shrink) and (a.bag or a.recover):
+        ap.error('--regularise: only with the plain stream replay')
+    if a.no_regularise_shrink and not a.regularise > 0:
+        ap.error('--no-regularise-shrink needs --regularise SCALE')
     if not 0.0 <= a.temper_ess <= 1.0:
         ap.error('--temper-ess: RATIO must lie in [0, 1]')
     if a.temper_ess > 0 and (a.bag or a.recover):
@@ -647,6 +664,8 @@ def main(argv=None):
             params.update(drift_init_std=str([float(x) for x in a.drift_init_std]))
         if a.drift_walk_std:
             params.update(drift_walk_std=str([float(x) for x in a.drift_walk_std]))
+    if a.regularise > 0:
+        params.update(regularise_scale=a.regularise, regularise_shrink=not a.no_regularise_shrink)
     if a.fix_period > 0:
         params.update(fix_topic='/sam/external/uw_gps_odom', fix_std=a.fix_std, fix_history_depth=a.fix_history_depth,
                       fix_max_age=max(10.0, 2.0 * a.fix_latency))
