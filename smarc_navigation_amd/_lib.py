@@ -1,5 +1,5 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
-mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h and mcl_regularise.h).
+mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h and mcl_quantile.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -98,6 +98,17 @@ class TemperRes(C.Structure):
     """mcl_temper_result (include/mcl_temper.h)"""
     _fields_ = [('j', C.c_int32), ('floor_hit', C.c_int32), ('levels_evaluated', C.c_int32), ('reserved', C.c_int32),
                 ('n_target', C.c_int64), ('n_live', C.c_int64), ('beta', C.c_double), ('max_lw', C.c_double)]
+
+
+class QuantileQuery(C.Structure):
+    """mcl_quantile_query (include/mcl_quantile.h)"""
+    _fields_ = [('quantity', C.c_int32), ('weighted', C.c_int32), ('centre', C.c_double * 3)]
+
+
+class QuantileResult(C.Structure):
+    """mcl_quantile_result (include/mcl_quantile.h)"""
+    _fields_ = [('value', C.c_double), ('key', C.c_uint64), ('mass', C.c_uint64), ('total', C.c_uint64),
+                ('n_used', C.c_int64)]
 
 
 # every symbol include/mcl.h, mcl_dr.h and mcl_map.h declare: name -> (restype, argtypes)
@@ -251,6 +262,20 @@ REGULARISE_SYMBOLS = {
     'mcl_regularise_last': (C.c_int, [_vp, C.POINTER(RegulariseResult)]),
 }
 
+# include/mcl_quantile.h: exact order statistics of the cloud (median pose, credible radii)
+QUANTILE_SYMBOLS = {
+    'mcl_quantile_key': (C.c_int, [_d, C.POINTER(C.c_uint64)]),
+    'mcl_quantile_value': (C.c_int, [C.c_uint64, C.POINTER(_d)]),
+    'mcl_quantile_threshold': (C.c_int, [_d, C.POINTER(C.c_uint64)]),
+    'mcl_quantile_reached': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(_i32)]),
+    'mcl_cloud_quantiles': (C.c_int, [_vp, C.POINTER(QuantileQuery), _vp, _i32, C.POINTER(QuantileResult)]),
+    'mcl_cloud_mass': (C.c_int, [_vp, C.POINTER(QuantileQuery), _d, _vp, _i32, _vp, C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_int64)]),
+    'mcl_cloud_key_hist': (C.c_int, [_vp, C.POINTER(QuantileQuery), _d, C.c_uint64, _i32, _vp]),
+    'mcl_group_cloud_quantiles': (C.c_int, [C.POINTER(_vp), _i32, C.POINTER(QuantileQuery), _vp, _i32,
+                                            C.POINTER(QuantileResult)]),
+}
+
 _lib = None
 
 
@@ -266,7 +291,7 @@ def load():
     for name, (res, args) in (list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()) +
                               list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items()) +
                               list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
-                              list(REGULARISE_SYMBOLS.items())):
+                              list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

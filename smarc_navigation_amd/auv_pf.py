@@ -104,6 +104,11 @@ DEFAULT_PARAMS = {
     # were.  It comes on top of resampling_noise_covariance, which may then be zero.  0 = off: the call is never made and
     # the node computes what it computed without the parameters.
     'regularise_scale': 0.0, 'regularise_shrink': True,
+    # Credible region (include/mcl_quantile.h): a probability in (0, 1]: every loc_loop also asks the cloud for the radius
+    # that holds that share of the posterior about the pose it publishes, and for the heading half-width that does -- exact
+    # order statistics, kept in `last_credible`.  There is no standard message for it: nothing more is published.  0 = off:
+    # the call is never made and the node computes what it computed without the parameter.
+    'credible_prob': 0.0,
 }
 
 
@@ -365,6 +370,12 @@ class auv_pf(object):
             if why:
                 raise ValueError('regularise_scale: ' + why)
         self.regularise_calls = 0       # resamplings that were regularised
+        # credible region about the published pose
+        self.credible_prob = float(p['credible_prob'])
+        if not 0.0 <= self.credible_prob <= 1.0:
+            raise ValueError('credible_prob must lie in [0, 1], not %r' % self.credible_prob)
+        self.last_credible = None       # dict(prob, radius, yaw_halfwidth, n_used, centre) of the last loc_loop
+        self.credible_calls = 0
         self.regularise_hs = []         # the bandwidth h of each, in order (host arithmetic: regularise_bandwidth)
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
@@ -673,5 +684,12 @@ class auv_pf(object):
         with self.lock:
             self.poses.data = self.particles.poses()  # (n, 7): position + quaternion_from_euler per particle
             self.poses.header.stamp = self.transport.now()
-            self.update_loc_pose()
+            mean, yaw, _ = self.update_loc_pose()
+            if self.credible_prob > 0.0:
+                # how well is that pose known: the radius and heading half-width that hold credible_prob of the cloud
+                centre = (float(mean[0]), float(mean[1]), float(yaw))
+                c = self.particles.credible((self.credible_prob,), centre)
+                self.credible_calls += 1
+                self.last_credible = dict(prob=self.credible_prob, radius=c.radius[self.credible_prob],
+                                          yaw_halfwidth=c.yaw_halfwidth[self.credible_prob], n_used=c.n_used, centre=centre)
             self.transport.publish_poses(self.poses)

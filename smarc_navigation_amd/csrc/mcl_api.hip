@@ -14,6 +14,7 @@
 #include "mcl_host_temper.h"
 #include "mcl_host_drift.h"
 #include "mcl_host_regularise.h"
+#include "mcl_host_quantile.h"
 // global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
 #include "mcl_recovery.h"
 // (the kernels of mcl_pose_modes, include/mcl_modes.h, come with mcl_host.h: csrc/mcl_modes.h)
@@ -1452,6 +1453,47 @@ int mcl_regularise_last(mcl_handle* h, mcl_regularise_result* result) {
   if (h->reg_dims == 0) return fail(h, MCL_ERR_STATE, "regularise_last: no mcl_regularise call yet");
   RET_IF(set_device(h));
   return regularise_last(h, result);
+}
+
+// ---- exact order statistics (include/mcl_quantile.h; host: mcl_host_quantile.h, kernels: csrc/mcl_quantile.h)
+int mcl_quantile_key(double v, uint64_t* key) { return quantile_key_impl(v, key); }
+
+int mcl_quantile_value(uint64_t key, double* v) { return quantile_value_impl(key, v); }
+
+int mcl_quantile_threshold(double p, uint64_t* P) { return quantile_threshold_impl(p, P); }
+
+int mcl_quantile_reached(uint64_t mass, uint64_t total, uint64_t P, int32_t* reached) {
+  return quantile_reached_impl(mass, total, P, reached);
+}
+
+int mcl_cloud_quantiles(mcl_handle* h, const mcl_quantile_query* query, const double* probs, int32_t n_probs,
+                        mcl_quantile_result* out) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!query || !probs || !out) return fail(h, MCL_ERR_INVALID, "cloud_quantiles: null argument");
+  return quant_run(h, query, probs, n_probs, out);
+}
+
+int mcl_cloud_mass(mcl_handle* h, const mcl_quantile_query* query, double max_lw, const double* values, int32_t n_values,
+                   uint64_t* mass, uint64_t* total, int64_t* n_used) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!query || !values || !mass || !total || !n_used) return fail(h, MCL_ERR_INVALID, "cloud_mass: null argument");
+  return quant_mass_run(h, query, max_lw, values, n_values, mass, total, n_used);
+}
+
+int mcl_cloud_key_hist(mcl_handle* h, const mcl_quantile_query* query, double max_lw, uint64_t prefix, int32_t prefix_bits,
+                       uint64_t hist[256]) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!query || !hist) return fail(h, MCL_ERR_INVALID, "cloud_key_hist: null argument");
+  return quant_key_hist(h, query, max_lw, prefix, prefix_bits, hist);
+}
+
+int mcl_group_cloud_quantiles(mcl_handle** shards, int32_t ns, const mcl_quantile_query* query, const double* probs,
+                              int32_t n_probs, mcl_quantile_result* out) {
+  if (!shards || ns < 1) return MCL_ERR_INVALID;
+  for (int s = 0; s < ns; ++s)
+    if (!shards[s]) return MCL_ERR_INVALID;
+  if (!query || !probs || !out) return fail(shards[0], MCL_ERR_INVALID, "group_cloud_quantiles: null argument");
+  return group_quant_run(shards, ns, query, probs, n_probs, out);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

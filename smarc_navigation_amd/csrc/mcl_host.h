@@ -2,7 +2,7 @@
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
 // mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h,
-// mcl_host_drift.h, mcl_host_regularise.h
+// mcl_host_drift.h, mcl_host_regularise.h, mcl_host_quantile.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -247,6 +247,7 @@ struct mcl_handle {
   double reg_h = 0.0, reg_a = 0.0;   // ... its bandwidth and shrink factor
   DevBuf<double> reg_part;     // per-workgroup sums [REG_SUMS_MAX][grid]
   DevBuf<double> reg_res;      // REG_RES_WORDS: the record of the last call (sums, shift, mean, cov, factor, dead mask)
+  DevBuf<u64> quant_dev;       // order statistics (include/mcl_quantile.h): the state block of csrc/mcl_quantile.h, QS_WORDS (lazily)
   bool timing = false;
   std::vector<TimedRegion> regions;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

@@ -5,7 +5,8 @@
 // mcl_history_enable and mcl_drift_enable, the stds of mcl_drift_config, the pose arguments of the acoustic updates and
 // mcl_history_bracket), and the lattice, predicate
 // and round plan of mcl_temper (also run by its pick kernel: MCL_HD), and the rules, bandwidth and factor of
-// mcl_regularise (the factor also run by its kernel).  No HIP header: the
+// mcl_regularise (the factor also run by its kernel), and the keys, threshold, predicate,
+// start and bin choice of mcl_cloud_quantiles (include/mcl_quantile.h; the kernels run the same functions).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -23,6 +24,7 @@
 #include "../../include/mcl_temper.h"
 #include "../../include/mcl_drift.h"
 #include "../../include/mcl_regularise.h"
+#include "../../include/mcl_quantile.h"
 
 namespace {
 
@@ -552,6 +554,88 @@ int regularise_bandwidth_impl(int64_t n, int32_t dims, double scale, int32_t shr
     *a = 1.0;
   }
   return MCL_OK;
+}
+
+// ---- exact order statistics (include/mcl_quantile.h): the key of a value, the threshold of a probability, the 128-bit
+// predicate, where the radix select starts and which bin a round picks.  The kernels (csrc/mcl_quantile.h) run quant_key,
+// quant_reached and quant_start themselves; the host-driven shard search runs quant_pick_bin, whose rule -- the first bin
+// whose cumulative mass reaches the threshold -- the pick kernel states once more across a wave.
+constexpr int QUANT_ROUNDS = 8;   // bytes of a key
+// key(v + 0.0): order-preserving, -0 and +0 one key (NaN: the callers exclude it)
+MCL_HD inline unsigned long long quant_key(double v) {
+  const double w = v + 0.0;
+  unsigned long long b;
+  __builtin_memcpy(&b, &w, sizeof b);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+MCL_HD inline double quant_value(unsigned long long k) {
+  const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  double v;
+  __builtin_memcpy(&v, &b, sizeof v);
+  return v;
+}
+// 2^32 mass >= P total in 128 bits: the left side is below 2^96, the right side below 2^128
+MCL_HD inline bool quant_reached(unsigned long long mass, unsigned long long total, unsigned long long P) {
+  typedef unsigned __int128 u128;
+  return ((u128)mass << 32) >= (u128)P * (u128)total;
+}
+// the first round that has to run and the bytes above it, from the smallest and largest key of the used particles: the
+// leading bytes both share are skipped, the last round always runs (it also finds S); no used particle (kmin > kmax): the
+// last round alone, over nothing
+struct QuantStart {
+  int start;                   // 0 ... 7
+  unsigned long long prefix;   // the key's leading `start` bytes
+};
+MCL_HD inline QuantStart quant_start(unsigned long long kmin, unsigned long long kmax) {
+  QuantStart r = {QUANT_ROUNDS - 1, 0ull};
+  if (kmin > kmax) return r;
+  int s = 0;
+  while (s < QUANT_ROUNDS - 1 && (kmin >> (56 - 8 * s)) == (kmax >> (56 - 8 * s))) ++s;
+  r.start = s;
+  r.prefix = s == 0 ? 0ull : kmin >> (64 - 8 * s);
+  return r;
+}
+// the bin a round picks: the first d with reached(below + hist[0] + ... + hist[d]); -1: none (total = 0).  *cum = the
+// cumulative mass up to and including the bin.
+inline int quant_pick_bin(const uint64_t hist[256], uint64_t below, uint64_t total, uint64_t P, uint64_t* cum) {
+  if (total == 0) return -1;
+  uint64_t c = below;
+  for (int d = 0; d < 256; ++d) {
+    c += hist[d];
+    if (quant_reached(c, total, P)) {
+      *cum = c;
+      return d;
+    }
+  }
+  return -1;
+}
+int quantile_key_impl(double v, uint64_t* key) {
+  if (!key || std::isnan(v)) return MCL_ERR_INVALID;
+  *key = quant_key(v);
+  return MCL_OK;
+}
+int quantile_value_impl(uint64_t key, double* v) {
+  if (!v) return MCL_ERR_INVALID;
+  *v = quant_value(key);
+  return MCL_OK;
+}
+int quantile_threshold_impl(double p, uint64_t* P) {
+  if (!P || !(p >= 1.0 / 4294967296.0 && p <= 1.0)) return MCL_ERR_INVALID;
+  *P = (uint64_t)std::floor(p * 4294967296.0);   // (the scaling by 2^32 is exact; 1 <= P <= 2^32)
+  return MCL_OK;
+}
+int quantile_reached_impl(uint64_t mass, uint64_t total, uint64_t P, int32_t* reached) {
+  if (!reached) return MCL_ERR_INVALID;
+  *reached = quant_reached(mass, total, P) ? 1 : 0;
+  return MCL_OK;
+}
+// what every query has to satisfy before a handle is looked at: nullptr, or the rule that is broken
+const char* quantile_query_why(const mcl_quantile_query* q) {
+  if (!q) return "null query";
+  if (q->quantity < MCL_Q_X || q->quantity > MCL_Q_RADIUS2) return "unknown quantity";
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(q->centre[k])) return "the centre is not finite";
+  return nullptr;
 }
 
 }  // namespace

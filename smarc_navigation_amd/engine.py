@@ -115,6 +115,49 @@ def temper_target(ess_ratio, n_global):
     return max(1, int(math.ceil(float(ess_ratio) * int(n_global))))
 
 
+Q_X, Q_Y, Q_YAW_DEV, Q_ABS_YAW_DEV, Q_RADIUS2 = 0, 1, 2, 3, 4
+_QUANTITIES = {'x': Q_X, 'y': Q_Y, 'yaw_dev': Q_YAW_DEV, 'abs_yaw_dev': Q_ABS_YAW_DEV, 'radius2': Q_RADIUS2}
+
+
+@dataclasses.dataclass
+class Quantile(object):
+    """mcl_quantile_result as a Python object (include/mcl_quantile.h): the value (NaN: no mass), its key, the mass M(key)
+    at or below it, the total mass S and the particles whose value is not NaN -- Python integers"""
+    value: float
+    key: int
+    mass: int
+    total: int
+    n_used: int
+
+    @staticmethod
+    def from_c(c):
+        return Quantile(float(c.value), int(c.key), int(c.mass), int(c.total), int(c.n_used))
+
+
+@dataclasses.dataclass
+class Credible(object):
+    """what Engine.credible returns: the component-wise median pose (x, y, yaw), the radius that holds a share p of the
+    posterior about `centre` (radius[p], metres) and the heading bound (yaw_halfwidth[p], radians), the particles used"""
+    median: tuple
+    radius: dict
+    yaw_halfwidth: dict
+    n_used: int
+    centre: tuple
+
+
+def make_quantile_query(quantity, centre=None, weighted=False):
+    q = _lib.QuantileQuery()
+    q.quantity = int(_QUANTITIES.get(quantity, quantity)) if isinstance(quantity, str) else int(quantity)
+    if isinstance(quantity, str) and quantity not in _QUANTITIES:
+        raise ValueError('quantity: one of %s' % ', '.join(sorted(_QUANTITIES)))
+    q.weighted = 1 if weighted else 0
+    c = (0.0, 0.0, 0.0) if centre is None else tuple(float(v) for v in centre)
+    if len(c) != 3:
+        raise ValueError('centre: (x, y, yaw)')
+    q.centre[:] = c
+    return q
+
+
 def make_mode_grid(x0, y0, cell, nx, ny, n_yaw):
     g = _lib.ModeGrid()
     g.x0, g.y0, g.cell = float(x0), float(y0), float(cell)
@@ -255,6 +298,69 @@ class Engine(object):
         nm, no = C.c_int32(0), C.c_int64(0)
         self._ck(self.lib.mcl_pose_modes(self.h, C.byref(g), k, out, C.byref(nm), C.byref(no)))
         return [PoseMode(out[j]) for j in range(nm.value)], int(no.value)
+
+    # ---- exact order statistics of the cloud (include/mcl_quantile.h)
+    def cloud_quantiles(self, quantity, probs, centre=None, weighted=False):
+        """the quantiles of a quantity ('x', 'y', 'yaw_dev', 'abs_yaw_dev', 'radius2', or MCL_Q_*) about centre =
+        (x, y, yaw) (odom frame; None: zeros) at up to eight probabilities in [2^-32, 1], all found in the same passes
+        (mcl_cloud_quantiles): a list of Quantile, one per probability.  weighted: by the pending log-weights."""
+        q = make_quantile_query(quantity, centre, weighted)
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = (_lib.QuantileResult * max(p.size, 1))()
+        self._ck(self.lib.mcl_cloud_quantiles(self.h, C.byref(q), _ptr(p), p.size, out))
+        return [Quantile.from_c(out[k]) for k in range(p.size)]
+
+    def cloud_mass(self, quantity, values, centre=None, weighted=False, max_lw=None):
+        """the inverse question (mcl_cloud_mass): dict(mass = M(key(v)) per value, total = S, n_used, fraction = mass / total
+        per value (NaN: no mass)) of THIS shard; integers are Python integers.  weighted: max_lw is the cloud's largest finite
+        log-weight (None: this handle's own, from weight_stats)."""
+        q = make_quantile_query(quantity, centre, weighted)
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if weighted and max_lw is None:
+            ws = self.weight_stats()
+            max_lw = ws.max_lw if ws.argmax_gid >= 0 else -math.inf
+        mass, total, used = np.zeros(max(v.size, 1), np.uint64), C.c_uint64(0), C.c_int64(0)
+        self._ck(self.lib.mcl_cloud_mass(self.h, C.byref(q), float(max_lw) if weighted else 0.0, _ptr(v), v.size, _ptr(mass),
+                                         C.byref(total), C.byref(used)))
+        m, t = [int(x) for x in mass[:v.size]], int(total.value)
+        return dict(mass=m, total=t, n_used=int(used.value), fraction=[x / t if t else math.nan for x in m])
+
+    def cloud_key_hist(self, quantity, prefix, prefix_bits, centre=None, weighted=False, max_lw=0.0):
+        """this shard's masses by the next 8 key bits among the keys whose leading prefix_bits bits equal prefix
+        (mcl_cloud_key_hist): 256 Python integers"""
+        q = make_quantile_query(quantity, centre, weighted)
+        hist = np.zeros(256, np.uint64)
+        self._ck(self.lib.mcl_cloud_key_hist(self.h, C.byref(q), float(max_lw), int(prefix), int(prefix_bits), _ptr(hist)))
+        return [int(x) for x in hist]
+
+    def credible(self, probs=(0.5, 0.95), centre='mean', weighted=False):
+        """a Credible: about centre = 'mean' (mean_cov's x, y, yaw), 'median' (the component-wise median, x and y first) or
+        (x, y, yaw), the radius that holds each share p of the posterior (the correctly rounded square root of the exact
+        quantile of the squared distance) and the half-width of the heading interval that does, and the median pose."""
+        probs = tuple(float(p) for p in probs)
+        if isinstance(centre, str):
+            if centre == 'mean':
+                mean, yaw, _ = self.mean_cov()
+                c = (float(mean[0]), float(mean[1]), float(yaw))
+            elif centre == 'median':
+                mx = self.cloud_quantiles(Q_X, [0.5], None, weighted)[0].value
+                my = self.cloud_quantiles(Q_Y, [0.5], None, weighted)[0].value
+                # (a lower median is a particle's own yaw: a centre inside the cloud wherever the cut at +-pi falls)
+                c = (mx, my, self.cloud_quantiles(Q_YAW_DEV, [0.5], None, weighted)[0].value)
+            else:
+                raise ValueError("credible: centre is 'mean', 'median' or (x, y, yaw)")
+            med_xy = (mx, my) if centre == 'median' else None
+        else:
+            c, med_xy = tuple(float(v) for v in centre), None
+        if med_xy is None:
+            med_xy = (self.cloud_quantiles(Q_X, [0.5], c, weighted)[0].value,
+                      self.cloud_quantiles(Q_Y, [0.5], c, weighted)[0].value)
+        dyaw = self.cloud_quantiles(Q_YAW_DEV, [0.5], c, weighted)[0].value
+        r2 = self.cloud_quantiles(Q_RADIUS2, probs, c, weighted)
+        ay = self.cloud_quantiles(Q_ABS_YAW_DEV, probs, c, weighted)
+        return Credible(median=(med_xy[0], med_xy[1], c[2] + dyaw),
+                        radius={p: math.sqrt(r.value) for p, r in zip(probs, r2)},
+                        yaw_halfwidth={p: r.value for p, r in zip(probs, ay)}, n_used=r2[0].n_used, centre=c)
 
     # ---- particle genealogy and the fixed-lag smoother (include/mcl_history.h)
     def history_bytes(self, depth):
@@ -796,6 +902,47 @@ def group_temper(engines, ess_ratio=0.5, apply=True, n_target=None):
     c = _lib.TemperRes()
     _lib.check(lib.mcl_group_temper(hs, ns, nt, 1 if apply else 0, C.byref(c)), engines[0].h)
     return TemperResult.from_c(c)
+
+
+def quantile_key(v):
+    """the order-preserving 64-bit key of v + 0.0 (mcl_quantile_key: host arithmetic); NaN is refused"""
+    k = C.c_uint64(0)
+    _lib.check(_lib.load().mcl_quantile_key(float(v), C.byref(k)))
+    return int(k.value)
+
+
+def quantile_value(key):
+    """the double a key stands for (mcl_quantile_value: host arithmetic)"""
+    v = C.c_double(0.0)
+    _lib.check(_lib.load().mcl_quantile_value(int(key), C.byref(v)))
+    return float(v.value)
+
+
+def quantile_threshold(p):
+    """P = floor(p 2^32), 2^-32 <= p <= 1 (mcl_quantile_threshold: host arithmetic)"""
+    t = C.c_uint64(0)
+    _lib.check(_lib.load().mcl_quantile_threshold(float(p), C.byref(t)))
+    return int(t.value)
+
+
+def quantile_reached(mass, total, P):
+    """2^32 mass >= P total in 128-bit integers (mcl_quantile_reached: host arithmetic)"""
+    r = C.c_int32(0)
+    _lib.check(_lib.load().mcl_quantile_reached(int(mass), int(total), int(P), C.byref(r)))
+    return bool(r.value)
+
+
+def group_cloud_quantiles(engines, quantity, probs, centre=None, weighted=False):
+    """Engine.cloud_quantiles over shards that together hold the cloud (mcl_group_cloud_quantiles): the unsharded call's
+    result bit for bit, for any split.  A list of Quantile."""
+    lib = _lib.load()
+    ns = len(engines)
+    hs = (C.c_void_p * ns)(*[e.h for e in engines])
+    q = make_quantile_query(quantity, centre, weighted)
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    out = (_lib.QuantileResult * max(p.size, 1))()
+    _lib.check(lib.mcl_group_cloud_quantiles(hs, ns, C.byref(q), _ptr(p), p.size, out), engines[0].h)
+    return [Quantile.from_c(out[k]) for k in range(p.size)]
 
 
 def merge_weight_stats(parts):

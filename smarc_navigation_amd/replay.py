@@ -26,6 +26,7 @@ auv_ekf_localization/rosbags/rosbag_handler.py:8-19):
 """
 import argparse
 import json
+import math
 
 import numpy as np
 
@@ -261,6 +262,20 @@ def synthetic_stream(n_steps=3000, current=(0.0, 0.0), yaw_rate_bias=0.0, gps_ev
     return st
 
 
+def credible_summary(prob, radii, est_xyz, truth_xyz=None):
+    """what --credible adds to a summary: the probability, the median of the stated radii and, against a truth, the share of
+    the published poses whose true position lay inside the stated radius -- the filter's calibration; a well-tuned filter
+    gives about `prob`.  A radius that is NaN (no particle with a position) contains nothing."""
+    radii = np.asarray(radii, dtype=np.float64)
+    out = dict(credible_prob=float(prob), credible_pings=int(radii.size))
+    if truth_xyz is not None and radii.size:
+        fin = radii[np.isfinite(radii)]
+        err = np.hypot(np.asarray(est_xyz)[:, 0] - np.asarray(truth_xyz)[:, 0], np.asarray(est_xyz)[:, 1] - np.asarray(truth_xyz)[:, 1])
+        out['credible_radius_median'] = float(np.median(fin)) if fin.size else float('nan')
+        out['credible_containment'] = float(np.mean(err <= radii))
+    return out
+
+
 def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0,
            fix_period=0.0, fix_latency=0.0, fix_seed=0):
     """Drive the node with a recorded stream; returns dict(pf_xyz[n_pub,3], pub_idx, summary).  smooth_lag > 0: also
@@ -283,7 +298,7 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
     pf.start_timing(float(stream['t0']) if 't0' in stream else float(stream['stamp'][0]) - 0.02)
     gps_at = {int(k): j for j, k in enumerate(stream['gps_idx'])} if 'gps_idx' in stream else {}
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])} if 'mbes_idx' in stream else {}
-    pub_idx, pf_xyz = [], []
+    pub_idx, pf_xyz, cred_r = [], [], []
     stats = DRStats() if ('gps_idx' in stream and 'dr_xyz' in stream) else None
     fixes = make_fixes(stream, m2o, fix_period, fix_latency, pf.fix_std, fix_seed) if fix_period > 0 else []
     next_fix = 0
@@ -331,6 +346,8 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
             p = tr.odom_corrected[-1].pose.pose.position
             pub_idx.append(k)
             pf_xyz.append([p.x, p.y, p.z])
+            if pf.credible_prob > 0.0:
+                cred_r.append(float(pf.last_credible['radius']))
             if stats is not None:
                 stats.add(2, stream['stamp'][k], [p.x, p.y, p.z])
     pf_xyz = np.array(pf_xyz)
@@ -358,6 +375,11 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
         summary['regularise_scale'], summary['regularise_shrink'] = float(pf.regularise_scale), bool(pf.regularise_shrink)
         summary['regularise_calls'] = int(pf.regularise_calls)
         summary['regularise_h_mean'] = float(np.mean(pf.regularise_hs)) if pf.regularise_hs else 0.0
+    if pf.credible_prob > 0.0:
+        # credible region (include/mcl_quantile.h): the radius that held credible_prob of the cloud about every published pose
+        out_cred = np.array(cred_r)
+        summary.update(credible_summary(pf.credible_prob, out_cred, pf_xyz,
+                                        np.asarray(stream['truth_xyz'])[pub_idx] if 'truth_xyz' in stream else None))
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -463,21 +485,26 @@ def replay_bag(path, params=None, m2o=None, utm2map=None, grid=None, mesh=None, 
 def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=1.0, m2o=None, yaw=(-np.pi, np.pi),
                    process_cov=(0.01, 0.01, 0, 0, 0, 1e-4), resample_cov=(0.04, 0.04, 0, 0, 0, 1e-3), alpha_slow=0.001,
                    alpha_fast=0.1, max_fraction=0.1, inject=True, estimate='mean', mode_cell=1.0, mode_n_yaw=36,
-                   smooth_lag=0):
+                   smooth_lag=0, credible=0.0):
     """Global localisation with kidnap recovery on a recorded stream (--recover): the cloud starts uniform over the map's
     footprint, and every ping runs the separate calls  predict ... -> update_mbes -> weight_stats -> resample ->
     inject_uniform(fraction)  with the fraction of recovery.AugmentedMCL (the likelihood per valid beam, a short-term
     against a long-term average).  The node class is not involved.  estimate='mean' publishes mcl_mean_cov's pose;
     'mode' the heaviest cluster's (mode 0 of mcl_pose_modes on a lattice of mode_cell metres x mode_n_yaw bins over the
-    map's footprint) when there is one, otherwise the mean.  Returns dict(pf_xyz[m,3] published pose after every ping,
+    map's footprint) when there is one, otherwise the mean; 'median' the component-wise median of x and y (exact order
+    statistics, include/mcl_quantile.h; z is the mean's).  credible = P > 0: after every ping also the radius that holds P
+    of the cloud about the published pose (out['credible_radius']); with a truth the summary gains credible_radius_median
+    and credible_containment (credible_summary).  Returns dict(pf_xyz[m,3] published pose after every ping,
     pub_idx, fractions[m], injected[m], log_lik_per_beam[m], n_eff[m], summary).  smooth_lag > 0: also out['smooth'], the
     lag-smooth_lag smoothed track (SmoothTrack), one entry per ping; an injected particle inherits its slot's past."""
     from . import engine as eng
     from . import recovery
     if 'mbes_idx' not in stream or (grid is None and mesh is None):
         raise ValueError('replay_recover: needs a stream with MBES pings and a map')
-    if estimate not in ('mean', 'mode'):
-        raise ValueError("replay_recover: estimate must be 'mean' or 'mode'")
+    if estimate not in ('mean', 'mode', 'median'):
+        raise ValueError("replay_recover: estimate must be 'mean', 'mode' or 'median'")
+    if not 0.0 <= credible <= 1.0:
+        raise ValueError('replay_recover: credible must lie in [0, 1]')
     e = eng.Engine(int(particles), process_cov=process_cov, resample_cov=resample_cov, m2o=m2o, seed=seed)
     if grid is not None:
         e.set_map_grid(grid['z'], grid['origin'], float(grid['res']))
@@ -492,6 +519,8 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
     r_max = float(stream['mbes_range_max']) if 'mbes_range_max' in stream else 100.0
     t_prev = float(stream['t0']) if 't0' in stream else float(stream['stamp'][0]) - 0.02
     out = dict(pf_xyz=[], pub_idx=[], fractions=[], injected=[], log_lik_per_beam=[], n_eff=[])
+    if credible > 0.0:
+        out['credible_radius'] = []
     for k in range(len(stream['stamp'])):
         t = float(stream['stamp'][k])
         e.predict(stream['v'][k], float(stream['wz'][k]), stream['q'][k], float(stream['z'][k]), t - t_prev, stamp=t)
@@ -516,6 +545,11 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
             modes = e.pose_modes(mode_cell, k=1, grid=lattice)[0]
             if modes:
                 pose = modes[0].mean[:3]
+        if estimate == 'median':
+            pose = np.array([e.cloud_quantiles('x', [0.5])[0].value, e.cloud_quantiles('y', [0.5])[0].value, pose[2]])
+        if credible > 0.0:
+            r2 = e.cloud_quantiles('radius2', [credible], (float(pose[0]), float(pose[1]), 0.0))[0].value
+            out['credible_radius'].append(math.sqrt(r2))
         out['pf_xyz'].append(pose)
         out['pub_idx'].append(k)
     track = smooth.finish() if smooth is not None else None
@@ -528,6 +562,10 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
         if 'truth_xyz' in stream:
             ref = np.asarray(stream['truth_xyz'])[out['pub_idx']]
             summary['final_error_vs_truth'] = float(np.linalg.norm(out['pf_xyz'][-1, :2] - ref[-1, :2]))
+    if credible > 0.0:
+        summary.update(credible_summary(credible, out['credible_radius'], out['pf_xyz'],
+                                        np.asarray(stream['truth_xyz'])[out['pub_idx']]
+                                        if 'truth_xyz' in stream and len(out['pub_idx']) else None))
     if track is not None:
         out['smooth'] = track
         smooth_summary(track, stream, summary)
@@ -563,8 +601,14 @@ def main(argv=None):
                     help='global localisation with kidnap recovery (replay_recover): uniform start over the map, '
                          'augmented-MCL injection; needs --map-grid and MBES pings in the stream')
     ap.add_argument('--sigma', type=float, default=1.0, help='--recover: MBES range sigma')
-    ap.add_argument('--estimate', choices=('mean', 'mode'), default='mean',
-                    help='--recover: publish the mean pose, or the heaviest cluster of the cloud (mcl_pose_modes)')
+    ap.add_argument('--credible', type=float, default=0.0, metavar='P',
+                    help='after every published pose also ask the cloud for the radius that holds the share P of the posterior '
+                         'about it (the node\'s credible_prob, include/mcl_quantile.h); with a truth the summary gains '
+                         'credible_radius_median and credible_containment, the share of poses whose true position lay inside '
+                         'the stated radius (a well-tuned filter gives about P); 0: off')
+    ap.add_argument('--estimate', choices=('mean', 'mode', 'median'), default='mean',
+                    help='--recover: publish the mean pose, the heaviest cluster of the cloud (mcl_pose_modes), or the component-wise '
+                         'median of x and y (mcl_cloud_quantiles)')
     ap.add_argument('--smooth', type=int, default=0, metavar='LAG',
                     help='also emit the fixed-lag smoothed track: every resampled ping as the LAG pings after it correct it '
                          '(particle genealogy, include/mcl_history.h); --out then writes it next to the filtered track')
@@ -612,6 +656,10 @@ def main(argv=None):
         ap.error('--regularise: only with the plain stream replay')
     if a.no_regularise_shrink and not a.regularise > 0:
         ap.error('--no-regularise-shrink needs --regularise SCALE')
+    if not 0.0 <= a.credible <= 1.0:
+        ap.error('--credible: P must lie in [0, 1]')
+    if a.credible > 0 and a.bag:
+        ap.error('--credible: not with --bag')
     if not 0.0 <= a.temper_ess <= 1.0:
         ap.error('--temper-ess: RATIO must lie in [0, 1]')
     if a.temper_ess > 0 and (a.bag or a.recover):
@@ -646,7 +694,7 @@ def main(argv=None):
     grid = dict(np.load(a.map_grid)) if a.map_grid else None
     if a.recover:
         res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=a.sigma, m2o=m2o,
-                             estimate=a.estimate, smooth_lag=a.smooth)
+                             estimate=a.estimate, smooth_lag=a.smooth, credible=a.credible)
         if a.out:
             np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz'], res['fractions']]), delimiter=',',
                        header='step,x,y,z,injected_fraction')
@@ -664,6 +712,8 @@ def main(argv=None):
             params.update(drift_init_std=str([float(x) for x in a.drift_init_std]))
         if a.drift_walk_std:
             params.update(drift_walk_std=str([float(x) for x in a.drift_walk_std]))
+    if a.credible > 0:
+        params.update(credible_prob=a.credible)
     if a.regularise > 0:
         params.update(regularise_scale=a.regularise, regularise_shrink=not a.no_regularise_shrink)
     if a.fix_period > 0:
