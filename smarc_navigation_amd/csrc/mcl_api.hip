@@ -15,10 +15,8 @@
 #include "mcl_host_drift.h"
 #include "mcl_host_regularise.h"
 #include "mcl_host_quantile.h"
-// global localisation and kidnap recovery: uniform draws, weight statistics (include/mcl_recovery.h)
-#include "mcl_recovery.h"
-// (the kernels of mcl_pose_modes, include/mcl_modes.h, come with mcl_host.h: csrc/mcl_modes.h)
-
+#include "mcl_host_recovery.h"
+#include "mcl_host_modes.h"
 
 // dead-reckoning integrator (host only; uses euler_from_quat above)
 #include "mcl_dr_impl.h"
@@ -963,45 +961,7 @@ int mcl_mbes_visit_order(mcl_handle* h, uint32_t* slots, int32_t* sorted) {
   return MCL_OK;
 }
 
-// ---- global localisation and kidnap recovery (include/mcl_recovery.h)
-namespace {
-// the argument block of k_uniform_state from a caller's box: bounds checked, the MAP frame resolved against cfg.m2o
-int uniform_args(mcl_handle* h, const mcl_box* box, uint32_t purpose, uint32_t step, const char* who, UniformArgs& a) {
-  const char* reason;
-  const int rc = check_box(box, h->cfg.m2o, &reason);
-  if (rc != MCL_OK) return fail(h, rc, std::string(who) + ": " + reason);
-  const double b[6] = {box->x_min, box->x_max, box->y_min, box->y_max, box->yaw_min, box->yaw_max};
-  memset(&a, 0, sizeof a);
-  for (int c = 0; c < 3; ++c) {
-    a.lo[c] = b[2 * c];
-    a.hi[c] = b[2 * c + 1];
-    a.w[c] = b[2 * c + 1] - b[2 * c];
-  }
-  if (box->frame == MCL_FRAME_MAP) {
-    const double* m = h->cfg.m2o;
-    a.r00 = m[0];
-    a.r01 = m[1];
-    a.r10 = m[4];
-    a.r11 = m[5];
-    a.tx = m[3];
-    a.ty = m[7];
-    a.theta = std::atan2(m[4], m[0]);
-    a.xform = !(m[0] == 1.0 && m[1] == 0.0 && m[4] == 0.0 && m[5] == 1.0 && m[3] == 0.0 && m[7] == 0.0);
-  }
-  a.k0 = (uint32_t)h->cfg.seed;
-  a.k1 = (uint32_t)(h->cfg.seed >> 32);
-  a.step = step;
-  a.purpose = purpose;
-  a.gid0 = h->goff;
-  return MCL_OK;
-}
-// REPLAY uniforms (n x per doubles, per <= 6) into the replay buffer
-int upload_replay_uniforms(mcl_handle* h, const double* u, int per) {
-  RESERVE(h, h->replay_dev, 6 * (size_t)h->n);
-  return upload(h, h->replay_dev, u, sizeof(double) * (size_t)per * (size_t)h->n);
-}
-}  // namespace
-
+// ---- global localisation and kidnap recovery (include/mcl_recovery.h; host: mcl_host_recovery.h, kernels: csrc/mcl_recovery.h)
 int mcl_map_bounds(mcl_handle* h, double xy_min_max[4]) {
   if (!h || !xy_min_max) return MCL_ERR_INVALID;
   RET_IF(need_map(h, "map_bounds"));
@@ -1013,19 +973,7 @@ int mcl_init_particles_uniform(mcl_handle* h, const mcl_box* box, const double* 
   if (!h) return MCL_ERR_INVALID;
   if (!box) return fail(h, MCL_ERR_INVALID, "init_particles_uniform: null box");
   RET_IF(set_device(h));
-  UniformArgs a;
-  RET_IF(uniform_args(h, box, 5u, 0u, "init_particles_uniform", a));
-  const double* rp = nullptr;
-  if (h->cfg.rng_mode == MCL_RNG_REPLAY) {
-    if (!replay_uniforms) return fail(h, MCL_ERR_INVALID, "init_particles_uniform: REPLAY mode needs n x 3 uniforms");
-    RET_IF(upload_replay_uniforms(h, replay_uniforms, 3));
-    rp = h->replay_dev;
-  }
-  RET_IF(state_overwritten(h));
-  t_begin(h, MCL_K_NOISE);
-  k_uniform_state<false><<<grid_for(h->n), MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, rp, nullptr);
-  t_end(h);
-  HIPCHK(h, hipGetLastError());
+  RET_IF(recovery_init_uniform(h, box, replay_uniforms));
   filter_restarted(h);
   h->have_state = true;
   history_clear(h);
@@ -1036,29 +984,7 @@ int mcl_weight_stats(mcl_handle* h, mcl_wstats* out) {
   if (!h || !out) return MCL_ERR_INVALID;
   if (!h->have_lw) return fail(h, MCL_ERR_STATE, "weight_stats: no log-weights (call an update first)");
   RET_IF(set_device(h));
-  const long long ntiles = (h->n + WS_TILE - 1) / WS_TILE;
-  static_assert(sizeof(WsPartial) % sizeof(double) == 0, "the tile records lie behind the result words of one double array");
-  RESERVE(h, h->wstats_dev, WS_OUT_WORDS + sizeof(WsPartial) / sizeof(double) * (size_t)ntiles);
-  WsPartial* part = reinterpret_cast<WsPartial*>(h->wstats_dev + WS_OUT_WORDS);
-  t_begin(h, MCL_K_NORMALISE);
-  k_wstats_partial<<<(unsigned)ntiles, MCL_BLOCK, 0, h->stream>>>(h->lw, h->n, h->goff, part);
-  k_wstats_final<<<1, MCL_BLOCK, 0, h->stream>>>(part, ntiles, state_ptrs(h->state[h->cur], h->n), h->goff, h->wstats_dev);
-  t_end(h);
-  HIPCHK(h, hipGetLastError());
-  double r[11];
-  HIPCHK(h, hipMemcpyAsync(r, h->wstats_dev, sizeof r, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  int64_t words[2];
-  memcpy(words, r + 3, sizeof words);
-  out->n = h->n;
-  out->n_live = words[1];
-  out->argmax_gid = words[0];
-  out->max_lw = r[0];
-  out->sum_w = r[1];
-  out->sum_w2 = r[2];
-  for (int c = 0; c < 6; ++c) out->map_pose[c] = r[5 + c];
-  wstats_finish(out);
-  return MCL_OK;
+  return recovery_weight_stats(h, out);
 }
 
 int mcl_weight_stats_merge(const mcl_wstats* parts, int32_t n_parts, mcl_wstats* out) {
@@ -1072,39 +998,10 @@ int mcl_inject_uniform(mcl_handle* h, double fraction, const mcl_box* box, const
   if (!(fraction >= 0.0 && fraction <= 1.0)) return fail(h, MCL_ERR_INVALID, "inject_uniform: fraction outside [0, 1]");
   if (h->have_lw) return fail(h, MCL_ERR_STATE, "inject_uniform: log-weights pending (resample first: they describe the particles as they are)");
   RET_IF(set_device(h));
-  UniformArgs a;
-  RET_IF(uniform_args(h, box, 6u, h->step_inject, "inject_uniform", a));
-  a.fraction = fraction;
-  if (h->cfg.rng_mode == MCL_RNG_REPLAY && !replay_uniforms)
-    return fail(h, MCL_ERR_INVALID, "inject_uniform: REPLAY mode needs n x 4 uniforms");
-  if (fraction == 0.0) {
-    if (n_injected) *n_injected = 0;
-    return MCL_OK;
-  }
-  const double* rp = nullptr;
-  if (h->cfg.rng_mode == MCL_RNG_REPLAY) {
-    RET_IF(upload_replay_uniforms(h, replay_uniforms, 4));
-    rp = h->replay_dev;
-  }
-  RESERVE(h, h->inject_cnt, 1 + MCL_MAX_GRID);
-  RET_IF(state_overwritten(h));
-  const int grid = grid_for(h->n);
-  t_begin(h, MCL_K_NOISE);
-  k_uniform_state<true><<<grid, MCL_BLOCK, 0, h->stream>>>(state_ptrs(h->state[h->cur], h->n), h->n, a, rp, h->inject_cnt + 1);
-  if (n_injected) k_count_final<<<1, MCL_BLOCK, 0, h->stream>>>(h->inject_cnt + 1, grid, h->inject_cnt);
-  t_end(h);
-  HIPCHK(h, hipGetLastError());
-  h->step_inject++;
-  if (n_injected) {
-    u64 cnt = 0;
-    HIPCHK(h, hipMemcpyAsync(&cnt, h->inject_cnt, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *n_injected = (int64_t)cnt;
-  }
-  return MCL_OK;
+  return recovery_inject(h, fraction, box, replay_uniforms, n_injected);
 }
 
-// ---- dominant modes of the cloud (include/mcl_modes.h; kernels: csrc/mcl_modes.h)
+// ---- dominant modes of the cloud (include/mcl_modes.h; host: mcl_host_modes.h, kernels: csrc/mcl_modes.h)
 int mcl_mode_grid_check(const mcl_mode_grid* g, int64_t* n_cells) { return mode_grid_check_impl(g, n_cells, nullptr); }
 
 int mcl_pose_modes(mcl_handle* h, const mcl_mode_grid* g, int32_t k_max, mcl_mode* modes, int32_t* n_modes,
@@ -1118,76 +1015,7 @@ int mcl_pose_modes(mcl_handle* h, const mcl_mode_grid* g, int32_t k_max, mcl_mod
   if (h->world > 1) return fail(h, MCL_ERR_UNSUPPORTED, "pose_modes: a sharded cloud (world > 1) is not supported");
   if (!h->have_state) return fail(h, MCL_ERR_STATE, "pose_modes: no particles (call mcl_init_particles / mcl_set_particles first)");
   RET_IF(set_device(h));
-  const int k = k_max, gp = grid_for(h->n), gc = grid_for(n_cells);
-  RESERVE(h, h->modes_hist, (size_t)n_cells);
-  RESERVE(h, h->modes_score, (size_t)n_cells);
-  RESERVE(h, h->modes_cell, (size_t)h->n);
-  RESERVE(h, h->modes_rec, 2 * (size_t)MCL_MAX_GRID);
-  RESERVE(h, h->modes_part, (size_t)MODES_MAX_K * MODES_SUMS * MCL_MAX_GRID);
-  RESERVE(h, h->modes_res, MODES_RES_WORDS);
-  ModeLattice lat;
-  lat.x0 = g->x0;
-  lat.y0 = g->y0;
-  lat.cell = g->cell;
-  lat.dyaw = (2.0 * MCL_PI) / (double)g->n_yaw;
-  lat.nx = g->nx;
-  lat.ny = g->ny;
-  lat.n_yaw = g->n_yaw;
-  u64* rec_out = h->modes_rec;
-  u64* rec_key = h->modes_rec + MCL_MAX_GRID;
-  ModePeak* peaks = reinterpret_cast<ModePeak*>(h->modes_res + MODES_RES_PEAKS);
-  const StatePtrs st = state_ptrs(h->state[h->cur], h->n);
-  t_begin(h, MCL_K_MEAN_COV);
-  HIPCHK(h, hipMemsetAsync(h->modes_hist, 0, sizeof(u32) * (size_t)n_cells, h->stream));
-  k_modes_hist<<<gp, MCL_BLOCK, 0, h->stream>>>(st, h->n, lat, h->modes_cell, h->modes_hist, rec_out);
-  k_count_final<<<1, MCL_BLOCK, 0, h->stream>>>(rec_out, gp, reinterpret_cast<u64*>(h->modes_res + MODES_RES_OUTSIDE));
-  k_modes_score<<<gc, MCL_BLOCK, 0, h->stream>>>(h->modes_hist, lat.nx, lat.ny, lat.n_yaw, (u32)n_cells, h->modes_score, rec_key);
-  k_modes_peak_final<<<1, MCL_BLOCK, 0, h->stream>>>(rec_key, gc, lat.nx, lat.ny, peaks, 0);
-  for (int m = 1; m < k; ++m) {
-    k_modes_peak_partial<<<gc, MCL_BLOCK, 0, h->stream>>>(h->modes_score, lat.nx, lat.ny, lat.n_yaw, (u32)n_cells, peaks, m, rec_key);
-    k_modes_peak_final<<<1, MCL_BLOCK, 0, h->stream>>>(rec_key, gc, lat.nx, lat.ny, peaks, m);
-  }
-  k_modes_moments<<<gp, MCL_BLOCK, 0, h->stream>>>(st, h->n, h->modes_cell, lat, peaks, k, h->modes_part);
-  k_sum_final<<<k * MODES_SUMS, MCL_BLOCK, 0, h->stream>>>(h->modes_part, gp, h->modes_res);
-  t_end(h);
-  HIPCHK(h, hipGetLastError());
-  double res[MODES_RES_WORDS];
-  HIPCHK(h, hipMemcpyAsync(res, h->modes_res, sizeof res, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  ModePeak pk[MODES_MAX_K];
-  memcpy(pk, res + MODES_RES_PEAKS, sizeof pk);
-  if (n_outside) {
-    u64 cnt = 0;
-    memcpy(&cnt, res + MODES_RES_OUTSIDE, sizeof cnt);
-    *n_outside = (int64_t)cnt;
-  }
-  int found = 0;
-  for (; found < k && pk[found].score != 0u; ++found) {
-    const double* a = res + found * MODES_SUMS;
-    const ModePeak& p = pk[found];
-    mcl_mode& o = modes[found];
-    const double cnt = a[0];
-    const double cx = g->x0 + ((double)p.ix + 0.5) * g->cell, cy = g->y0 + ((double)p.iy + 0.5) * g->cell;
-    const double mdx = a[1] / cnt, mdy = a[2] / cnt;
-    o.count = (int64_t)cnt;
-    o.score = (int64_t)p.score;
-    o.ix = p.ix;
-    o.iy = p.iy;
-    o.iyaw = p.iyaw;
-    o.reserved = 0;
-    o.mean6[0] = cx + mdx;
-    o.mean6[1] = cy + mdy;
-    o.mean6[2] = a[3] / cnt;
-    o.mean6[3] = a[4] / cnt;
-    o.mean6[4] = a[5] / cnt;
-    o.mean6[5] = std::atan2(a[6], a[7]);
-    o.cov_xy[0] = a[8] / cnt - mdx * mdx;
-    o.cov_xy[1] = a[9] / cnt - mdx * mdy;
-    o.cov_xy[2] = a[10] / cnt - mdy * mdy;
-    o.yaw_R = std::hypot(a[6], a[7]) / cnt;
-  }
-  *n_modes = found;
-  return MCL_OK;
+  return modes_run(h, g, k_max, n_cells, modes, n_modes, n_outside);
 }
 
 // ---- particle genealogy (include/mcl_history.h; host: mcl_host_history.h, kernels: csrc/mcl_history.h)

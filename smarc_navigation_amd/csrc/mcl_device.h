@@ -69,6 +69,46 @@ __device__ __forceinline__ T wave_scan_incl_dpp(T v) {
 // the last bit of a floating-point sum is compared)
 template <class T>
 __device__ __forceinline__ T wave_sum_dpp(T v) { return readlane63(wave_scan_incl_dpp(v)); }
+
+// The fixed tree of the moment kernels (k_modes_moments, k_history_frame, k_drift_moments, k_reg_moments): the order of
+// every addition between a lane's term and the published sum, a function of the particle count alone -- which is what
+// makes those sums reproducible, and what tests/test_gpu_moment_tree.py pins bit for bit against a restatement in numpy.
+//   1. wave: wave_sum_dpp of the 64 terms of one grid-stride iteration (a lane that does not count contributes +0.0).
+//      wave_scan_incl_dpp adds, inside each row of 16 lanes, the lane 1, then 2, then 4, then 8 below (a lane without a
+//      source adds +0.0); then lane 15 into row 1 and lane 47 into row 3, then lane 31 into rows 2 and 3.  Lane 63 holds
+//      the sum.
+//   2. iterations: lane 0 adds that sum to its wave's accumulator acc[wave][row] (LDS, +0.0 at the start), one
+//      iteration after the other.
+//   3. workgroup: ((acc[0] + acc[1]) + acc[2]) + acc[3], stored as part[row * gridDim.x + blockIdx.x].
+//   4. grid: k_sum_final (mcl_kernels.h), one workgroup per row: thread t adds records t, t + 256, ... in index order to
+//      +0.0, then block_sum -- a __shfl_down tree (offsets 32 ... 1) per wave and one more over the four wave sums.
+// The grid is grid_for(n) workgroups of MCL_BLOCK.  A kernel declares __shared__ double acc[MCL_BLOCK / MCL_WAVE][rows]
+// and calls tree_zero once, tree_add(acc, row, term) from whole waves for every term, tree_flush once.  Zeroing and
+// flushing stride by the workgroup's size, written NW * MCL_WAVE (acc has a row per wave) and not read from blockDim.x:
+// read inside a __device__ function, blockDim.x is compiled in its general form (a partial last workgroup) and not as
+// the kernel's own uniform size, which takes the main loop's stride out of the scalar registers (10 VGPRs more).
+template <int NW, int NS>
+__device__ __forceinline__ void tree_zero(double (&acc)[NW][NS]) {
+  for (int t = threadIdx.x; t < NW * NS; t += NW * MCL_WAVE) (&acc[0][0])[t] = 0.0;
+  __syncthreads();
+}
+template <int NW, int NS>
+__device__ __forceinline__ void tree_add(double (&acc)[NW][NS], int row, double term) {
+  const double r = wave_sum_dpp(term);
+  if ((threadIdx.x & 63) == 0) acc[threadIdx.x >> 6][row] += r;
+}
+// the first `rows` rows, into part[rows][gridDim.x]
+template <int NW, int NS>
+__device__ __forceinline__ void tree_flush(double (&acc)[NW][NS], int rows, double* __restrict__ part) {
+  __syncthreads();
+  for (int t = threadIdx.x; t < rows; t += NW * MCL_WAVE) {
+    double r = acc[0][t];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) r += acc[w][t];
+    part[(size_t)t * gridDim.x + blockIdx.x] = r;
+  }
+}
+
 template <class T>
 __device__ __forceinline__ T wave_sum(T v) {
   if constexpr (std::is_integral<T>::value) {

@@ -4,8 +4,9 @@
 #pragma once
 #include "mcl_kernels.h"
 #include "mcl_history.h"
+#include "mcl_regularise.h"
 
-#define DRIFT_SUMS 9        // e0, e1, e2, e0 e0, e0 e1, e0 e2, e1 e1, e1 e2, e2 e2  (e = d - the drift of slot 0)
+#define DRIFT_SUMS 9        // e0, e1, e2, then e_r e_c at 3 + reg_packed(r, c): e0 e0, e1 e0, e1 e1, e2 e0, e2 e1, e2 e2  (e = d - the drift of slot 0)
 #define DRIFT_RES_WORDS 12  // the DRIFT_SUMS sums, then the shift (the drift of slot 0)
 
 struct DriftDraw {
@@ -91,47 +92,13 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_drift_gather(HistMap m, u32 n, do
 }
 
 // ------------------------------------------------------------------ moments
-// The nine sums about the drift of slot 0, in the fixed tree of k_modes_moments / k_history_frame: per wave iteration
-// the nine terms (zero in the lanes past n) are summed across the wave in the scan's fixed order and added, by lane 0,
-// to the wave's LDS accumulator; the workgroup's four accumulators are added in wave order into one record per
-// workgroup -- k_sum_final adds the records in index order.  The grid follows from n alone (grid_for).
+// The nine sums about the drift of slot 0: mcl_regularise.h's moments of three values, none of them an angle.
 __global__ void __launch_bounds__(MCL_BLOCK) k_drift_moments(const double* __restrict__ cx, const double* __restrict__ cy,
                                                              const double* __restrict__ bw, long long n,
                                                              double* __restrict__ part /*[DRIFT_SUMS][grid]*/,
                                                              double* __restrict__ shift_out) {
-#pragma clang fp contract(off)
+  static_assert(DRIFT_SUMS == 3 + 3 * (3 + 1) / 2, "the rows moments_about_slot0<3> writes");
   __shared__ double acc[MCL_BLOCK / MCL_WAVE][DRIFT_SUMS];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < (MCL_BLOCK / MCL_WAVE) * DRIFT_SUMS) (&acc[0][0])[threadIdx.x] = 0.0;
-  __syncthreads();
-  const double s0 = cx[0], s1 = cy[0], s2 = bw[0];
-  for (long long base = blockIdx.x * (long long)blockDim.x + (threadIdx.x & ~63); base < n;
-       base += (long long)gridDim.x * blockDim.x) {
-    const long long i = base + lane;
-    double b[3] = {0.0, 0.0, 0.0};
-    if (i < n) {
-      b[0] = cx[i] - s0;
-      b[1] = cy[i] - s1;
-      b[2] = bw[i] - s2;
-    }
-#pragma unroll
-    for (int j = 0; j < DRIFT_SUMS; ++j) {
-      // (the six products are formed where they are summed: fewer live registers)
-      const double t = j < 3 ? b[j] : (j < 6 ? b[0] * b[j - 3] : (j < 8 ? b[1] * b[j - 5] : b[2] * b[2]));
-      const double r = wave_sum_dpp(t);
-      if (lane == 0) acc[wv][j] += r;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < DRIFT_SUMS) {
-    double r = acc[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < MCL_BLOCK / MCL_WAVE; ++k) r += acc[k][threadIdx.x];
-    part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = r;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    shift_out[0] = s0;
-    shift_out[1] = s1;
-    shift_out[2] = s2;
-  }
+  const double* const v[3] = {cx, cy, bw};
+  moments_about_slot0<3, false>(acc, v, n, blockDim.x, part, shift_out);
 }

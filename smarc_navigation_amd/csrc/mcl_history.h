@@ -94,13 +94,11 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_history_count0(const u32* __restr
 }
 
 // One frame of the backward walk, one pass over its slots: the count-weighted sums of the slots with c > 0, and, when an
-// older frame follows, c_next[parent[s]] += c[s] (C_next zeroed by the caller; integer atomics).  The sums follow
-// k_modes_moments: per wave iteration the eight terms, zero in the lanes with c == 0, are summed across the wave in the
-// scan's fixed order and added, by lane 0, to the wave's LDS accumulator; the workgroup's four accumulators are added in
-// wave order into one record per workgroup -- k_sum_final adds the records in index order.  The grid follows from n alone,
-// so the tree is a function of (frames, link, n).  A wave whose 64 slots all have c == 0 reads their counts and nothing
-// else -- which pays only where whole waves are empty: the surviving ancestors are scattered over the slots, and at 1 M
-// particles nearly every wave still holds one 64 frames back (measured).
+// older frame follows, c_next[parent[s]] += c[s] (C_next zeroed by the caller; integer atomics).  The sums are the fixed
+// tree of mcl_device.h: the eight terms about slot 0 of the frame, zero in the lanes with c == 0.  A wave whose 64 slots
+// all have c == 0 reads their counts and nothing else -- which pays only where whole waves are empty: the surviving
+// ancestors are scattered over the slots, and at 1 M particles nearly every wave still holds one 64 frames back
+// (measured).
 __global__ void __launch_bounds__(MCL_BLOCK) k_history_frame(const u32* __restrict__ C, const u32* __restrict__ parent,
                                                              u32* __restrict__ C_next, const double* __restrict__ fx,
                                                              const double* __restrict__ fy, const double* __restrict__ fyaw,
@@ -108,9 +106,8 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_history_frame(const u32* __restri
                                                              double* __restrict__ shift_out) {
 #pragma clang fp contract(off)
   __shared__ double acc[MCL_BLOCK / MCL_WAVE][HIST_SUMS];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < (MCL_BLOCK / MCL_WAVE) * HIST_SUMS) (&acc[0][0])[threadIdx.x] = 0.0;
-  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  tree_zero(acc);
   const double x0 = fx[0], y0 = fy[0];
   for (u32 base = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < n; base += gridDim.x * blockDim.x) {
     const u32 s = base + lane;
@@ -127,17 +124,10 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_history_frame(const u32* __restri
 #pragma unroll
     for (int j = 0; j < HIST_SUMS; ++j) {
       const double t = j < 4 ? w * b[j] : (j == 4 ? w * (b[0] * b[0]) : (j == 5 ? w * (b[0] * b[1]) : (j == 6 ? w * (b[1] * b[1]) : (c != 0u ? 1.0 : 0.0))));
-      const double r = wave_sum_dpp(t);
-      if (lane == 0) acc[wv][j] += r;
+      tree_add(acc, j, t);
     }
   }
-  __syncthreads();
-  if (threadIdx.x < HIST_SUMS) {
-    double r = acc[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < MCL_BLOCK / MCL_WAVE; ++k) r += acc[k][threadIdx.x];
-    part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = r;
-  }
+  tree_flush(acc, HIST_SUMS, part);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     shift_out[0] = x0;
     shift_out[1] = y0;

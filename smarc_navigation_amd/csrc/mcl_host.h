@@ -2,7 +2,7 @@
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
 // mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h,
-// mcl_host_drift.h, mcl_host_regularise.h, mcl_host_quantile.h
+// mcl_host_drift.h, mcl_host_regularise.h, mcl_host_quantile.h, mcl_host_recovery.h, mcl_host_modes.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

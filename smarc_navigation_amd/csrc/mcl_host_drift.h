@@ -112,13 +112,10 @@ int drift_mean_cov(mcl_handle* h, double* mean3, double* cov6) {
   const double m[3] = {r[0] / N, r[1] / N, r[2] / N};
   if (mean3)
     for (int c = 0; c < 3; ++c) mean3[c] = m[c] + r[DRIFT_SUMS + c];
-  if (cov6) {
-    cov6[0] = r[3] / N - m[0] * m[0];
-    cov6[1] = r[4] / N - m[0] * m[1];
-    cov6[2] = r[5] / N - m[0] * m[2];
-    cov6[3] = r[6] / N - m[1] * m[1];
-    cov6[4] = r[7] / N - m[1] * m[2];
-    cov6[5] = r[8] / N - m[2] * m[2];
+  if (cov6) {   // xx, xy, xz, yy, yz, zz from the packed lower triangle the kernel leaves
+    int k = 0;
+    for (int a = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b) cov6[k++] = r[3 + reg_packed(b, a)] / N - m[a] * m[b];
   }
   return MCL_OK;
 }

@@ -186,19 +186,17 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_modes_peak_final(const u64* __res
 
 // ------------------------------------------------------------------ moments
 // One pass over the particles with the stored cell ids.  A particle lies in at most one window (the windows are
-// disjoint).  Per wave iteration and per mode that has a particle in the wave: the eleven terms, zero in the other lanes,
-// are summed across the wave in the scan's fixed order and added, by lane 0, to the wave's LDS accumulator; the
-// workgroup's four accumulators are added in wave order into one record per workgroup -- k_sum_final adds the records
-// in index order.  The grid follows from n alone (grid_for), so the tree is a function of (state, n, lattice).
+// disjoint).  The sums are the fixed tree of mcl_device.h, row m * MODES_SUMS + j for term j of mode m: per wave
+// iteration and per mode that has a particle in the wave, the eleven terms, zero in the lanes outside that mode's window.
 __global__ void __launch_bounds__(MCL_BLOCK) k_modes_moments(StatePtrs s, long long n, const u32* __restrict__ cell_id,
                                                              ModeLattice g, const ModePeak* __restrict__ peaks, int k,
                                                              double* __restrict__ part /*[k][MODES_SUMS][grid]*/) {
 #pragma clang fp contract(off)
-  __shared__ double acc[MCL_BLOCK / MCL_WAVE][MODES_MAX_K][MODES_SUMS];
+  __shared__ double acc[MCL_BLOCK / MCL_WAVE][MODES_MAX_K * MODES_SUMS];
   __shared__ int pk[MODES_MAX_K][4];      // ix, iy, iyaw, score != 0
   __shared__ double ctr[MODES_MAX_K][2];  // the peak cell's centre
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int t = threadIdx.x; t < (MCL_BLOCK / MCL_WAVE) * MODES_MAX_K * MODES_SUMS; t += blockDim.x) (&acc[0][0][0])[t] = 0.0;
+  const int lane = threadIdx.x & 63;
+  tree_zero(acc);
   if (threadIdx.x < k) {
     const ModePeak p = peaks[threadIdx.x];
     pk[threadIdx.x][0] = p.ix;
@@ -208,7 +206,7 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_modes_moments(StatePtrs s, long l
     ctr[threadIdx.x][0] = g.x0 + ((double)p.ix + 0.5) * g.cell;
     ctr[threadIdx.x][1] = g.y0 + ((double)p.iy + 0.5) * g.cell;
   }
-  __syncthreads();
+  __syncthreads();   // (pk, ctr.  A barrier of its own: with the peaks set up ahead of tree_zero's, 83 VGPRs instead of 62)
   for (long long base = blockIdx.x * (long long)blockDim.x + (threadIdx.x & ~63); base < n;
        base += (long long)gridDim.x * blockDim.x) {
     const long long i = base + lane;
@@ -239,17 +237,9 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_modes_moments(StatePtrs s, long l
 #pragma unroll
       for (int j = 0; j < MODES_SUMS; ++j) {
         const double t = j == 0 ? 1.0 : (j < 8 ? b[j - 1] : (j == 8 ? b[0] * b[0] : (j == 9 ? b[0] * b[1] : b[1] * b[1])));
-        const double r = wave_sum_dpp(in ? t : 0.0);
-        if (lane == 0) acc[wv][m][j] += r;
+        tree_add(acc, m * MODES_SUMS + j, in ? t : 0.0);
       }
     }
   }
-  __syncthreads();
-  for (int t = threadIdx.x; t < k * MODES_SUMS; t += blockDim.x) {
-    const int m = t / MODES_SUMS, j = t - m * MODES_SUMS;
-    double r = acc[0][m][j];
-#pragma unroll
-    for (int w = 1; w < MCL_BLOCK / MCL_WAVE; ++w) r += acc[w][m][j];
-    part[(size_t)t * gridDim.x + blockIdx.x] = r;
-  }
+  tree_flush(acc, k * MODES_SUMS, part);
 }

@@ -34,57 +34,51 @@ __device__ __forceinline__ double reg_centre(double v, double s) {
 }
 
 // ------------------------------------------------------------------ moments
-// The D + D (D + 1) / 2 sums about slot 0 in the fixed tree of k_drift_moments: per wave iteration every term (zero in the
-// lanes past n) is summed across the wave in the scan's fixed order and added, by lane 0, to the wave's LDS accumulator;
-// the workgroup's four accumulators are added in wave order into one record per workgroup -- k_sum_final adds the records
-// in index order.  The products are formed where they are summed: D values stay live, not D (D + 1) / 2.
-template <int D>
-__global__ void __launch_bounds__(MCL_BLOCK) k_reg_moments(RegPtrs p, long long n, double* __restrict__ part /*[NS][grid]*/,
-                                                           double* __restrict__ shift_out) {
+// The D + D (D + 1) / 2 sums of D values about slot 0, in the fixed tree of mcl_device.h: rows 0 .. D - 1 the sums of
+// e_r, row D + reg_packed(r, c) the sum of e_r e_c; zero terms in the lanes past n.  ANGLE2: dimension 2 is an angle, its
+// difference taken into [-pi, pi).  The products are formed where they are summed: D values stay live, not D (D + 1) / 2.
+// One body for k_reg_moments (v = x, y, yaw[, cx, cy, bw]) and for k_drift_moments (mcl_drift.h: v = cx, cy, bw); acc and
+// block = blockDim.x come from the kernel (mcl_device.h, the fixed tree: blockDim.x is read in kernels only).
+template <int D, bool ANGLE2, class V>
+__device__ __forceinline__ void moments_about_slot0(double (&acc)[MCL_BLOCK / MCL_WAVE][D + D * (D + 1) / 2],
+                                                    const V& v /*[D] pointers*/, long long n, u32 block,
+                                                    double* __restrict__ part /*[NS][grid]*/,
+                                                    double* __restrict__ shift_out) {
 #pragma clang fp contract(off)
   constexpr int NS = D + D * (D + 1) / 2;
-  __shared__ double acc[MCL_BLOCK / MCL_WAVE][NS];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < (MCL_BLOCK / MCL_WAVE) * NS) (&acc[0][0])[threadIdx.x] = 0.0;
-  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  tree_zero(acc);
   double s[D];
 #pragma unroll
-  for (int r = 0; r < D; ++r) s[r] = p.v[r][0];
-  for (long long base = blockIdx.x * (long long)blockDim.x + (threadIdx.x & ~63); base < n;
-       base += (long long)gridDim.x * blockDim.x) {
+  for (int r = 0; r < D; ++r) s[r] = v[r][0];
+  for (long long base = blockIdx.x * (long long)block + (threadIdx.x & ~63); base < n; base += (long long)gridDim.x * block) {
     const long long i = base + lane;
     double e[D];
 #pragma unroll
     for (int r = 0; r < D; ++r) e[r] = 0.0;
     if (i < n) {
 #pragma unroll
-      for (int r = 0; r < D; ++r) e[r] = r == 2 ? reg_centre<2>(p.v[r][i], s[r]) : reg_centre<0>(p.v[r][i], s[r]);
+      for (int r = 0; r < D; ++r) e[r] = (ANGLE2 && r == 2) ? reg_centre<2>(v[r][i], s[r]) : reg_centre<0>(v[r][i], s[r]);
     }
 #pragma unroll
-    for (int r = 0; r < D; ++r) {
-      const double t = wave_sum_dpp(e[r]);
-      if (lane == 0) acc[wv][r] += t;
-    }
+    for (int r = 0; r < D; ++r) tree_add(acc, r, e[r]);
 #pragma unroll
     for (int r = 0; r < D; ++r) {
 #pragma unroll
-      for (int c = 0; c <= r; ++c) {
-        const double t = wave_sum_dpp(e[r] * e[c]);
-        if (lane == 0) acc[wv][D + r * (r + 1) / 2 + c] += t;
-      }
+      for (int c = 0; c <= r; ++c) tree_add(acc, D + reg_packed(r, c), e[r] * e[c]);
     }
   }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double r = acc[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < MCL_BLOCK / MCL_WAVE; ++k) r += acc[k][threadIdx.x];
-    part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = r;
-  }
+  tree_flush(acc, NS, part);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
     for (int r = 0; r < D; ++r) shift_out[r] = s[r];
   }
+}
+template <int D>
+__global__ void __launch_bounds__(MCL_BLOCK) k_reg_moments(RegPtrs p, long long n, double* __restrict__ part,
+                                                           double* __restrict__ shift_out) {
+  __shared__ double acc[MCL_BLOCK / MCL_WAVE][D + D * (D + 1) / 2];
+  moments_about_slot0<D, true>(acc, p.v, n, blockDim.x, part, shift_out);
 }
 
 // ------------------------------------------------------------------ factor

@@ -356,6 +356,78 @@ def sum_roundings(n, block, max_grid):
     return -(-n // (grid * block)) + 6 + block // 64 + -(-grid // 64) + 6 + 8
 
 
+# The summation tree of the moment kernels (mcl_device.h, "the fixed tree": k_modes_moments, k_history_frame,
+# k_drift_moments, k_reg_moments), restated operation by operation: every `+` below is one fp64 addition the device makes,
+# in the device's order, so the sums agree bit for bit -- the sign of a zero included.
+def _wave_sum_dpp(v):
+    """wave_sum_dpp of (..., 64) lanes: wave_scan_incl_dpp, then lane 63.  A lane without a source adds +0.0."""
+    row_lane = np.arange(64) % 16
+    for k in (1, 2, 4, 8):                         # row_shr:k inside rows of 16 lanes
+        src = np.zeros_like(v)
+        src[..., k:] = v[..., :-k]
+        src[..., row_lane < k] = 0.0
+        v = v + src
+    src = np.zeros_like(v)                         # row_bcast:15, row mask 0xa: lanes 15 and 47 into rows 1 and 3
+    src[..., 16:32] = v[..., 15:16]
+    src[..., 48:64] = v[..., 47:48]
+    v = v + src
+    src = np.zeros_like(v)                         # row_bcast:31, row mask 0xc: lane 31 into rows 2 and 3
+    src[..., 32:64] = v[..., 31:32]
+    v = v + src
+    return v[..., 63]
+
+
+def _wave_sum_shfl(v):
+    """wave_sum of (..., 64) doubles: v += __shfl_down(v, o) for o = 32 ... 1 (a lane whose source lies past the wave reads
+    itself); lane 0 holds the sum"""
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., np.where(lane + o < 64, lane + o, lane)]
+    return v[..., 0]
+
+
+def sum_final_tree(rec):
+    """k_sum_final over one row of per-workgroup records: thread t adds records t, t + 256, ... to +0.0 in index order;
+    block_sum: a __shfl_down tree per wave, then one over the four wave sums (the other lanes of wave 0 hold +0.0)"""
+    rec = np.asarray(rec, dtype=np.float64)
+    acc = np.zeros(MCL_BLOCK)
+    for i in range(0, rec.size, MCL_BLOCK):
+        chunk = rec[i:i + MCL_BLOCK]
+        acc[:chunk.size] = acc[:chunk.size] + chunk
+    sh = np.zeros(64)
+    sh[:MCL_BLOCK // 64] = _wave_sum_shfl(acc.reshape(MCL_BLOCK // 64, 64))
+    return _wave_sum_shfl(sh)
+
+
+def moment_tree_sums(terms):
+    """terms (rows, n): the term every lane contributes, one row per sum -> (rows,) what the moment kernel and k_sum_final
+    leave.  Per grid-stride iteration of a wave (64 consecutive particles from blockIdx 256 + wave 64, stride grid x 256;
+    the lanes past n hold +0.0; a wave whose first lane lies past n does not run) the wave's sum goes through
+    _wave_sum_dpp and is added by lane 0 to the wave's accumulator, which starts at +0.0; the four accumulators of a
+    workgroup are added in wave order; sum_final_tree adds the grid_for(n) records."""
+    terms = np.atleast_2d(np.asarray(terms, dtype=np.float64))
+    n = terms.shape[1]
+    waves = MCL_BLOCK // 64
+    grid = min(-(-n // MCL_BLOCK), MCL_MAX_GRID)
+    stride = grid * MCL_BLOCK
+    iters = -(-n // stride)
+    base = (np.arange(iters)[:, None, None] * grid + np.arange(grid)[None, :, None]) * MCL_BLOCK + 64 * np.arange(waves)
+    runs = base < n                                           # (iters, grid, waves)
+    out = np.zeros(terms.shape[0])
+    for j, t in enumerate(terms):
+        v = np.zeros(iters * stride)
+        v[:n] = t
+        w = _wave_sum_dpp(v.reshape(iters, grid, waves, 64))
+        acc = np.zeros((grid, waves))
+        for it in range(iters):
+            acc = np.where(runs[it], acc + w[it], acc)
+        rec = acc[:, 0]
+        for k in range(1, waves):
+            rec = rec + acc[:, k]
+        out[j] = sum_final_tree(rec)
+    return out
+
+
 def two_pass_roundings(n):
     return sum_roundings(n, MCL_BLOCK, MCL_MAX_GRID)
 
