@@ -107,6 +107,7 @@ int mcl_create(const mcl_config* cfg, mcl_handle** out) {
     h->env_visit = env_tristate("MCL_VISIT");
     h->env_sweep_uniform = env_tristate("MCL_SWEEP_UNIFORM");
     if (const char* sv = getenv("MCL_SWEEP_STEP_CAP")) h->env_sweep_step_cap = std::max(0, atoi(sv));
+    if (const char* sv = getenv("MCL_SWEEP_WAVE_CAP")) h->env_sweep_wave_cap = std::max(0, atoi(sv));
     if (const char* sv = getenv("MCL_VISIT_BINS")) {
       int b[3] = {0, 0, 0};
       if (sscanf(sv, "%d,%d,%d", &b[0], &b[1], &b[2]) == 3 && b[0] >= 1 && b[1] >= 1 && b[2] >= 1 &&

@@ -154,6 +154,7 @@ struct mcl_handle {
   DevBuf<u32> defer2_idx;        // TIN with holes: what the fan slice -- the sweep's hand-over kernel there -- declines in turn
   int env_handover_slice = -1;      // MCL_HANDOVER_SLICE=0: the ray traversal takes the TIN sweep's hand-overs even on meshes with holes (A/B)
   int env_sweep_step_cap = 0;       // MCL_SWEEP_STEP_CAP=n: the lattice walk gives up after n steps (tests of the step-limit path; 0: the walk's own limit)
+  int env_sweep_wave_cap = 0;       // MCL_SWEEP_WAVE_CAP=n: the wave-level bound of the assembly walk loop (tests; 0: derived from r_max, the resolution and the step cap)
   int env_sweep_uniform = -1;       // MCL_SWEEP_UNIFORM=1: waves of the lattice sweep whose lanes share a path share the walk (mcl_sweep.h; default off: the scalar unit makes it slower than the per-lane loop)
   DevBuf<unsigned long long> sweep_work_dev;   // MCL_DEBUG_WORK: the lattice sweep's (shared, all) walk steps per wave, 64 words
   DevBuf<unsigned> reasons_dev;  // -DSWEEP_REASONS builds: why the sweep declined (16 counters)

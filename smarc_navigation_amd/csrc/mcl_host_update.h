@@ -609,12 +609,24 @@ void debug_sweep_handovers(mcl_handle* h, const MbesArgs& a) {
 #endif
 }
 
+// The hard bound of the assembly walk loop (mcl_sweep.h: sweep_walk_asm), a wave's step count.  Every lane has its own
+// limit, max_steps = 3 (s_stop + 4 res) / res + 16 with s_stop <= r_max + 2 res (or the step cap), tested on every second
+// step: a lane is out by step max_steps + 2.  The wave's bound lies above that for every lane -- it never binds unless
+// the loop's own exit logic is wrong, and then the wave ends in hand-overs instead of spinning.
+int sweep_wave_cap(float r_max, float res, int step_cap) {
+  const double steps = 3.0 * ((double)r_max + 6.0 * (double)res) / (double)res + 16.0;
+  int cap = steps < 1e9 ? (int)steps : 1000000000;   // (NaN: the comparison fails)
+  if (step_cap > 0 && step_cap < cap) cap = step_cap;
+  return cap + 8;
+}
+
 // What the sweep declines (mcl_sweep.h: tilt, position, no nadir hit, a border the slice may re-cross) goes to the
 // general kernel through the hand-over list.
 int run_sweep(mcl_handle* h, const MbesPlan& p, MbesArgs& a, const MbesCounters& wh) {
   a.sweep_noclamp = sweep_noclamp(h, p) ? 1 : 0;
   a.sweep_uniform = h->env_sweep_uniform == 1 ? 1 : 0;   // (off unless asked for: measured slower than the per-lane loop)
   a.sweep_step_cap = h->env_sweep_step_cap;
+  a.sweep_wave_cap = h->env_sweep_wave_cap ? h->env_sweep_wave_cap : sweep_wave_cap(a.r_max, a.res, a.sweep_step_cap);
   a.sweep_work = nullptr;
   if (h->env_debug_work) {
     RESERVE(h, h->sweep_work_dev, 64);

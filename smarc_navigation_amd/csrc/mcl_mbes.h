@@ -128,6 +128,7 @@ struct MbesArgs {
   int sweep_nsub;             // lanes per particle side (1, 2 or 4: small clouds split a side's beams over several lanes)
   int sweep_noclamp;          // 1: no beam of this ping can meet the seabed beyond r_max (proved on the host): the merge loop skips the clamp
   int sweep_step_cap;         // MCL_SWEEP_STEP_CAP (tests): when > 0 the lattice walk's step limit is at most this -- the limit itself is a safety net no sane walk reaches
+  int sweep_wave_cap;         // the assembly walk loop's hard bound (mcl_sweep.h: sweep_walk_asm): a wave leaves the loop when its step count reaches this, whatever its lanes' own tests say -- above every lane's limit (mcl_host_update.h: sweep_wave_cap; MCL_SWEEP_WAVE_CAP=n, tests, sets it)
   int sweep_uniform;          // 1 (MCL_SWEEP_UNIFORM=1): a wave whose lanes stand on the same triangle walks with the lattice triple in scalar registers (mcl_sweep.h: the shared walk); 0, the default: every wave takes the per-lane loop
   unsigned long long* sweep_work;   // MCL_DEBUG_WORK: 64 words, every wave of the lattice sweep adds (steps walked shared << 32 | steps walked) to one of them (or nullptr)
   float sweep_c2z_min;        // cos of the largest fan-plane tilt the sweep accepts (terrain slope bound, mcl_host_update.h)

@@ -120,37 +120,41 @@ typedef float sweep_rec __attribute__((ext_vector_type(4)));   // {side-signed t
 #define SWEEP_BIAS1 32u
 #define SWEEP_PREV_OFF 48u   // ... and the record one place back towards the nadir is at bp + 48 on either side
 // first half: the pending beam's tangent in TAN, its record in A = v[60:63] (.x: the next beam's tangent); fetches B
-#define SWEEP_MERGE_HALF1(TAN, OFF1, CLAMP)                                                     \
+#define SWEEP_MERGE_HALF1X(TAN, OFF1, CLAMP, TP, SC, TC)                                                  \
       "v_fma_f32 %[d], -" TAN ", %[dts], %[dss]\n\t"                                     \
       "s_waitcnt lgkmcnt(0)\n\t"                                                         \
-      "v_fma_f32 %[e2], -v60, %[tc], %[sc]\n\t"                                          \
+      "v_fma_f32 %[e2], -v60, " TC ", " SC "\n\t"                                          \
       "ds_read_b128 v[56:59], %[bp]" OFF1 "\n\t"                                         \
       "v_rcp_f32 %[d], %[d]\n\t"                                                         \
       "v_cmp_le_f32 vcc, 0, %[e2]\n\t"                                                   \
       "s_andn2_b64 vcc, exec, vcc\n\t"                                                   \
       "s_or_b64 %[odd], %[odd], vcc\n\t"                                                 \
       "v_mul_f32 %[ep], %[num], %[d]\n\t"                                                \
-      "v_med3_f32 %[ep], %[ep], %[tp], %[tc]\n\t"                                        \
+      "v_med3_f32 %[ep], %[ep], " TP ", " TC "\n\t"                                        \
       "v_fma_f32 %[ep], -%[ep], v61, v62\n\t"                                            \
       CLAMP("v_max_f32 %[ep], %[ep], v63\n\t")                                           \
       "v_fmac_f32 %[acc], %[ep], %[ep]\n\t"                                              \
       "s_andn2_b64 exec, exec, vcc\n\t"
 // second half: the pending beam's tangent in A.x = v60, its record in B = v[56:59]; fetches A, moves bp by two records
-#define SWEEP_MERGE_HALF2(OFF2, STEP2, CLAMP)                                                   \
+#define SWEEP_MERGE_HALF2X(OFF2, STEP2, CLAMP, TP, SC, TC)                                                \
       "v_fma_f32 %[d], -v60, %[dts], %[dss]\n\t"                                         \
       "s_waitcnt lgkmcnt(0)\n\t"                                                         \
-      "v_fma_f32 %[ec], -v56, %[tc], %[sc]\n\t"                                          \
+      "v_fma_f32 %[ec], -v56, " TC ", " SC "\n\t"                                          \
       "ds_read_b128 v[60:63], %[bp]" OFF2 "\n\t"                                         \
       STEP2 "\n\t"                                                                       \
       "v_rcp_f32 %[d], %[d]\n\t"                                                         \
       "v_cmp_le_f32 vcc, 0, %[ec]\n\t"                                                   \
       "s_nop 0\n\t"                                                                      \
       "v_mul_f32 %[ep], %[num], %[d]\n\t"                                                \
-      "v_med3_f32 %[ep], %[ep], %[tp], %[tc]\n\t"                                        \
+      "v_med3_f32 %[ep], %[ep], " TP ", " TC "\n\t"                                        \
       "v_fma_f32 %[ep], -%[ep], v57, v58\n\t"                                            \
       CLAMP("v_max_f32 %[ep], %[ep], v59\n\t")                                           \
       "v_fmac_f32 %[acc], %[ep], %[ep]\n\t"                                              \
       "s_and_b64 exec, exec, vcc\n\t"
+// (the walk loop in assembly, sweep_walk_asm below, swaps the roles of the two vertices from step to step: there the
+//  segment's tp, sc and tc are text; the statement of one segment names its operands)
+#define SWEEP_MERGE_HALF1(TAN, OFF1, CLAMP) SWEEP_MERGE_HALF1X(TAN, OFF1, CLAMP, "%[tp]", "%[sc]", "%[tc]")
+#define SWEEP_MERGE_HALF2(OFF2, STEP2, CLAMP) SWEEP_MERGE_HALF2X(OFF2, STEP2, CLAMP, "%[tp]", "%[sc]", "%[tc]")
 #define SWEEP_CLAMP_ON(x) x
 #define SWEEP_CLAMP_OFF(x)
 #define SWEEP_MERGE_ASM_TEXT(OFFP, OFF0, OFF1, OFF2, STEP2, STEP1, L1, L9, CLAMP)                \
@@ -205,6 +209,194 @@ __device__ __forceinline__ void sweep_merge_asm(int sel, float& acc, unsigned& b
                  [ep] "=&v"(ep), [d] "=&v"(d), [ec] "=&v"(ec), [e2] "=&v"(e2), [sav] "=&s"(sav), [odd] "=&s"(odd)
                : [dss] "v"(dss), [num] "v"(num), [tp] "v"(tp), [sc] "v"(sc), [tc] "v"(tc), [dts] "v"(dts), [sel] "s"(sel)
                : "vcc", "scc", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+}
+
+#ifndef SWEEP_WALK_CXX
+#define SWEEP_WALK_CXX 0   // 1: the per-lane walk loop stays the compiler's, around the assembly merge statement above (for bisecting)
+#endif
+// The whole per-lane loop of the lattice sweep's main kernels in ONE statement (gfx950): walk step and merge loop of
+// sweep_side<2 | 3, false, false, false>, lane_walk there.  As an island in compiled code the merge statement paid on every
+// segment, of about four beams, for what never changes in a wave's life or was at hand a moment ago: a scalar dispatch on
+// side and clamp, the pending record and its tangent read again from LDS behind a full wait, copies around the
+// operands, and an exec save / branch / restore sequence for each of the walk step's four divergent exits.  Here
+// * side and clamp are resolved ONCE: four copies of the loop behind one scalar branch;
+// * the pending record and tangent stay in v[56:63] from segment to segment.  Only a lane that left the merge loop in its
+//   first half holds them in the other tuple: those lanes alone fetch them again (under the mask the bp correction of
+//   that half runs under anyway), and nothing waits for it before the next segment's first test;
+// * a lane leaves the walk by clearing its exec bit, one branch on execz ends the wave's loop.  The verdict is a wave mask:
+//   okm collects the lanes that leave through `bp == bp_end` or `sc > s_stop`; every other way out -- the step limit, a
+//   vertex that is not above the horizon (or a NaN: the map border), the wave's hard bound -- leaves ok false;
+// * the loop is unrolled by two with the roles of (previous, current) vertex swapped, like the C++ loop, and the node
+//   registers rotate with it: the new node's id is formed in the FREE one of four id registers, its plane function in the
+//   free one of three -- one move per two steps, which keeps the id of the node found last in ONE register for the code
+//   behind the loop, whichever half a lane left in;
+// * a wave-uniform count ends the loop for every lane still in it at `cap` steps (mcl_host_update.h: sweep_wave_cap): a
+//   mistake in the exit logic ends in hand-overs, not in a wave that spins.
+// Every floating-point instruction is the C++ loop's on the same operands in the same order (the list: the disassembly of
+// the -DSWEEP_MERGE_CXX=1 build, which tests/test_gpu_zz_walk_asm.py compares against bit for bit); the integer chain of
+// the next node is one instruction shorter than the compiler's (SWEEP_WALK_NODE).  No memory is written: the loads are LDS
+// reads and a range-checked buffer load.
+// Measured (profiles/README.md): the vector count of a wave falls by 2 %, its scalar count by a third -- the compiler's loop
+// was already down to one move per two steps; what the island cost was scalar work.
+// (hazards: a v_rcp result is read no earlier than in the merge loop; v_cmp -> SALU read of VCC and SALU write of EXEC ->
+//  VALU are interlocked; every LDS / buffer result is read behind its s_waitcnt, and both counters are drained before the
+//  statement ends -- a lane may leave with its next height or a record still in flight.)
+// next node NK = AP + Bn.P - C of the triangle across the edge and its height load.  The byte offset without unpacking
+// j: NK = i 65536 + j (j signed), so 4 NK + g0b + i (ny4 - 262144) = 4 j + g0b + i ny4 (mod 2^32) with i = (NK + 32768) >> 16
+// -- six instructions (the compiler's chain: seven); i stays in h0 for the plane functions.  (The offset is formed in the
+// register of dss: dead once the load is issued.  |i| < 30000 and 4 ny < 2^23, checked on the host: the 24-bit multiply.)
+#define SWEEP_WALK_NODE(NK, AP)                                                                                                  \
+      "v_sub_u32 " NK ", %[bq], %[cp]\n\t"                                                                                       \
+      "v_add_u32 " NK ", " NK ", " AP "\n\t"                                                                                     \
+      "v_add_u32 %[h0], 0x8000, " NK "\n\t"                                                                                      \
+      "v_lshl_add_u32 %[dss], " NK ", 2, %[g0b]\n\t"                                                                             \
+      "v_ashrrev_i32 %[h0], 16, %[h0]\n\t"                                                                                       \
+      "v_mad_i32_i24 %[dss], %[h0], %[ny4w], %[dss]\n\t"                                                                         \
+      "buffer_load_dword %[hn], %[dss], %[grsrc], 0 offen\n\t"
+// the segment (SP, TP) -> (SC, TC): its constants (dts, dss, num), then its beams; on exit the pending beam's
+// tangent is in v56 and its record in (or on its way to) v[60:63] on every lane
+#define SWEEP_WALK_MERGE(L, SP, TP, SC, TC, OFFP, OFF0, OFF1, OFF2, STEP2, STEP1, CLAMP)                                          \
+      "v_sub_f32 %[dts], " TC ", " TP "\n\t"                                                                                     \
+      "v_sub_f32 %[dss], " SC ", " SP "\n\t"                                                                                     \
+      "v_mul_f32 %[num], " SP ", %[dts]\n\t"                                                                                     \
+      "v_fma_f32 %[num], " TP ", %[dss], -%[num]\n\t"                                                                            \
+      "s_mov_b64 %[sav], exec\n\t"                                                                                               \
+      "s_mov_b64 %[odd], 0\n\t"                                                                                                  \
+      "s_waitcnt lgkmcnt(0)\n\t"                                                                                                 \
+      "v_fma_f32 %[ec], -v56, " TC ", " SC "\n\t"                                                                                \
+      "v_cmp_le_f32 vcc, 0, %[ec]\n\t"                                                                                           \
+      "s_and_b64 exec, exec, vcc\n\t"                                                                                            \
+      "s_cbranch_execz " L "9f\n"                                                                                                \
+      L "1:\n\t"                                                                                                                 \
+      SWEEP_MERGE_HALF1X("v56", OFF1, CLAMP, TP, SC, TC)                                                                         \
+      "s_cbranch_execz " L "9f\n\t"                                                                                              \
+      SWEEP_MERGE_HALF2X(OFF2, STEP2, CLAMP, TP, SC, TC)                                                                         \
+      "s_cbranch_execnz " L "1b\n"                                                                                               \
+      L "9:\n\t"                                                                                                                 \
+      "s_and_b64 exec, %[odd], %[sav]\n\t"                                                                                       \
+      "s_cbranch_scc0 " L "8f\n\t"                                                                                               \
+      STEP1 "\n\t"                                                                                                               \
+      "ds_read_b32 v56, %[bp]" OFFP "\n\t"                                                                                       \
+      "ds_read_b128 v[60:63], %[bp]" OFF0 "\n"                                                                                   \
+      L "8:\n\t"                                                                                                                 \
+      "s_mov_b64 exec, %[sav]\n\t"
+// the three tests that end a walk normally (every second step, like the C++ loop: EXITS)
+#define SWEEP_WALK_EXITS(SC)                                                                                                     \
+      "s_xor_b64 %[okm], %[okm], exec\n\t"                                                                                       \
+      "v_cmp_ne_u32 vcc, %[bp], %[bpe]\n\t"                                                                                      \
+      "s_and_b64 exec, exec, vcc\n\t"                                                                                            \
+      "v_cmp_ngt_f32 vcc, " SC ", %[sstop]\n\t"                                                                                  \
+      "s_and_b64 exec, exec, vcc\n\t"                                                                                            \
+      "s_xor_b64 %[okm], %[okm], exec\n\t"                                                                                       \
+      "v_cmp_le_i32 vcc, %[step], %[maxs]\n\t"                                                                                   \
+      "s_and_b64 exec, exec, vcc\n\t"                                                                                            \
+      "s_cbranch_execz 900f\n\t"
+// the new node NK (plane function -> DN, the free register; AD: the one of the node found before) replaces the node on its
+// side of the plane, the crossing of the new edge becomes (SP, TP); LAST: what the first half does for the code behind the loop
+#define SWEEP_WALK_CROSS(NK, AP, DN, AD, SP, TP, LAST)                                                                           \
+      "v_cvt_f32_i32_sdwa %[ep], sext(" NK ") dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0\n\t"                           \
+      "v_cvt_f32_i32 %[h0], %[h0]\n\t"                                                                                           \
+      "s_waitcnt vmcnt(0)\n\t"                                                                                                   \
+      "v_fma_f32 " DN ", %[pz], %[hn], %[p0]\n\t"                                                                                \
+      "v_fmac_f32 " DN ", %[pv], %[ep]\n\t"                                                                                      \
+      "v_fmac_f32 " DN ", %[pu], %[h0]\n\t"                                                                                      \
+      "v_xor_b32 %[ec], " DN ", " AD "\n\t"                                                                                      \
+      "v_cmp_gt_i32 vcc, 0, %[ec]\n\t"                                                                                           \
+      "v_cndmask_b32 %[bd], %[bd], " AD ", vcc\n\t"                                                                              \
+      "v_cndmask_b32 %[bs], %[bs], %[as], vcc\n\t"                                                                               \
+      "v_sub_f32 %[d], " DN ", %[bd]\n\t"                                                                                        \
+      "v_cndmask_b32 %[bt], %[bt], %[at], vcc\n\t"                                                                               \
+      "v_rcp_f32 %[d], %[d]\n\t"                                                                                                 \
+      "v_fma_f32 %[as], %[sz], %[hn], %[s0]\n\t"                                                                                 \
+      "v_fma_f32 %[at], %[tz], %[hn], %[t0]\n\t"                                                                                 \
+      "v_cndmask_b32 %[cp], " AP ", %[bq], vcc\n\t"                                                                              \
+      "v_fmac_f32 %[as], %[sv], %[ep]\n\t"                                                                                       \
+      "v_fmac_f32 %[at], %[tv], %[ep]\n\t"                                                                                       \
+      "v_cndmask_b32 %[bq], %[bq], " AP ", vcc\n\t"                                                                              \
+      "v_fmac_f32 %[as], %[su], %[h0]\n\t"                                                                                       \
+      "v_fmac_f32 %[at], %[tu], %[h0]\n\t"                                                                                       \
+      "v_mul_f32 %[d], " DN ", %[d]\n\t"                                                                                         \
+      "v_sub_f32 %[ec], %[bs], %[as]\n\t"                                                                                        \
+      "v_sub_f32 %[e2], %[bt], %[at]\n\t"                                                                                        \
+      "v_fma_f32 " SP ", %[d], %[ec], %[as]\n\t"                                                                                 \
+      "v_fma_f32 " TP ", %[d], %[e2], %[at]\n\t"                                                                                 \
+      LAST                                                                                                                       \
+      "v_cmp_lt_f32 vcc, 0, " TP "\n\t"                                                                                          \
+      "s_and_b64 exec, exec, vcc\n\t"                                                                                            \
+      "s_cbranch_execz 900f\n\t"
+// one copy of the loop (K: its label prefix).  Ids: (A.P, Bn.P, C, free) = (ap, bq, cp, aw) before the first half,
+// (aw, bq, cp, ap) before the second; plane functions: (A.d, Bn.d, free) = (ad, bd, dw) and (dw, bd, ad).  mid: enter at
+// the second half (the shared walk hands over at either parity)
+#define SWEEP_WALK_LOOP(K, OFFP, OFF0, OFF1, OFF2, STEP2, STEP1, CLAMP)                                                          \
+      "ds_read_b32 v56, %[bp]" OFFP "\n\t"                                                                                       \
+      "ds_read_b128 v[60:63], %[bp]" OFF0 "\n\t"                                                                                 \
+      "s_cmp_lg_u32 %[mid], 0\n\t"                                                                                               \
+      "s_cbranch_scc0 " K "00f\n\t"                                                                                              \
+      "v_mov_b32 %[aw], %[ap]\n\t"                                                                                               \
+      "v_mov_b32 %[dw], %[ad]\n\t"                                                                                               \
+      "s_branch " K "50f\n"                                                                                                      \
+      K "00:\n\t"                                                                                                                \
+      SWEEP_WALK_NODE("%[aw]", "%[ap]")                                                                                          \
+      SWEEP_WALK_MERGE(K "1", "%[s1]", "%[t1]", "%[s2]", "%[t2]", OFFP, OFF0, OFF1, OFF2, STEP2, STEP1, CLAMP)                    \
+      SWEEP_WALK_EXITS("%[s2]")                                                                                                  \
+      SWEEP_WALK_CROSS("%[aw]", "%[ap]", "%[dw]", "%[ad]", "%[s1]", "%[t1]", "v_mov_b32 %[ap], %[aw]\n\t")                       \
+      K "50:\n\t"                                                                                                                \
+      SWEEP_WALK_NODE("%[ap]", "%[aw]")                                                                                          \
+      SWEEP_WALK_MERGE(K "2", "%[s2]", "%[t2]", "%[s1]", "%[t1]", OFFP, OFF0, OFF1, OFF2, STEP2, STEP1, CLAMP)                    \
+      SWEEP_WALK_CROSS("%[ap]", "%[aw]", "%[ad]", "%[dw]", "%[s2]", "%[t2]", "")                                                 \
+      "s_add_u32 %[step], %[step], 2\n\t"                                                                                        \
+      "s_cmp_lt_i32 %[step], %[cap]\n\t"                                                                                         \
+      "s_cbranch_scc1 " K "00b\n\t"                                                                                              \
+      "s_branch 900f\n"
+#define SWEEP_WALK_SIDE0(K, CLAMP) \
+  SWEEP_WALK_LOOP(K, " offset:48", " offset:64", " offset:80", " offset:96", "v_add_u32 %[bp], 32, %[bp]", "v_add_u32 %[bp], 16, %[bp]", CLAMP)
+#define SWEEP_WALK_SIDE1(K, CLAMP) \
+  SWEEP_WALK_LOOP(K, " offset:48", " offset:32", " offset:16", "", "v_subrev_u32 %[bp], 32, %[bp]", "v_subrev_u32 %[bp], 16, %[bp]", CLAMP)
+// in / out: the walk's state (A, Bn, C; the two vertices), acc, bp, step; k: the lane's constants.  Returns the lane's ok.
+struct SweepWalkConst {
+  float pu, pv, pz, p0, su, sv, sz, s0, tu, tv, tz, t0, s_stop;
+  unsigned bp_end;
+  int g0b, max_steps;
+};
+__device__ __forceinline__ bool sweep_walk_asm(int sel, int mid, int& step, int cap, int ny4, __amdgpu_buffer_rsrc_t grsrc,
+                                               const SweepWalkConst& k, float& acc, unsigned& bp, int& AP, float& Ad, float& As,
+                                               float& At, int& BP, float& Bd, float& Bs, float& Bt, int& C, float& s1,
+                                               float& t1, float& s2, float& t2) {
+  float dw, h0, hn, dts, dss, num, d, ep, e2;
+  int aw;
+  unsigned ec;   // (a scratch register of the loop; on exit the verdict)
+  unsigned long long sav, odd, okm, ent;
+  asm volatile("s_mov_b64 %[ent], exec\n\t"
+               "s_mov_b64 %[okm], 0\n\t"
+               "s_cmp_lt_u32 %[sel], 2\n\t"
+               "s_cbranch_scc0 902f\n\t"
+               "s_cmp_lg_u32 %[sel], 0\n\t"
+               "s_cbranch_scc1 901f\n\t"
+               SWEEP_WALK_SIDE0("1", SWEEP_CLAMP_ON)
+               "901:\n\t"
+               SWEEP_WALK_SIDE1("2", SWEEP_CLAMP_ON)
+               "902:\n\t"
+               "s_cmp_lg_u32 %[sel], 2\n\t"
+               "s_cbranch_scc1 903f\n\t"
+               SWEEP_WALK_SIDE0("3", SWEEP_CLAMP_OFF)
+               "903:\n\t"
+               SWEEP_WALK_SIDE1("4", SWEEP_CLAMP_OFF)
+               "900:\n\t"
+               "s_mov_b64 exec, %[ent]\n\t"
+               "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t"
+               "v_cndmask_b32_e64 %[ec], 0, 1, %[okm]"
+               : [acc] "+v"(acc), [bp] "+v"(bp), [ap] "+v"(AP), [ad] "+v"(Ad), [as] "+v"(As), [at] "+v"(At), [bq] "+v"(BP),
+                 [bd] "+v"(Bd), [bs] "+v"(Bs), [bt] "+v"(Bt), [cp] "+v"(C), [s1] "+v"(s1), [t1] "+v"(t1), [s2] "+v"(s2),
+                 [t2] "+v"(t2), [step] "+s"(step),
+                 [aw] "=&v"(aw), [dw] "=&v"(dw), [h0] "=&v"(h0), [hn] "=&v"(hn), [dts] "=&v"(dts), [dss] "=&v"(dss),
+                 [num] "=&v"(num), [d] "=&v"(d), [ep] "=&v"(ep), [ec] "=&v"(ec), [e2] "=&v"(e2), [sav] "=&s"(sav),
+                 [odd] "=&s"(odd), [okm] "=&s"(okm), [ent] "=&s"(ent)
+               : [pu] "v"(k.pu), [pv] "v"(k.pv), [pz] "v"(k.pz), [p0] "v"(k.p0), [su] "v"(k.su), [sv] "v"(k.sv), [sz] "v"(k.sz),
+                 [s0] "v"(k.s0), [tu] "v"(k.tu), [tv] "v"(k.tv), [tz] "v"(k.tz), [t0] "v"(k.t0), [sstop] "v"(k.s_stop),
+                 [bpe] "v"(k.bp_end), [g0b] "v"(k.g0b), [maxs] "v"(k.max_steps), [sel] "s"(sel), [mid] "s"(mid),
+                 [cap] "s"(cap), [ny4w] "s"(ny4 - 262144), [grsrc] "s"(grsrc)
+               : "vcc", "scc", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+  return ec != 0u;
 }
 
 // The crossing of the half line s = T t with the segment (sp, tp) -> (sc, tc), as its t: with ds = sc - sp, dt = tc - tp,
@@ -514,6 +706,13 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
   // cost the kernel its register budget (the compiler keeps the state of either alive through the other).
   // Returns the step a lane left at (WORK, the kernel that counts for MCL_DEBUG_WORK: read outside the loop the wave's
   // count becomes every lane's own, a move per iteration).
+  // (the main kernels take this loop as ONE assembly statement, sweep_walk_asm above; the loop below is theirs in the
+  //  reference and diagnostic builds and everybody else's)
+#if SWEEP_MERGE_CXX || SWEEP_WALK_CXX || defined(SWEEP_REASONS) || defined(SWEEP_TIMELINE)
+  constexpr bool walk_asm = false;
+#else
+  constexpr bool walk_asm = !EXPECT_ONLY && !SUB && !WORK;
+#endif
   const auto lane_walk = [&](int step, bool mid) -> int {
     for (;; step += 2) {
       if (!mid && walk_step(s_prev, t_prev, s_cur, t_cur, step, std::true_type())) break;
@@ -628,7 +827,16 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     const bool fin = __builtin_amdgcn_inverse_ballot_w64(fin_m);
     ok = __builtin_amdgcn_inverse_ballot_w64(ok_m);
     int n_steps = n_shared;
-    if ((how & 1) == 0 && !fin) n_steps = lane_walk(how == 2 ? step : step + 2, how == 2);
+    if ((how & 1) == 0 && !fin) {
+      if constexpr (walk_asm) {
+        int st = how == 2 ? step : step + 2;
+        const SweepWalkConst kc = {pu, pv, pz, p0, su, sv, sz, s0, tu, tv, tz, t0, s_stop, bp_end, g0b, max_steps};
+        ok = sweep_walk_asm(msel, __builtin_amdgcn_readfirstlane(how == 2 ? 1 : 0), st, a.sweep_wave_cap, ny4, grsrc, kc, acc, bp, A.P, A.d, A.s, A.t, Bn.P, Bn.d,
+                            Bn.s, Bn.t, C, s_prev, t_prev, s_cur, t_cur);   // (a lane that walks on came out of the shared walk with ok)
+      } else {
+        n_steps = lane_walk(how == 2 ? step : step + 2, how == 2);
+      }
+    }
     if (WORK && a.sweep_work) {
       // MCL_DEBUG_WORK: (steps walked shared, steps walked) of this wave, one atomic per wave over 64 words
       const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
