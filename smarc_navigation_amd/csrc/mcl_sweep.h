@@ -414,18 +414,6 @@ struct SweepNode {
   float s, t;   // in-plane coordinates, s mirrored so that it grows outward on this lane's side
 };
 
-// SURF 2: every cell split along 00-11; SURF 3: along 10-01.  (Height grids, SURF 0: sweep_side_grid below.)
-// Returns false when the particle has to go to the general kernel.  acc: sum over this side's beams of
-// ((range - expected) * weight)^2; EXPECT_ONLY: expected ranges to exp_row[b] instead.
-// The map border: only the nadir ray (cast without bounds tests) has to stay inside the map; a slice that leaves the
-//   map ENDS there (the NaN ring, top of this file): the beams left return r_max.  That conclusion needs the slice to
-//   cross the border line once: the border's trace in the fan plane must be steeper than the slice can be, which the
-//   fan's tilt, the map's steepest slope and the angle between fan and border decide (sweep_border_final); a level
-//   vehicle always qualifies, a tilted fan slanting along the border over steep terrain goes to the traversal kernel.
-// SUB (sub-fans, small clouds): the beams of a side are split over `nsub` lanes; each resolves only its own run of
-//   beams [sub * per, (sub + 1) * per) and starts its walk where the first of them meets the seabed (see the start of
-//   the walk below) -- the walk is a chain of dependent loads, so at 65 536 particles one lane per side leaves the
-//   chip three quarters empty and every lane waiting; four lanes per side fill it, each with a quarter of the walk.
 // May a slice that has just stepped off the map end there?  h: the NaN it loaded (payload 1: an x side, 2: a y side,
 // 3: a corner).  In plane coordinates the border x = x_b is the line s = s_L + k t with |k| <= sin(tilt) / |c1x|, the
 // slice is t = f(s) with |f'| <= (slope + sin(tilt)) / (cos(tilt) - slope sin(tilt)); they meet once if |k f'| < 1
@@ -437,68 +425,103 @@ __device__ __forceinline__ bool sweep_border_final(const MbesArgs& a, float h, f
   return (side == 1u || side == 2u) & (lhs < rhs * fabsf(side == 1u ? c1x : c1y));
 }
 
-template <int SURF, bool EXPECT_ONLY, bool SUB = false, bool WORK = false>
-__device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P, const float4* __restrict__ sbeam,
-                                           const float* __restrict__ stail, int side, int sub, int nsub,
-                                           float* __restrict__ exp_row, float& acc_out) {
-  acc_out = 0.f;
-  const int nx = a.nx, ny = a.ny, B = a.n_beams;
-  // every test before the first map access feeds ONE verdict (`pre`), tested once
-  bool pre = P.um >= 1.0 && P.um < (double)(nx - 2) && P.vm >= 1.0 && P.vm < (double)(ny - 2);  // (NaN: false)
-  const float c2z = P.c2[2];
-  pre = pre & (c2z >= a.sweep_c2z_min);  // else the fan plane is too far from vertical for the terrain's slopes
-  const double fum = pre ? floor(P.um) : 1.0, fvm = pre ? floor(P.vm) : 1.0;
-  const int I0 = (int)fum, J0 = (int)fvm;
-  const float ul = (float)(P.um - fum), vl = (float)(P.vm - fvm);
-  const float res = a.res, inv_res = (float)a.inv_res, oz = P.oz;
-  const float sg = side ? -1.f : 1.f;
-  // beams of this side (of this lane's run of them), outward from the nadir
+// ------------------------------------------------------------------ what the per-side functions share
+// The lane's run of beams, outward from the nadir, and how far out its walk can go.
+// SUB (sub-fans, small clouds): the beams of a side are split over `nsub` lanes; each resolves only its own run of
+//   beams [sub * per, (sub + 1) * per) and starts its walk where the first of them meets the seabed (sweep_start) -- the
+//   walk is a chain of dependent loads, so at 65 536 particles one lane per side leaves the chip three quarters empty
+//   and every lane waiting; four lanes per side fill it, each with a quarter of the walk.
+struct SweepRun {
+  int first;        // beams of the side before this run (SUB; else 0)
+  int ptr, pend;    // the run's first beam and the one beyond its last, by beam index
+  int pstep;        // + 1 on side 0, - 1 on side 1
+  bool none;        // no beam: the lane only takes part in the nadir cast
+  float s_stop;     // the stop distance of the walk
+};
+template <bool SUB>
+__device__ __forceinline__ SweepRun sweep_run(const MbesArgs& a, const MbesPose& P, int side, int sub, int nsub) {
+  SweepRun r;
+  const int B = a.n_beams;
   const int nb_side = side ? a.b_split : B - a.b_split;
   const int per = SUB ? max((nb_side + nsub - 1) / nsub, 2) : nb_side;   // (>= 2: a later run finds its first two tangents in the records of the two beams before it)
-  const int first = SUB ? min(sub * per, nb_side) : 0, last = SUB ? min(first + per, nb_side) : nb_side;
-  int ptr = side ? a.b_split - 1 - first : a.b_split + first;
-  const int pstep = side ? -1 : 1, pend = side ? a.b_split - 1 - last : a.b_split + last;
-  const bool none = ptr == pend;
+  r.first = SUB ? min(sub * per, nb_side) : 0;
+  const int last = SUB ? min(r.first + per, nb_side) : nb_side;
+  r.ptr = side ? a.b_split - 1 - r.first : a.b_split + r.first;
+  r.pstep = side ? -1 : 1;
+  r.pend = side ? a.b_split - 1 - last : a.b_split + last;
+  r.none = r.ptr == r.pend;
   // ---- how far out can the walk go?  The outermost beam of the side is below every node once it reaches z_min
-  float s_stop = none ? 0.f : a.r_max;  // (a side without beams only takes part in the nadir cast)
-  if (!none) {
+  float s_stop = r.none ? 0.f : a.r_max;  // (a side without beams only takes part in the nadir cast)
+  if (!r.none) {
     const float2 sc = a.beam_sc[side ? 0 : B - 1];
-    const float dz_e = sc.x * P.c1[2] - sc.y * c2z;
-    if (dz_e < -1e-4f) s_stop = fminf(s_stop, (a.zmin_map - oz) * fast_rcp(dz_e) * fabsf(sc.x));
+    const float dz_e = sc.x * P.c1[2] - sc.y * P.c2[2];
+    if (dz_e < -1e-4f) s_stop = fminf(s_stop, (a.zmin_map - P.oz) * fast_rcp(dz_e) * fabsf(sc.x));
   }
-  s_stop += 2.f * res;
-  // ---- footprint of everything the lane may touch: X = O + s (+-c1) - t c2 with s in [-2 res, s_stop + 2 res] and
-  // t between the values at which such a point can lie on the surface (z in [z_min, z_max]); 3 nodes of margin
-  {
-    const float rc = fast_rcp(c2z);
-    const float sl = fabsf(P.c1[2]) * (s_stop + 2.f * res);
-    const float t_hi = ((oz - a.zmin_map) + sl) * rc + res, t_lo = fminf(((oz - a.zmax_map) - sl) * rc - res, 0.f);
-    const float s_hi = s_stop + 2.f * res;
-    const float ax = sg * P.c1[0] * inv_res, ay = sg * P.c1[1] * inv_res, bx = -P.c2[0] * inv_res, by = -P.c2[1] * inv_res;
-    const float fi0 = (float)I0, fj0 = (float)J0;
-    // only the nadir ray (cast below without bounds tests) has to stay inside: t in [t_lo, t_hi] along -c2
-    const float n0 = fminf(t_lo * bx, t_hi * bx), n1 = fmaxf(t_lo * bx, t_hi * bx);
-    const float m0 = fminf(t_lo * by, t_hi * by), m1 = fmaxf(t_lo * by, t_hi * by);
-    pre = pre & (fi0 + n0 >= 3.f) & (fi0 + n1 <= (float)(nx - 5)) & (fj0 + m0 >= 3.f) & (fj0 + m1 <= (float)(ny - 5));
-    pre = pre & (s_hi * fmaxf(fabsf(ax), fabsf(ay)) + fmaxf(-t_lo, t_hi) * fmaxf(fabsf(bx), fabsf(by)) < 30000.f);  // packed coordinates
+  r.s_stop = s_stop + 2.f * a.res;
+  return r;
+}
+
+// Footprint of everything a lane of a lattice or grid walk may touch: X = O + s (+-c1) - t c2 with s in
+// [-2 res, s_stop + 2 res] and t between the values at which such a point can lie on the surface (z in [z_min, z_max]);
+// 3 nodes of margin.  Only the nadir ray (cast without bounds tests) has to stay inside the map, t in [t_lo, t_hi] along
+// -c2: a slice that leaves the map ENDS there (the NaN ring, top of this file).  The last test: packed coordinates.
+// (I0, J0): the sensor's cell; sg: + 1 on side 0, - 1 on side 1.
+__device__ __forceinline__ bool sweep_footprint(const MbesArgs& a, const MbesPose& P, float sg, int I0, int J0, float s_stop) {
+  const float res = a.res, inv_res = (float)a.inv_res, oz = P.oz;
+  const float rc = fast_rcp(P.c2[2]);
+  const float sl = fabsf(P.c1[2]) * (s_stop + 2.f * res);
+  const float t_hi = ((oz - a.zmin_map) + sl) * rc + res, t_lo = fminf(((oz - a.zmax_map) - sl) * rc - res, 0.f);
+  const float s_hi = s_stop + 2.f * res;
+  const float ax = sg * P.c1[0] * inv_res, ay = sg * P.c1[1] * inv_res, bx = -P.c2[0] * inv_res, by = -P.c2[1] * inv_res;
+  const float fi0 = (float)I0, fj0 = (float)J0;
+  const float n0 = fminf(t_lo * bx, t_hi * bx), n1 = fmaxf(t_lo * bx, t_hi * bx);
+  const float m0 = fminf(t_lo * by, t_hi * by), m1 = fmaxf(t_lo * by, t_hi * by);
+  return (fi0 + n0 >= 3.f) & (fi0 + n1 <= (float)(a.nx - 5)) & (fj0 + m0 >= 3.f) & (fj0 + m1 <= (float)(a.ny - 5)) &
+         (s_hi * fmaxf(fabsf(ax), fabsf(ay)) + fmaxf(-t_lo, t_hi) * fmaxf(fabsf(bx), fabsf(by)) < 30000.f);
+}
+
+// The height array inside its ring of NaNs, seen from the sensor's cell: pitch nyp = ny + 2, node (i, j) at
+// [(i + 1) * nyp + j + 1]; gp points at node (I0, J0), and the walks address nodes relative to it.
+struct SweepMapWindow {
+  int nyp, ny4, g0b;               // pitch in nodes and in bytes, byte offset of node (I0, J0)
+  const float* __restrict__ gp;
+  __amdgpu_buffer_rsrc_t grsrc;    // the array as a raw buffer (stride 0, num_records in bytes): out-of-range reads return 0
+  // node (i, j) relative to (I0, J0) through the buffer.  (The footprint test keeps a sane walk inside the map; a
+  // NaN-driven one is stopped by the buffer's own range check: a raw buffer load beyond num_records returns 0 -- no
+  // clamp, no 64-bit address arithmetic.  |i| < 30000 and 4 ny < 2^23 -- checked on the host --: the full-rate 24-bit multiply)
+  __device__ __forceinline__ float h(int i, int j) const {
+    return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, __mul24(i, ny4) + ((j << 2) + g0b), 0, 0));
   }
-  if (!pre) SWEEP_FAIL(1);
-  // the height array inside its ring of NaNs: pitch nyp = ny + 2, node (i, j) at [(i + 1) * nyp + j + 1]
-  const int nyp = a.nyp;
-  const int g0i = (I0 + 1) * nyp + (J0 + 1);  // (maps below 2^30 nodes: checked on the host)
-  const float* __restrict__ gp = a.grid_pad + (size_t)g0i;  // node (I0, J0)
-  // ... as a raw buffer (stride 0, num_records in bytes): out-of-range reads return 0
-  const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.grid_pad, 0, (nx + 2) * nyp * 4, 0x00020000);
-  const int ny4 = nyp * 4, g0b = g0i * 4;
-  // ---- start of the walk: the nadir hit, by the ordinary clearance traversal on the global height array.  A later
-  // run of a side's beams (SUB, first > 0) starts where ITS first beam meets the seabed instead -- the same traversal
-  // along that beam, a few dozen cells -- and walks on from there: under the tilt bound the slice is a graph over s, so
-  // everything the sweep's argument needs holds from any exact hit outward.  If that beam has no hit inside r_max the
-  // lane falls back to walking out from the nadir (it resolves nothing on the way: its first beam is still pending).
+};
+__device__ __forceinline__ SweepMapWindow sweep_map_window(const MbesArgs& a, int I0, int J0) {
+  SweepMapWindow w;
+  w.nyp = a.nyp;
+  const int g0i = (I0 + 1) * w.nyp + (J0 + 1);  // (maps below 2^30 nodes: checked on the host)
+  w.gp = a.grid_pad + (size_t)g0i;
+  w.grsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.grid_pad, 0, (a.nx + 2) * w.nyp * 4, 0x00020000);
+  w.ny4 = w.nyp * 4;
+  w.g0b = g0i * 4;
+  return w;
+}
+
+// Start of the walk: the nadir hit, by the ordinary clearance traversal on the global height array.  A later run of a
+// side's beams (SUB, first > 0) starts where ITS first beam meets the seabed instead -- the same traversal along that
+// beam, a few dozen cells -- and walks on from there: under the tilt bound the slice is a graph over s, so everything
+// the sweep's argument needs holds from any exact hit outward.  If that beam has no hit inside r_max the lane falls back
+// to walking out from the nadir (it resolves nothing on the way: its first beam is still pending).
+// Returns the range r0 of the hit (r_max: none) along the ray (dxs, dys, .) that was cast.
+struct SweepStart {
+  float r0, dxs, dys;
+};
+template <int SURF, bool SUB>
+__device__ __forceinline__ SweepStart sweep_start(const MbesArgs& a, const MbesPose& P, const SweepRun& run,
+                                                  const SweepMapWindow& w, int I0, int J0, float ul, float vl) {
+  const int nx = a.nx, ny = a.ny;
+  const float res = a.res, inv_res = (float)a.inv_res, oz = P.oz, c2z = P.c2[2];
   float dxs = -P.c2[0], dys = -P.c2[1], dzs = -c2z, r0 = 0.f;
   bool own_start = false;
-  if (SUB && first > 0 && !none) {
-    const float2 sc = a.beam_sc[ptr];
+  if (SUB && run.first > 0 && !run.none) {
+    const float2 sc = a.beam_sc[run.ptr];
     dxs = sc.x * P.c1[0] - sc.y * P.c2[0];
     dys = sc.x * P.c1[1] - sc.y * P.c2[1];
     dzs = sc.x * P.c1[2] - sc.y * c2z;
@@ -515,39 +538,181 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     }
   }
   for (int attempt = 0; attempt < 2; ++attempt) {
-    r0 = cast_clear<SURF>(gp, nyp, a, ul, vl, oz, dxs * inv_res, dys * inv_res, dzs, a.zmax_map, a.r_max);
+    r0 = cast_clear<SURF>(w.gp, w.nyp, a, ul, vl, oz, dxs * inv_res, dys * inv_res, dzs, a.zmax_map, a.r_max);
     if (!SUB || !own_start || ((r0 < a.r_max) & (r0 > 0.f))) break;
     dxs = -P.c2[0];
     dys = -P.c2[1];
     dzs = -c2z;
     own_start = false;
   }
-  if (!(r0 < a.r_max)) SWEEP_FAIL(5);
-  if (none) return true;
-  // ---- plane and in-plane coordinates as affine functions of (i, j, h): lattice coordinates relative to (I0, J0)
-  const float nx_ = P.c1[1] * P.c2[2] - P.c1[2] * P.c2[1], ny_ = P.c1[2] * P.c2[0] - P.c1[0] * P.c2[2],
-              nz_ = P.c1[0] * P.c2[1] - P.c1[1] * P.c2[0];
-  const float pu = nx_ * res, pv = ny_ * res, pz = nz_, p0 = -(pu * ul + pv * vl + pz * oz);
-  const float su = sg * P.c1[0] * res, sv = sg * P.c1[1] * res, sz = sg * P.c1[2];
-  float s0 = -(su * ul + sv * vl + sz * oz);   // (the shared walk turns it into a NaN on a lane whose walk is over)
-  const float tu = -P.c2[0] * res, tv = -P.c2[1] * res, tz = -c2z, t0 = -(tu * ul + tv * vl + tz * oz);
+  return {r0, dxs, dys};
+}
+
+// Plane and in-plane coordinates as affine functions of (i, j, h): lattice coordinates relative to the sensor's cell.
+// d: signed distance to the fan plane (scaled), s, t: in-plane, s mirrored so that it grows outward on the lane's side.
+struct SweepNormal {
+  float x, y, z;
+};
+__device__ __forceinline__ SweepNormal sweep_normal(const MbesPose& P) {   // c1 x c2 (the TIN forms its own coefficients from it)
+  return {P.c1[1] * P.c2[2] - P.c1[2] * P.c2[1], P.c1[2] * P.c2[0] - P.c1[0] * P.c2[2], P.c1[0] * P.c2[1] - P.c1[1] * P.c2[0]};
+}
+struct SweepFrame {
+  float pu, pv, pz, p0, su, sv, sz, s0, tu, tv, tz, t0;   // (s0 stays writable: the shared walk turns it into a NaN on a lane whose walk is over)
+  __device__ __forceinline__ float d(float fi, float fj, float h) const { return fmaf(pu, fi, fmaf(pv, fj, fmaf(pz, h, p0))); }
+  __device__ __forceinline__ float s(float fi, float fj, float h) const { return fmaf(su, fi, fmaf(sv, fj, fmaf(sz, h, s0))); }
+  __device__ __forceinline__ float t(float fi, float fj, float h) const { return fmaf(tu, fi, fmaf(tv, fj, fmaf(tz, h, t0))); }
+};
+__device__ __forceinline__ SweepFrame sweep_frame(const MbesArgs& a, const MbesPose& P, float sg, float ul, float vl) {
+  const float res = a.res, oz = P.oz;
+  const SweepNormal n = sweep_normal(P);
+  SweepFrame f;
+  f.pu = n.x * res, f.pv = n.y * res, f.pz = n.z, f.p0 = -(f.pu * ul + f.pv * vl + f.pz * oz);
+  f.su = sg * P.c1[0] * res, f.sv = sg * P.c1[1] * res, f.sz = sg * P.c1[2], f.s0 = -(f.su * ul + f.sv * vl + f.sz * oz);
+  f.tu = -P.c2[0] * res, f.tv = -P.c2[1] * res, f.tz = -P.c2[2], f.t0 = -(f.tu * ul + f.tv * vl + f.tz * oz);
+  return f;
+}
+
+// The beam table of a lane's side in LDS, walked by byte address: the next beam to resolve stays in registers across
+// segments (a vertex it passes beyond costs no LDS read), the one after it is already on its way from LDS -- one add per
+// beam.  Record b carries the tangent of the NEXT beam of its side in .x: the decision to leave the merge loop never
+// waits for the record that has just been requested.  The assembly loops (sweep_merge_asm, sweep_walk_asm) walk the
+// table through immediate offsets, which cannot be negative: where they run every table address is kept low by the
+// side's bias, and (bp - sb_off) >> 4 is still the beam.  tcur and bm are all the state the C++ loop keeps; the assembly
+// fetches both itself.
+template <bool EXPECT_ONLY, bool SUB>
+constexpr bool sweep_merge_is_asm = !EXPECT_ONLY && !SUB && !SWEEP_MERGE_CXX;
+struct SweepCursor {
+  unsigned sb_off, bp, bp_end;   // table base, pending beam, end of the run
+  int msel, pstep16;             // side + 2 noclamp (wave-uniform: sweep_merge_asm); bytes per beam, signed
+  float tcur;                    // tan of the pending beam (side-signed)
+  sweep_rec bm;                  // the pending beam's record
+  __device__ __forceinline__ int beam() const { return (int)(bp - sb_off) >> 4; }
+};
+template <bool EXPECT_ONLY, bool SUB>
+__device__ __forceinline__ SweepCursor sweep_cursor(const MbesArgs& a, const SweepRun& run, const float4* __restrict__ sbeam,
+                                                    const float* __restrict__ stail, int side) {
+  SweepCursor c;
+  c.sb_off = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)sbeam -
+             (sweep_merge_is_asm<EXPECT_ONLY, SUB> ? (side ? SWEEP_BIAS1 : SWEEP_BIAS0) : 0u);
+  c.bp = c.sb_off + (unsigned)(run.ptr * 16);
+  c.bp_end = c.sb_off + (unsigned)(run.pend * 16);
+  c.msel = side + 2 * a.sweep_noclamp;
+  c.pstep16 = run.pstep * 16;
+  c.tcur = stail[a.n_beams + side];
+  if (SUB && run.first > 0) c.tcur = sbeam[run.ptr - run.pstep].x;   // (a later run of the side: in the record one beam back)
+  const float4 r = sbeam[run.ptr];
+  c.bm.x = r.x;
+  c.bm.y = r.y;
+  c.bm.z = r.z;
+  c.bm.w = r.w;
+  return c;
+}
+
+// One beam resolved at in-plane t = tau: range = t / cos a, beyond r_max (or NaN): r_max.  The table carries the
+// residual's constants (mcl_host_update.h: upload_sweep_beams): (range_b - r) w = max(z w - t (w / cos a), (z - r_max) w).
+// y, z, w: the beam's record; b: its index (EXPECT_ONLY).
+template <bool EXPECT_ONLY>
+__device__ __forceinline__ void sweep_resolve(const MbesArgs& a, float* __restrict__ exp_row, int b, float tau, float y,
+                                              float z, float w, float& acc) {
+  if (EXPECT_ONLY) {
+    exp_row[b] = fminf(tau * y, a.r_max);
+  } else {
+    const float dd = hw_max(fmaf(-tau, y, z), w);
+    acc = fmaf(dd, dd, acc);
+  }
+}
+
+// The beams of the segment (sp, tp) -> (sc, tc): dts, dss, num its constants (seg_tau).  The main kernels: sweep_merge_asm
+// (sel = side + 2 noclamp, wave-uniform: c.msel, or what the caller makes of it).  Expected ranges, runs of a side's beams,
+// the compiler-built variant: the same loop in C++.  One beam on the segment: the crossing of the half line s = t tan a
+// with the chord (e changes sign: <= 0 at prev, >= 0 at cur); then on to the next beam of the table, until the pending
+// beam passes beyond this vertex.
+// (no end-of-table test: the record beyond the last beam has tan a = +inf and tc > 0, so e_cur = -inf.  The loop is
+//  rotated: e_cur of the NEXT beam is formed at the end of the body, one compare decides)
+template <bool EXPECT_ONLY, bool SUB>
+__device__ __forceinline__ void sweep_merge(const MbesArgs& a, int sel, SweepCursor& c, const float4* __restrict__ sbeam,
+                                            float* __restrict__ exp_row, float& acc, float dss, float num, float tp, float sc,
+                                            float tc, float dts) {
+  if (sweep_merge_is_asm<EXPECT_ONLY, SUB>) {
+    sweep_merge_asm(sel, acc, c.bp, dss, num, tp, sc, tc, dts);
+    return;
+  }
+  float e_cur = fmaf(-c.tcur, tc, sc);
+  while (e_cur >= 0.f && (!SUB || c.bp != c.bp_end)) {
+    const float tau = seg_tau(num, fmaf(-c.tcur, dts, dss), tp, tc);
+    sweep_resolve<EXPECT_ONLY>(a, exp_row, c.beam(), tau, c.bm.y, c.bm.z, c.bm.w, acc);
+    c.tcur = c.bm.x;
+    c.bp += c.pstep16;
+    const float4 r = sbeam[c.beam()];
+    c.bm.x = r.x;
+    c.bm.y = r.y;
+    c.bm.z = r.z;
+    c.bm.w = r.w;
+    e_cur = fmaf(-c.tcur, tc, sc);
+  }
+}
+
+// The beams left over when a walk ends for good, from `ptr` on: every one of them misses inside r_max.  Expected ranges:
+// r_max each; else the staged tail sum of their clamp values (SUB: the tail sums end with the lane's run).
+template <bool EXPECT_ONLY>
+__device__ __forceinline__ void sweep_tail(const MbesArgs& a, const SweepRun& run, const float* __restrict__ stail,
+                                           float* __restrict__ exp_row, int ptr, float& acc) {
+  if (EXPECT_ONLY) {
+    for (; ptr != run.pend; ptr += run.pstep) exp_row[ptr] = a.r_max;
+  } else {
+    acc += stail[ptr];
+  }
+}
+
+// SURF 2: every cell split along 00-11; SURF 3: along 10-01.  (Height grids, SURF 0: sweep_side_grid below.)
+// Returns false when the particle has to go to the general kernel.  acc: sum over this side's beams of
+// ((range - expected) * weight)^2; EXPECT_ONLY: expected ranges to exp_row[b] instead.
+// The map border: only the nadir ray (cast without bounds tests) has to stay inside the map; a slice that leaves the
+//   map ENDS there (the NaN ring, top of this file): the beams left return r_max.  That conclusion needs the slice to
+//   cross the border line once: the border's trace in the fan plane must be steeper than the slice can be, which the
+//   fan's tilt, the map's steepest slope and the angle between fan and border decide (sweep_border_final); a level
+//   vehicle always qualifies, a tilted fan slanting along the border over steep terrain goes to the traversal kernel.
+template <int SURF, bool EXPECT_ONLY, bool SUB = false, bool WORK = false>
+__device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P, const float4* __restrict__ sbeam,
+                                           const float* __restrict__ stail, int side, int sub, int nsub,
+                                           float* __restrict__ exp_row, float& acc_out) {
+  acc_out = 0.f;
+  const int nx = a.nx, ny = a.ny;
+  // every test before the first map access feeds ONE verdict (`pre`), tested once
+  bool pre = P.um >= 1.0 && P.um < (double)(nx - 2) && P.vm >= 1.0 && P.vm < (double)(ny - 2);  // (NaN: false)
+  const float c2z = P.c2[2];
+  pre = pre & (c2z >= a.sweep_c2z_min);  // else the fan plane is too far from vertical for the terrain's slopes
+  const double fum = pre ? floor(P.um) : 1.0, fvm = pre ? floor(P.vm) : 1.0;
+  const int I0 = (int)fum, J0 = (int)fvm;
+  const float ul = (float)(P.um - fum), vl = (float)(P.vm - fvm);
+  const float res = a.res, inv_res = (float)a.inv_res;
+  const float sg = side ? -1.f : 1.f;
+  const SweepRun run = sweep_run<SUB>(a, P, side, sub, nsub);
+  const float s_stop = run.s_stop;
+  pre = pre & sweep_footprint(a, P, sg, I0, J0, s_stop);
+  if (!pre) SWEEP_FAIL(1);
+  const SweepMapWindow W = sweep_map_window(a, I0, J0);
+  const SweepStart st0 = sweep_start<SURF, SUB>(a, P, run, W, I0, J0, ul, vl);
+  if (!(st0.r0 < a.r_max)) SWEEP_FAIL(5);
+  if (run.none) return true;
+  SweepFrame F = sweep_frame(a, P, sg, ul, vl);
   auto node = [&](int Pk) {
     SweepNode N;
     N.P = Pk;
     const int j = __builtin_amdgcn_sbfe(Pk, 0, 16), i = (Pk - j) >> 16;
-    const float h = gp[i * nyp + j];
+    const float h = W.gp[i * W.nyp + j];
     const float fi = (float)i, fj = (float)j;
-    N.d = fmaf(pu, fi, fmaf(pv, fj, fmaf(pz, h, p0)));
-    N.s = fmaf(su, fi, fmaf(sv, fj, fmaf(sz, h, s0)));
-    N.t = fmaf(tu, fi, fmaf(tv, fj, fmaf(tz, h, t0)));
+    N.d = F.d(fi, fj, h);
+    N.s = F.s(fi, fj, h);
+    N.t = F.t(fi, fj, h);
     return N;
   };
-  // ---- the triangle under the nadir hit
+  // ---- the triangle under the start hit
   SweepNode A, Bn;
   int C;
   float s_prev, t_prev, s_cur, t_cur;
   {
-    const float uh = fmaf(r0, dxs * inv_res, ul), vh = fmaf(r0, dys * inv_res, vl);
+    const float uh = fmaf(st0.r0, st0.dxs * inv_res, ul), vh = fmaf(st0.r0, st0.dys * inv_res, vl);
     const float cfi = floorf(uh), cfj = floorf(vh);
     const float fu = uh - cfi, fv = vh - cfj;
     const int c00 = (int)cfi * 65536 + (int)cfj;
@@ -592,60 +757,7 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
   bool ok = true;
   int max_steps = (int)(3.f * (s_stop + 4.f * res) * inv_res) + 16;
   if (a.sweep_step_cap) max_steps = min(max_steps, a.sweep_step_cap);   // (MCL_SWEEP_STEP_CAP, tests: no sane walk reaches the limit itself)
-  // the next beam to resolve stays in registers across segments (a vertex it passes beyond costs no LDS read), the one
-  // after it is already on its way from LDS: the table is walked by pointer, one add per beam
-  // (record b carries the tangent of the NEXT beam of its side in .x: the decision to leave the merge loop never waits
-  //  for the record that has just been requested)
-  // (by its LDS byte address: the merge loop of the main kernels is assembly, sweep_merge_asm above)
-  // (the assembly loop walks the table through immediate offsets, which cannot be negative: every table address is
-  //  kept low by the side's bias -- sweep_merge_asm -- and (bp - sb_off) >> 4 is still the beam)
-  const unsigned sb_off = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)sbeam -
-                          ((!EXPECT_ONLY && !SUB && !SWEEP_MERGE_CXX) ? (side ? SWEEP_BIAS1 : SWEEP_BIAS0) : 0u);
-  unsigned bp = sb_off + (unsigned)(ptr * 16);
-  const unsigned bp_end = sb_off + (unsigned)(pend * 16);
-  const int msel = side + 2 * a.sweep_noclamp;
-  const int pstep16 = pstep * 16;
-  float tcur = stail[a.n_beams + side];   // tan of the pending beam (side-signed): all the state the C++ loop keeps
-  if (SUB && first > 0) tcur = sbeam[ptr - pstep].x;   // (a later run of the side: in the record one beam back)
-  sweep_rec bm;   // the pending beam's record
-  {
-    const float4 r = sbeam[ptr];
-    bm.x = r.x;
-    bm.y = r.y;
-    bm.z = r.z;
-    bm.w = r.w;
-  }
-  // the beams of the segment (sp, tp) -> (sc, tc): dts, dss, num its constants (seg_tau)
-  const auto merge_segment = [&](float sp, float tp, float sc, float tc, float dts, float dss, float num) {
-    // (no end-of-table test: the record beyond the last beam has tan a = +inf and tc > 0, so e_cur = -inf.  The
-    //  loop is rotated: e_cur of the NEXT beam is formed at the end of the body, one compare decides)
-    float e_cur = fmaf(-tcur, tc, sc);
-    if (!EXPECT_ONLY && !SUB && !SWEEP_MERGE_CXX) {
-      sweep_merge_asm(msel, acc, bp, dss, num, tp, sc, tc, dts);   // (msel = side + 2 noclamp: wave-uniform)
-    } else {
-      // one beam on the segment (prev -> cur): the crossing of the half line s = t tan a with the chord (e changes
-      // sign: <= 0 at prev, >= 0 at cur); then on to the next beam of the table
-      while (e_cur >= 0.f && (!SUB || bp != bp_end)) {   // until the pending beam passes beyond this vertex
-        const float tau = seg_tau(num, fmaf(-tcur, dts, dss), tp, tc);
-        // range = t / cos a, beyond r_max (or NaN): r_max.  The table carries the residual's constants
-        // (mcl_host_update.h: upload_sweep_beams): (range_b - r) w = max(z w - t (w / cos a), (z - r_max) w)
-        if (EXPECT_ONLY) {
-          exp_row[(int)(bp - sb_off) >> 4] = fminf(tau * bm.y, a.r_max);
-        } else {
-          const float dd = hw_max(fmaf(-tau, bm.y, bm.z), bm.w);
-          acc = fmaf(dd, dd, acc);
-        }
-        tcur = bm.x;
-        bp += pstep16;
-        const float4 r = sbeam[(int)(bp - sb_off) >> 4];
-        bm.x = r.x;
-        bm.y = r.y;
-        bm.z = r.z;
-        bm.w = r.w;
-        e_cur = fmaf(-tcur, tc, sc);
-      }
-    }
-  };
+  SweepCursor cur = sweep_cursor<EXPECT_ONLY, SUB>(a, run, sbeam, stail, side);
   // one step of the walk: resolve the beams of the segment (sp, tp) -> (sc, tc), then cross into the next triangle.
   // Returns true when the walk is over (all beams resolved, stop distance, map border, failure).
   // (EXITS: the three tests that end a walk normally are made every SECOND step -- a step too many finds its beams
@@ -654,15 +766,12 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     // the third node of the triangle across (A, Bn): its height load is in flight while the beams are resolved
     const int Nk = (int)((unsigned)A.P + (unsigned)Bn.P - (unsigned)C);
     const int nj = __builtin_amdgcn_sbfe(Nk, 0, 16), ni = (Nk - nj) >> 16;
-    // (the footprint test keeps a sane walk inside the map; a NaN-driven one is stopped by the buffer's own range check:
-    //  a raw buffer load beyond num_records returns 0 -- no clamp, no 64-bit address arithmetic.  |ni| < 30000 and
-    //  4 ny < 2^23 -- checked on the host --: the full-rate 24-bit multiply)
-    const float hN = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, __mul24(ni, ny4) + ((nj << 2) + g0b), 0, 0));
+    const float hN = W.h(ni, nj);
     const float dts = tc - tp;
     const float dss = sc - sp, num = fmaf(tp, dss, -(sp * dts));   // (the segment's constants of seg_tau)
-    merge_segment(sp, tp, sc, tc, dts, dss, num);
+    sweep_merge<EXPECT_ONLY, SUB>(a, cur.msel, cur, sbeam, exp_row, acc, dss, num, tp, sc, tc, dts);
     if (decltype(EXITS)::value) {
-      if (bp == bp_end) return true;
+      if (cur.bp == cur.bp_end) return true;
       if (sc > s_stop) return true;  // every beam left misses inside r_max (tail below)
       if (step > max_steps) {   // (step: the wave's own count -- every lane still walking has taken as many)
         SWEEP_NOTE(11);
@@ -671,7 +780,7 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
       }
     }
     const float fi = (float)ni, fj = (float)nj;
-    const float dN = fmaf(pu, fi, fmaf(pv, fj, fmaf(pz, hN, p0)));
+    const float dN = F.d(fi, fj, hN);
     // the new node replaces the one on ITS side of the plane; the next edge joins it to the one that stays.  The new
     // node always becomes A, the one that stays moves to Bn only when it was A: five selects and two moves per step
     // (nine selects with fixed roles "A below, Bn above"); the new node's s and t are formed in A's registers, after
@@ -685,8 +794,8 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     Bn.t = keep_a ? A.t : Bn.t;
     A.P = Nk;
     A.d = dN;
-    A.s = fmaf(su, fi, fmaf(sv, fj, fmaf(sz, hN, s0)));
-    A.t = fmaf(tu, fi, fmaf(tv, fj, fmaf(tz, hN, t0)));
+    A.s = F.s(fi, fj, hN);
+    A.t = F.t(fi, fj, hN);
     const float lam = A.d * fast_rcp(A.d - Bn.d);
     const float s_new = fmaf(lam, Bn.s - A.s, A.s), t_new = fmaf(lam, Bn.t - A.t, A.t);
     // every crossing is a vertex of the slice.  The new vertex takes the place of the one before last and the CALLER
@@ -733,8 +842,8 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     // SLOWER than the per-lane one -- 31 vector instructions against 40, but three times the scalar ones, and one scalar
     // unit serves the four SIMDs of a CU -- so by default every wave takes the per-lane loop.
     int uA = __builtin_amdgcn_readfirstlane(A.P), uB = __builtin_amdgcn_readfirstlane(Bn.P), uC = __builtin_amdgcn_readfirstlane(C);
-    const int ug0b = __builtin_amdgcn_readfirstlane(g0b);
-    const bool same = (A.P == uA) & (Bn.P == uB) & (C == uC) & (g0b == ug0b);
+    const int ug0b = __builtin_amdgcn_readfirstlane(W.g0b);
+    const bool same = (A.P == uA) & (Bn.P == uB) & (C == uC) & (W.g0b == ug0b);
     const bool gate = a.sweep_uniform && __builtin_amdgcn_ballot_w64(same) == __builtin_amdgcn_ballot_w64(true);
     // The loop itself leaves no lane behind: every branch in it is the wave's (the compiler keeps a value in scalar
     // registers only where no lane's way through the loop can differ).  A lane whose walk is over (`fin`) stays and is
@@ -750,13 +859,13 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
       const int nj = (int)(short)Nk, ni = (Nk - nj) >> 16;
       // (the offset goes through the load's range-checked vector operand like walk_step's -- one move --: the buffer's
       //  range check is what ends a NaN-driven walk, and the scalar offset operand is outside it)
-      const float hN = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, ni * ny4 + ((nj << 2) + ug0b), 0, 0));
+      const float hN = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(W.grsrc, ni * W.ny4 + ((nj << 2) + ug0b), 0, 0));
       const float dts = tc - tp;
       const float dss = sc - sp, num = fmaf(tp, dss, -(sp * dts));
-      merge_segment(sp, tp, sc, tc, dts, dss, num);
+      sweep_merge<EXPECT_ONLY, SUB>(a, cur.msel, cur, sbeam, exp_row, acc, dss, num, tp, sc, tc, dts);
       unsigned long long out_m = fin_m, over_m = 0ull;   // over before this step, or by its exit tests (walk_step's, in its order)
       if (decltype(EXITS)::value) {
-        out_m |= __builtin_amdgcn_ballot_w64(bp == bp_end) | __builtin_amdgcn_ballot_w64(sc > s_stop);
+        out_m |= __builtin_amdgcn_ballot_w64(cur.bp == cur.bp_end) | __builtin_amdgcn_ballot_w64(sc > s_stop);
         over_m = __builtin_amdgcn_ballot_w64(step > max_steps) & ~out_m;   // (the step limit)
 #ifdef SWEEP_REASONS
         if (__builtin_amdgcn_inverse_ballot_w64(over_m)) SWEEP_NOTE(11);
@@ -765,7 +874,7 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
       }
       const int uA_was = uA;
       const float fi = (float)ni, fj = (float)nj;
-      const float dN = fmaf(pu, fi, fmaf(pv, fj, fmaf(pz, hN, p0)));
+      const float dN = F.d(fi, fj, hN);
       // which node stays is still each lane's own verdict; the wave follows it on the scalar side while it is unanimous
       const bool keep_a = (__float_as_int(dN) ^ __float_as_int(A.d)) < 0;
       const unsigned long long kb = __builtin_amdgcn_ballot_w64(keep_a) & ~out_m;
@@ -785,8 +894,8 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
       }
       uA = Nk;
       A.d = dN;
-      A.s = fmaf(su, fi, fmaf(sv, fj, fmaf(sz, hN, s0)));
-      A.t = fmaf(tu, fi, fmaf(tv, fj, fmaf(tz, hN, t0)));
+      A.s = F.s(fi, fj, hN);
+      A.t = F.t(fi, fj, hN);
       const float lam = A.d * fast_rcp(A.d - Bn.d);
       const float s_new = fmaf(lam, Bn.s - A.s, A.s), t_new = fmaf(lam, Bn.t - A.t, A.t);
       sp = s_new;
@@ -803,7 +912,7 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
         const int last = decltype(EXITS)::value && __builtin_amdgcn_inverse_ballot_w64(over_m) ? uA_was : Nk;
         A.P = now ? last : A.P;
         sp = now ? __builtin_nanf("") : sp;
-        s0 = now ? __builtin_nanf("") : s0;
+        F.s0 = now ? __builtin_nanf("") : F.s0;
         fin_m |= now_m;
       }
       return part;
@@ -830,9 +939,11 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     if ((how & 1) == 0 && !fin) {
       if constexpr (walk_asm) {
         int st = how == 2 ? step : step + 2;
-        const SweepWalkConst kc = {pu, pv, pz, p0, su, sv, sz, s0, tu, tv, tz, t0, s_stop, bp_end, g0b, max_steps};
-        ok = sweep_walk_asm(msel, __builtin_amdgcn_readfirstlane(how == 2 ? 1 : 0), st, a.sweep_wave_cap, ny4, grsrc, kc, acc, bp, A.P, A.d, A.s, A.t, Bn.P, Bn.d,
-                            Bn.s, Bn.t, C, s_prev, t_prev, s_cur, t_cur);   // (a lane that walks on came out of the shared walk with ok)
+        const SweepWalkConst kc = {F.pu, F.pv, F.pz, F.p0, F.su, F.sv, F.sz, F.s0, F.tu, F.tv, F.tz, F.t0,
+                                   s_stop, cur.bp_end, W.g0b, max_steps};
+        ok = sweep_walk_asm(cur.msel, __builtin_amdgcn_readfirstlane(how == 2 ? 1 : 0), st, a.sweep_wave_cap, W.ny4, W.grsrc, kc,
+                            acc, cur.bp, A.P, A.d, A.s, A.t, Bn.P, Bn.d, Bn.s, Bn.t, C, s_prev, t_prev, s_cur,
+                            t_cur);   // (a lane that walks on came out of the shared walk with ok)
       } else {
         n_steps = lane_walk(how == 2 ? step : step + 2, how == 2);
       }
@@ -854,18 +965,11 @@ __device__ __forceinline__ bool sweep_side(const MbesArgs& a, const MbesPose& P,
     // the tail below).  (hN: the height of the node this lane found last, A -- loaded again here rather than kept alive
     // across the loop; su = +-c1x res: the walk keeps no other copy)
     const int lj = __builtin_amdgcn_sbfe(A.P, 0, 16), li = (A.P - lj) >> 16;
-    const float hN = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, __mul24(li, ny4) + ((lj << 2) + g0b), 0, 0));
-    ok = (hN != hN) && sweep_border_final(a, hN, c2z, su * inv_res, sv * inv_res);
+    const float hN = W.h(li, lj);
+    ok = (hN != hN) && sweep_border_final(a, hN, c2z, F.su * inv_res, F.sv * inv_res);
     if (!ok) SWEEP_NOTE(hN != hN ? 10 : 12);
   }
-  if (ok && bp != bp_end) {
-    ptr = (int)(bp - sb_off) >> 4;
-    if (EXPECT_ONLY) {
-      for (; ptr != pend; ptr += pstep) exp_row[ptr] = a.r_max;
-    } else {
-      acc += stail[ptr];   // (SUB: the staged tail sums end with this lane's run)
-    }
-  }
+  if (ok && cur.bp != cur.bp_end) sweep_tail<EXPECT_ONLY>(a, run, stail, exp_row, cur.beam(), acc);
   acc_out = acc;
   return ok;
 }
@@ -891,7 +995,7 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
                                                 const float* __restrict__ stail, int side, int sub, int nsub,
                                                 float* __restrict__ exp_row, float& acc_out) {
   acc_out = 0.f;
-  const int nx = a.nx, ny = a.ny, B = a.n_beams;
+  const int nx = a.nx, ny = a.ny;
   bool pre = P.um >= 1.0 && P.um < (double)(nx - 2) && P.vm >= 1.0 && P.vm < (double)(ny - 2);  // (NaN: false)
   const float c2z = P.c2[2];
   pre = pre & (c2z >= a.sweep_c2z_min);
@@ -900,98 +1004,39 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
   const float ul = (float)(P.um - fum), vl = (float)(P.vm - fvm);
   const float res = a.res, inv_res = (float)a.inv_res, oz = P.oz;
   const float sg = side ? -1.f : 1.f;
-  const int nb_side = side ? a.b_split : B - a.b_split;
-  const int per = SUB ? max((nb_side + nsub - 1) / nsub, 2) : nb_side;
-  const int first = SUB ? min(sub * per, nb_side) : 0, last = SUB ? min(first + per, nb_side) : nb_side;
-  int ptr = side ? a.b_split - 1 - first : a.b_split + first;
-  const int pstep = side ? -1 : 1, pend = side ? a.b_split - 1 - last : a.b_split + last;
-  const bool none = ptr == pend;
-  float s_stop = none ? 0.f : a.r_max;
-  if (!none) {
-    const float2 sc = a.beam_sc[side ? 0 : B - 1];
-    const float dz_e = sc.x * P.c1[2] - sc.y * c2z;
-    if (dz_e < -1e-4f) s_stop = fminf(s_stop, (a.zmin_map - oz) * fast_rcp(dz_e) * fabsf(sc.x));
-  }
-  s_stop += 2.f * res;
+  const SweepRun run = sweep_run<SUB>(a, P, side, sub, nsub);
+  const float s_stop = run.s_stop;
+  pre = pre & sweep_footprint(a, P, sg, I0, J0, s_stop);
+  if (!pre) SWEEP_FAIL(1);
+  const SweepMapWindow W = sweep_map_window(a, I0, J0);
+  const SweepStart st0 = sweep_start<0, SUB>(a, P, run, W, I0, J0, ul, vl);
+  if (!(st0.r0 < a.r_max)) SWEEP_FAIL(5);
+  if (!(st0.r0 > 0.f)) SWEEP_FAIL(9);  // the sensor is at or below the seabed (a grid is solid underneath)
+  if (run.none) return true;
+  const SweepFrame F = sweep_frame(a, P, sg, ul, vl);
   // (s, t) -> cells: u = ul + ax s + bx t, v = vl + ay s + by t
   const float ax = sg * P.c1[0] * inv_res, ay = sg * P.c1[1] * inv_res, bx = -P.c2[0] * inv_res, by = -P.c2[1] * inv_res;
-  {  // footprint (see sweep_side)
-    const float rc = fast_rcp(c2z);
-    const float sl = fabsf(P.c1[2]) * (s_stop + 2.f * res);
-    const float t_hi = ((oz - a.zmin_map) + sl) * rc + res, t_lo = fminf(((oz - a.zmax_map) - sl) * rc - res, 0.f);
-    const float s_hi = s_stop + 2.f * res;
-    const float fi0 = (float)I0, fj0 = (float)J0;
-    // only the start ray (cast below without bounds tests) has to stay inside the map (see sweep_side)
-    const float n0 = fminf(t_lo * bx, t_hi * bx), n1 = fmaxf(t_lo * bx, t_hi * bx);
-    const float m0 = fminf(t_lo * by, t_hi * by), m1 = fmaxf(t_lo * by, t_hi * by);
-    pre = pre & (fi0 + n0 >= 3.f) & (fi0 + n1 <= (float)(nx - 5)) & (fj0 + m0 >= 3.f) & (fj0 + m1 <= (float)(ny - 5));
-    pre = pre & (s_hi * fmaxf(fabsf(ax), fabsf(ay)) + fmaxf(-t_lo, t_hi) * fmaxf(fabsf(bx), fabsf(by)) < 30000.f);
-  }
-  if (!pre) SWEEP_FAIL(1);
-  // the height array inside its ring of NaNs (see sweep_side)
-  const int nyp = a.nyp;
-  const int g0i = (I0 + 1) * nyp + (J0 + 1);
-  const float* __restrict__ gp = a.grid_pad + (size_t)g0i;
-  const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.grid_pad, 0, (nx + 2) * nyp * 4, 0x00020000);
-  const int ny4 = nyp * 4, g0b = g0i * 4;
-  // ---- start of the walk (see sweep_side): the nadir hit, or the hit of the first beam of a later run
-  float dxs = -P.c2[0], dys = -P.c2[1], dzs = -c2z, r0 = 0.f;
-  bool own_start = false;
-  if (SUB && first > 0 && !none) {
-    const float2 sc = a.beam_sc[ptr];
-    dxs = sc.x * P.c1[0] - sc.y * P.c2[0];
-    dys = sc.x * P.c1[1] - sc.y * P.c2[1];
-    dzs = sc.x * P.c1[2] - sc.y * c2z;
-    // like the nadir ray, the start ray is cast without bounds tests: down to z_min (or r_max) it has to stay inside
-    // the map with three nodes of margin -- else this lane walks out from the nadir like the first run
-    const float te = dzs < -1e-4f ? fminf(a.r_max, (a.zmin_map - oz) * fast_rcp(dzs) + res) : a.r_max;
-    const float ex = te * dxs * inv_res, ey = te * dys * inv_res;
-    own_start = ((float)I0 + fminf(ex, 0.f) >= 3.f) & ((float)I0 + fmaxf(ex, 0.f) <= (float)(nx - 5)) &
-                ((float)J0 + fminf(ey, 0.f) >= 3.f) & ((float)J0 + fmaxf(ey, 0.f) <= (float)(ny - 5));
-    if (!own_start) {
-      dxs = -P.c2[0];
-      dys = -P.c2[1];
-      dzs = -c2z;
-    }
-  }
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    r0 = cast_clear<0>(gp, nyp, a, ul, vl, oz, dxs * inv_res, dys * inv_res, dzs, a.zmax_map, a.r_max);
-    if (!SUB || !own_start || ((r0 < a.r_max) & (r0 > 0.f))) break;
-    dxs = -P.c2[0];
-    dys = -P.c2[1];
-    dzs = -c2z;
-    own_start = false;
-  }
-  if (!(r0 < a.r_max)) SWEEP_FAIL(5);
-  if (!(r0 > 0.f)) SWEEP_FAIL(9);  // the sensor is at or below the seabed (a grid is solid underneath)
-  if (none) return true;
-  // ---- plane and in-plane coordinates as affine functions of (i, j, h): lattice coordinates relative to (I0, J0)
-  const float nx_ = P.c1[1] * P.c2[2] - P.c1[2] * P.c2[1], ny_ = P.c1[2] * P.c2[0] - P.c1[0] * P.c2[2],
-              nz_ = P.c1[0] * P.c2[1] - P.c1[1] * P.c2[0];
-  const float pu = nx_ * res, pv = ny_ * res, pz = nz_, p0 = -(pu * ul + pv * vl + pz * oz);
-  const float su = sg * P.c1[0] * res, sv = sg * P.c1[1] * res, sz = sg * P.c1[2], s0 = -(su * ul + sv * vl + sz * oz);
-  const float tu = -P.c2[0] * res, tv = -P.c2[1] * res, tz = -c2z, t0 = -(tu * ul + tv * vl + tz * oz);
   // ---- the cell under the start hit: its two crossings, the outer one is where this side leaves it
   int PA, e, n;                       // packed lattice: node A, the edge vector A -> B, the step into the next cell
   float dA, sA, tA, dB, sB, tB;       // plane function and in-plane coordinates of the edge's nodes
   float sp, tp, sc, tc;               // the arc of the current cell: entry and exit crossing
   float hp00, hp01, hp10, hp11;       // corner heights of the current cell
   {
-    const float uh = fmaf(r0, dxs * inv_res, ul), vh = fmaf(r0, dys * inv_res, vl);
+    const float uh = fmaf(st0.r0, st0.dxs * inv_res, ul), vh = fmaf(st0.r0, st0.dys * inv_res, vl);
     const float cfi = floorf(uh), cfj = floorf(vh);
     const int ci = (int)cfi, cj = (int)cfj;
     const int c00 = ci * 65536 + cj;
-    const float* cp = gp + (ci * nyp + cj);
+    const float* cp = W.gp + (ci * W.nyp + cj);
     hp00 = cp[0];
     hp01 = cp[1];
-    hp10 = cp[nyp];
-    hp11 = cp[nyp + 1];
+    hp10 = cp[W.nyp];
+    hp11 = cp[W.nyp + 1];
     struct Nd { float d, s, t; };
     const auto nd = [&](float fi, float fj, float h) {
       Nd N;
-      N.d = fmaf(pu, fi, fmaf(pv, fj, fmaf(pz, h, p0)));
-      N.s = fmaf(su, fi, fmaf(sv, fj, fmaf(sz, h, s0)));
-      N.t = fmaf(tu, fi, fmaf(tv, fj, fmaf(tz, h, t0)));
+      N.d = F.d(fi, fj, h);
+      N.s = F.s(fi, fj, h);
+      N.t = F.t(fi, fj, h);
       return N;
     };
     const Nd N00 = nd(cfi, cfj, hp00), N10 = nd(cfi + 1.f, cfj, hp10), N01 = nd(cfi, cfj + 1.f, hp01),
@@ -1052,24 +1097,23 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
   bool ok = true;
   const int max_steps = (int)(3.f * (s_stop + 4.f * res) * inv_res) + 16;
   int step = 0;
-  const float4* bp = sbeam + ptr;
-  const float4* const bp_end = sbeam + pend;
+  const float4* bp = sbeam + run.ptr;   // (the grid's merge is the compiler's: the table by pointer, not by LDS byte address like SweepCursor)
+  const float4* const bp_end = sbeam + run.pend;
   // (record b carries the tangent of the NEXT beam of its side: the pending tangent is all the state the loop keeps;
   //  the two-deep queue of rounds 2-3 cost two moves per beam)
   float tcur = stail[a.n_beams + side];       // tan of the pending beam (side-signed)
-  if (SUB && first > 0) tcur = bp[-pstep].x;
+  if (SUB && run.first > 0) tcur = bp[-run.pstep].x;
   float4 bm = bp[0];
   const float rc2z = fast_rcp(c2z);
   const float axay2 = 2.f * (ax * ay), axby2 = 2.f * fmaf(ax, by, ay * bx), bxby2 = 2.f * (bx * by);
   float hC = 0.f, hD = 0.f;   // the far corners loaded last (read after the loop: why did the walk end?)
   for (;;) {
     // the far corners of the cell across (A, B): their heights are in flight while this cell's beams are resolved
-    // (the footprint test keeps a sane walk inside the map; a NaN-driven one is stopped by the buffer's own range check)
     const int PC = PA + n, PD = PC + e;
     const int cj = __builtin_amdgcn_sbfe(PC, 0, 16), ci = (PC - cj) >> 16;
     const int dj = __builtin_amdgcn_sbfe(PD, 0, 16), di = (PD - dj) >> 16;
-    hC = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, __mul24(ci, ny4) + ((cj << 2) + g0b), 0, 0));
-    hD = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, __mul24(di, ny4) + ((dj << 2) + g0b), 0, 0));
+    hC = W.h(ci, cj);
+    hD = W.h(di, dj);
     // ---- the conic of the current cell (the one on the -n side of the edge): in the fan plane the clearance
     // z - h(u, v) over it is G = g0 + g1 s + g2 t + g3 s^2 + g4 s t + g5 t^2 (u, v, z affine in (s, t), h bilinear), and
     // along beam s = t tan a the quadratic g0 + (g1 T + g2) t + (g3 T^2 + g4 T + g5) t^2 -- orc_ray_grid's, with tau = t
@@ -1079,8 +1123,8 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
     const float pB = hp10 - hp00, pC = hp01 - hp00, pD = (hp00 - hp10) - (hp01 - hp11);
     const float uc = ul - (float)i0, vc = vl - (float)j0;
     const float g0 = oz - fmaf(pD * uc, vc, fmaf(pC, vc, fmaf(pB, uc, hp00)));
-    const float g1 = sz - fmaf(pD, fmaf(uc, ay, vc * ax), fmaf(pC, ay, pB * ax));
-    const float g2 = tz - fmaf(pD, fmaf(uc, by, vc * bx), fmaf(pC, by, pB * bx));
+    const float g1 = F.sz - fmaf(pD, fmaf(uc, ay, vc * ax), fmaf(pC, ay, pB * ax));
+    const float g2 = F.tz - fmaf(pD, fmaf(uc, by, vc * bx), fmaf(pC, by, pB * bx));
     const float g3n = pD * axay2, g4n = pD * axby2, g5n = pD * bxby2;   // -2 g3, -2 g4, -2 g5
     // how far (in e = s - t tan a, per unit tan a) the arc can bulge beyond its chord: along the chord the clearance is
     // -twist * du * dv * l (1 - l) <= |twist du dv| / 4, and moving along -c2 changes the clearance at a rate of at
@@ -1091,11 +1135,11 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
     {
       const int Pn = PA + emin + min(n, 0);
       const int j1 = __builtin_amdgcn_sbfe(Pn, 0, 16), i1 = (Pn - j1) >> 16;
-      const int ob = __mul24(i1, ny4) + ((j1 << 2) + g0b);
-      hp00 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, ob, 0, 0));
-      hp01 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, ob + 4, 0, 0));
-      hp10 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, ob, ny4, 0));
-      hp11 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(grsrc, ob + 4, ny4, 0));
+      const int ob = __mul24(i1, W.ny4) + ((j1 << 2) + W.g0b);
+      hp00 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(W.grsrc, ob, 0, 0));
+      hp01 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(W.grsrc, ob + 4, 0, 0));
+      hp10 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(W.grsrc, ob, W.ny4, 0));
+      hp11 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(W.grsrc, ob + 4, W.ny4, 0));
     }
     // ---- the beams of this arc.  (No end-of-table test: the record beyond the last beam has tan a = +inf and tc > 0,
     // so e_cur = -inf.  The loop is rotated: e_cur of the NEXT beam is formed at the end of the body.)
@@ -1115,17 +1159,11 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
       }
       return tau;
     };
-    // range = t / cos a, beyond r_max (or NaN): r_max.  The table carries the residual's constants (mcl_host_update.h:
-    // upload_sweep_beams): (range_b - r) w = max(z w - t (w / cos a), (z - r_max) w); then on to the next beam
+    // the pending beam resolved at tau; then on to the next beam
     const auto take = [&](float tau) {
-      if (EXPECT_ONLY) {
-        exp_row[bp - sbeam] = fminf(tau * bm.y, a.r_max);
-      } else {
-        const float dd = hw_max(fmaf(-tau, bm.y, bm.z), bm.w);
-        acc = fmaf(dd, dd, acc);
-      }
+      sweep_resolve<EXPECT_ONLY>(a, exp_row, (int)(bp - sbeam), tau, bm.y, bm.z, bm.w, acc);
       tcur = bm.x;
-      bp += pstep;
+      bp += run.pstep;
       bm = bp[0];
       e_cur = fmaf(-tcur, tc, sc);
     };
@@ -1161,12 +1199,8 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
     }
     // ---- across the edge: the exit edge of the next cell
     const float fci = (float)ci, fcj = (float)cj, fdi = (float)di, fdj = (float)dj;
-    const float dC = fmaf(pu, fci, fmaf(pv, fcj, fmaf(pz, hC, p0)));
-    const float sC = fmaf(su, fci, fmaf(sv, fcj, fmaf(sz, hC, s0)));
-    const float tC = fmaf(tu, fci, fmaf(tv, fcj, fmaf(tz, hC, t0)));
-    const float dD = fmaf(pu, fdi, fmaf(pv, fdj, fmaf(pz, hD, p0)));
-    const float sD = fmaf(su, fdi, fmaf(sv, fdj, fmaf(sz, hD, s0)));
-    const float tD = fmaf(tu, fdi, fmaf(tv, fdj, fmaf(tz, hD, t0)));
+    const float dC = F.d(fci, fcj, hC), sC = F.s(fci, fcj, hC), tC = F.t(fci, fcj, hC);
+    const float dD = F.d(fdi, fdj, hD), sD = F.s(fdi, fdj, hD), tD = F.t(fdi, fdj, hD);
     const bool viaA = dC > 0.f;               // exit (A, C): A stays, C takes B's place
     const bool viaB = !viaA & !(dD > 0.f);    // exit (D, B): D takes A's place, B stays; else (C, D)
     PA = viaA ? PA : (viaB ? PD : PC);
@@ -1193,17 +1227,10 @@ __device__ __forceinline__ bool sweep_side_grid(const MbesArgs& a, const MbesPos
     // a NaN corner: the next cell is off the map, the slice ends at the border -- final if it cannot come back (see
     // sweep_side; C and D lie beyond the same border line)
     const float hB = hC != hC ? hC : hD;
-    ok = (hB != hB) && sweep_border_final(a, hB, c2z, su * inv_res, sv * inv_res);
+    ok = (hB != hB) && sweep_border_final(a, hB, c2z, F.su * inv_res, F.sv * inv_res);
     if (!ok) SWEEP_NOTE(hB != hB ? 10 : 12);
   }
-  if (ok && bp != bp_end) {
-    ptr = (int)(bp - sbeam);
-    if (EXPECT_ONLY) {
-      for (; ptr != pend; ptr += pstep) exp_row[ptr] = a.r_max;
-    } else {
-      acc += stail[ptr];   // (SUB: the staged tail sums end with this lane's run)
-    }
-  }
+  if (ok && bp != bp_end) sweep_tail<EXPECT_ONLY>(a, run, stail, exp_row, (int)(bp - sbeam), acc);
   acc_out = acc;
   return ok;
 }
@@ -1271,7 +1298,7 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
                                                float* __restrict__ exp_row, float& acc_out) {
   acc_out = 0.f;
   const MeshArgs& ma = a.mesh;
-  const int nx = a.nx, ny = a.ny, B = a.n_beams;  // (cells + 1 of the cell grid: the mesh's bounding box)
+  const int nx = a.nx, ny = a.ny;  // (cells + 1 of the cell grid: the mesh's bounding box)
   bool pre = P.um >= 0.0 && P.um < (double)(nx - 1) && P.vm >= 0.0 && P.vm < (double)(ny - 1);  // (NaN: false)
   const float c2z = P.c2[2];
   // (HOLES, the outline linked: a sensor beyond the bounding box -- the vehicle has left the map and looks back in -- is no
@@ -1283,19 +1310,9 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
   const float ul = (float)(P.um - fum), vl = (float)(P.vm - fvm);
   const float res = a.res, inv_res = (float)a.inv_res, oz = P.oz;
   const float sg = side ? -1.f : 1.f;
-  const int nb_side = side ? a.b_split : B - a.b_split;
-  const int per = SUB ? max((nb_side + nsub - 1) / nsub, 2) : nb_side;   // (>= 2: a later run finds its first two tangents in the records of the two beams before it)
-  const int first = SUB ? min(sub * per, nb_side) : 0, last = SUB ? min(first + per, nb_side) : nb_side;
-  int ptr = side ? a.b_split - 1 - first : a.b_split + first;
-  const int pstep = side ? -1 : 1, pend = side ? a.b_split - 1 - last : a.b_split + last;
-  const bool none = ptr == pend;
-  float s_stop = none ? 0.f : a.r_max;
-  if (!none) {
-    const float2 sc = a.beam_sc[side ? 0 : B - 1];
-    const float dz_e = sc.x * P.c1[2] - sc.y * c2z;
-    if (dz_e < -1e-4f) s_stop = fminf(s_stop, (a.zmin_map - oz) * fast_rcp(dz_e) * fabsf(sc.x));
-  }
-  s_stop += 2.f * res;
+  const SweepRun run = sweep_run<SUB>(a, P, side, sub, nsub);
+  const float s_stop = run.s_stop;
+  const bool none = run.none;
   // (no footprint test: the walk goes from triangle to triangle through the adjacency table and ends at the mesh's
   //  border -- at the OUTER border of a rectangular map for good, under the rule of sweep_side's second pass)
   if (!pre && !off_box) SWEEP_FAIL(1);
@@ -1309,8 +1326,8 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
   // plane and in-plane coordinates from (x - Ox, y - Oy, z - Oz) in metres
   const double Ox = ma.x0 + P.um * (double)ma.cs, Oy = ma.y0 + P.vm * (double)ma.cs;
   const float Oxf = (float)Ox, Oyf = (float)Oy, dOx = (float)(Ox - (double)Oxf), dOy = (float)(Oy - (double)Oyf);
-  const float nx_ = P.c1[1] * P.c2[2] - P.c1[2] * P.c2[1], ny_ = P.c1[2] * P.c2[0] - P.c1[0] * P.c2[2],
-              nz_ = P.c1[0] * P.c2[1] - P.c1[1] * P.c2[0];
+  const SweepNormal nrm = sweep_normal(P);
+  const float nx_ = nrm.x, ny_ = nrm.y, nz_ = nrm.z;
   const float su = sg * P.c1[0], sv = sg * P.c1[1], sz = sg * P.c1[2];
   const float tu = -P.c2[0], tv = -P.c2[1], tz = -c2z;
   struct TinNode {
@@ -1492,53 +1509,9 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
   float acc = 0.f;
   bool ok = true;
   const int max_steps = (int)(6.f * (s_stop + 4.f * res) * inv_res) + 64;  // (triangles may be much smaller than a cell)
-  // (the table is walked by LDS byte address: the merge loop of the main kernel is sweep_merge_asm, as in sweep_side)
-  // (the assembly loop walks the table through immediate offsets, which cannot be negative: every table address is
-  //  kept low by the side's bias -- sweep_merge_asm -- and (bp - sb_off) >> 4 is still the beam)
-  const unsigned sb_off = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)sbeam -
-                          ((!EXPECT_ONLY && !SUB && !SWEEP_MERGE_CXX) ? (side ? SWEEP_BIAS1 : SWEEP_BIAS0) : 0u);
-  unsigned bp = sb_off + (unsigned)(ptr * 16);
-  const unsigned bp_end = sb_off + (unsigned)(pend * 16);
-  const int msel = side + 2 * a.sweep_noclamp;
-  const int pstep16 = pstep * 16;
-  float tcur = stail[a.n_beams + side];
-  if (SUB && first > 0) tcur = sbeam[ptr - pstep].x;
-  sweep_rec bm;   // the pending beam's record
-  {
-    const float4 r = sbeam[ptr];
-    bm.x = r.x;
-    bm.y = r.y;
-    bm.z = r.z;
-    bm.w = r.w;
-  }
+  SweepCursor cur = sweep_cursor<EXPECT_ONLY, SUB>(a, run, sbeam, stail, side);
   float gap_tan = -__builtin_inff();   // (HOLES) the largest tangent of a gap some beam of this lane looked into
   int gaps = 0;                        // (HOLES) gaps crossed on this side
-  // the beams of the segment (dss, num, tp) -> (sc, tc): sweep_merge_asm, or -- expected ranges, runs of a side's beams, the
-  // compiler-built variant -- the same loop in C++
-  const auto merge = [&](const int sel_, const float dss, const float num, const float tp, const float sc, const float tc, const float dts) {
-    if (!EXPECT_ONLY && !SUB && !SWEEP_MERGE_CXX) {
-      sweep_merge_asm(sel_, acc, bp, dss, num, tp, sc, tc, dts);   // (sel = side + 2 noclamp: wave-uniform)
-    } else {
-      float e_cur = fmaf(-tcur, tc, sc);
-      while (e_cur >= 0.f && (!SUB || bp != bp_end)) {
-        const float tau = seg_tau(num, fmaf(-tcur, dts, dss), tp, tc);
-        if (EXPECT_ONLY) {
-          exp_row[(int)(bp - sb_off) >> 4] = fminf(tau * bm.y, a.r_max);
-        } else {
-          const float dd = hw_max(fmaf(-tau, bm.y, bm.z), bm.w);
-          acc = fmaf(dd, dd, acc);
-        }
-        tcur = bm.x;
-        bp += pstep16;
-        const float4 r = sbeam[(int)(bp - sb_off) >> 4];
-        bm.x = r.x;
-        bm.y = r.y;
-        bm.z = r.z;
-        bm.w = r.w;
-        e_cur = fmaf(-tcur, tc, sc);
-      }
-    }
-  };
   // (HOLES) the beams that look into a gap whose far rim the slice meets at (xs, xt) -- tangents up to xs / xt, by the merge's
   // own test against that point scaled by a power of two (the next segment starts there: no beam between the two tests) --
   // hit nothing: each takes its clamp value (z - r_max) w, what the tail sums hold for the beams beyond the end of a walk.
@@ -1548,9 +1521,9 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
   // remembers the tangent, and the walk's t > 0 test carries the comparison.
   const auto gap_beams = [&](const float xs, const float xt) {
     const float K = 0x1p60f;
-    const unsigned bp_in = bp;
-    merge(msel & 1, 1.f, 1.f, xt * K, xs * K, xt * K, 0.f);
-    gap_tan = bp != bp_in ? fmaxf(gap_tan, xs * fast_rcp(xt)) : gap_tan;
+    const unsigned bp_in = cur.bp;
+    sweep_merge<EXPECT_ONLY, SUB>(a, cur.msel & 1, cur, sbeam, exp_row, acc, 1.f, 1.f, xt * K, xs * K, xt * K, 0.f);
+    gap_tan = cur.bp != bp_in ? fmaxf(gap_tan, xs * fast_rcp(xt)) : gap_tan;
   };
   if (HOLES && in_gap && !blind) gap_beams(s_cur, t_cur);   // (the nadir ray goes through a gap: the beams from the nadir to the rim)
   // into the triangle behind half-edge nb, whose record is (hq, hb): the new vertex replaces the one on ITS side of the
@@ -1595,9 +1568,9 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
     const u32 hb = he_nb(nb);
     const float dts = tc - tp;
     const float dss = sc - sp, num = fmaf(tp, dss, -(sp * dts));   // (the segment's constants of seg_tau)
-    merge(msel, dss, num, tp, sc, tc, dts);
+    sweep_merge<EXPECT_ONLY, SUB>(a, cur.msel, cur, sbeam, exp_row, acc, dss, num, tp, sc, tc, dts);
     if (decltype(EXITS)::value) {
-      if (bp == bp_end) return true;
+      if (cur.bp == cur.bp_end) return true;
       if (sc > s_stop) return true;
     }
     if (HOLES ? nb >= ma.tin_nhe : nb >= 0xfffffff0u) {
@@ -1633,7 +1606,7 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
         return true;
       }
       gap_beams(sc, tc);   // the beams that look into the gap miss
-      if (decltype(EXITS)::value && bp == bp_end) return true;
+      if (decltype(EXITS)::value && cur.bp == cur.bp_end) return true;
       ao = true;
       // (the step ends HERE, through this path's own copy of the crossing: state that changed in this branch alone and
       //  went on into the common code cost the loop eight register copies on every step -- 14 % of the kernel)
@@ -1658,14 +1631,7 @@ __device__ __forceinline__ bool sweep_side_tin(const MbesArgs& a, const MbesPose
       if (walk_step(s_cur, t_cur, s_prev, t_prev, step + 1, std::false_type())) break;
     }
   }
-  if (ok && bp != bp_end) {
-    ptr = (int)(bp - sb_off) >> 4;
-    if (EXPECT_ONLY) {
-      for (; ptr != pend; ptr += pstep) exp_row[ptr] = a.r_max;
-    } else {
-      acc += stail[ptr];
-    }
-  }
+  if (ok && cur.bp != cur.bp_end) sweep_tail<EXPECT_ONLY>(a, run, stail, exp_row, cur.beam(), acc);
   acc_out = acc;
   return ok;
 }
