@@ -229,6 +229,13 @@ __device__ __forceinline__ double load_agent(const double* p) {
 __device__ __forceinline__ void store_agent(double* p, double v) {
   __hip_atomic_store(p, v, MCL_ORDER_STORE, __HIP_MEMORY_SCOPE_AGENT);
 }
+// An update kernel publishes the largest log-likelihood each of its waves wrote (the normalisation needs max lw): one
+// atomic per wave on the ordered key, spread over the slots by the wave's index in the launch.  Called by the one lane
+// that holds the wave's maximum; -inf (nothing written, or NaNs only) publishes nothing.
+__device__ __forceinline__ void publish_wave_max(u64* slots, unsigned wave, double wmax) {
+  if (slots && wmax > -__builtin_inf())
+    atomicMax((unsigned long long*)&slots[wave & (MCL_MAX_SLOTS - 1)], ordered_key(wmax));
+}
 // max over the slots an update kernel filled (one wave; every lane gets the result)
 __device__ __forceinline__ double max_from_slots(const u64* slots) {
   u64 k = slots[threadIdx.x & 63];

@@ -1,8 +1,8 @@
 // mcl_host_pure.h -- the host arithmetic of libmcl_hip.so that touches no device: tf.transformations' Euler /
 // quaternion formulas, Philox on the host, the resample exchange's transfer plan, matrix_from_tf, the merge of shards'
 // weight statistics, and the safety bounds kernels rely on unchecked (steepest patch gradient of a height grid, landmark
-// gate radius, the box of the uniform draws, the range update's beam table, the lattice of mcl_pose_modes, the bytes of
-// mcl_history_enable and mcl_drift_enable, the stds of mcl_drift_config, the pose arguments of the acoustic updates and
+// gate radius, the box of the uniform draws, the range update's beam table, which measured ranges count (beam_valid),
+// the lattice of mcl_pose_modes, the bytes of mcl_history_enable and mcl_drift_enable, the stds of mcl_drift_config, the pose arguments of the acoustic updates and
 // mcl_history_bracket), and the lattice, predicate
 // and round plan of mcl_temper (also run by its pick kernel: MCL_HD), and the rules, bandwidth and factor of
 // mcl_regularise (the factor also run by its kernel), and the keys, threshold, predicate,
@@ -353,6 +353,16 @@ int history_bracket_impl(const double* s, int32_t held, double stamp, int32_t* l
   return MCL_OK;
 }
 
+// (functions the kernels run too -- one statement of each rule -- are MCL_HD)
+#if defined(__HIPCC__)
+#define MCL_HD __host__ __device__
+#else
+#define MCL_HD
+#endif
+// A measured range counts in a likelihood when it is positive; zero, negative and NaN mark a beam without a return.  The
+// one statement of the rule: the cast, slice and range kernels, and the host's beam table of the fan sweep.
+MCL_HD inline bool beam_valid(float range) { return range > 0.f; }
+
 // beam table of a range update: B directions normalised in fp64, then rounded; out[4 b ...] = unit x, y, z and the
 // measured range (0 without ranges).  A zero or non-finite direction is refused.
 int normalise_beams(const float* dirs, const float* ranges, int B, float* out) {
@@ -370,11 +380,6 @@ int normalise_beams(const float* dirs, const float* ranges, int B, float* out) {
 
 // ---- ESS-targeted tempering (include/mcl_temper.h): the exponent lattice, the pass predicate and the round plan.  The
 // pick kernel (csrc/mcl_temper.h) runs these very functions on the device: one statement of each rule.
-#if defined(__HIPCC__)
-#define MCL_HD __host__ __device__
-#else
-#define MCL_HD
-#endif
 // beta_j = T[j mod 64] 2^-(j div 64), T[i] = the correctly rounded double of 2^(-i / 64), written with the 17 digits
 // that name one double (no hexadecimal literals: `make host-asan` compiles this file as C++14); 0 <= j <= 2048 (unchecked)
 MCL_HD inline double temper_beta(int j) {

@@ -134,7 +134,7 @@ int upload_sweep_beams(mcl_handle* h, bool with_ranges, int B, double sigma, dou
   for (int b = 0; b < B; ++b) {
     const double ang = (double)h->beam_cache[b];
     const float rm = (with_ranges && (int)h->ranges_host.size() == B) ? h->ranges_host[b] : 0.f;
-    const bool valid = rm > 0.f;  // NaN fails the test (as in the cast kernels)
+    const bool valid = beam_valid(rm);
     nvalid += valid ? 1 : 0;
     // the residual's constants: (range_b - r) w with r = min(t / cos a, r_max) is max(z w - t (w / cos a), (z - r_max) w);
     // an invalid beam has all three zero.  Expected-range calls (no measured ranges) keep 1 / cos a in .y

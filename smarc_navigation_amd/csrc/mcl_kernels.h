@@ -1,6 +1,6 @@
 // mcl_kernels.h -- streaming kernels of the particle filter hot path (gfx950, wave64, fp64 SoA).
-// K1 predict, K2a GPS weight, K3 normalise/quantise, K4 u64 scan + offspring CDF, K5 lost-slot
-// scan + reassign gather + noise, K6 mean/cov, PoseArray export.  All HBM-streaming; no MFMA.
+// K1 predict, K2a GPS weight, K3 quantise, K4 u64 scan + offspring CDF, K6 mean/cov, PoseArray export (the resample
+// chain itself: mcl_resample.h).  All HBM-streaming; no MFMA.
 #pragma once
 #include "mcl_device.h"
 
@@ -175,28 +175,6 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_gps_logw(StatePtrs s, long long n
   }
 }
 
-// ------------------------------------------------------------------ K3: max log-weight
-__global__ void __launch_bounds__(MCL_BLOCK) k_max_partial(const double* __restrict__ v, long long n,
-                                                           double* __restrict__ part) {
-  __shared__ double sh[16];
-  double m = -__builtin_inf();
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    double x = v[i];
-    m = (x > m) ? x : m;  // NaN never wins
-  }
-  m = block_max(m, sh, -__builtin_inf());
-  if (threadIdx.x == 0) part[blockIdx.x] = m;
-}
-__global__ void __launch_bounds__(1024) k_max_final(const double* __restrict__ part, int np,
-                                                    double* __restrict__ out) {
-  __shared__ double sh[16];
-  double m = -__builtin_inf();
-  for (int i = threadIdx.x; i < np; i += blockDim.x) m = part[i] > m ? part[i] : m;
-  m = block_max(m, sh, -__builtin_inf());
-  if (threadIdx.x == 0) out[0] = m;
-}
-
 // ------------------------------------------------------------------ K3/K4: fixed-point weights
 // q_i = floor(w_i / mw * 2^s), w_i = det_exp(lw_i) + 1e-200 (mode 0: GPS, auv_pf.py:165), mw = weight of the max-lw
 // particle; mode 1 (log-likelihoods): floor(exp(lw_i) 2^(s - K)), K the integer exponent of the maximum
@@ -298,95 +276,6 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_offspring_cdf(const u64* __restri
       }
     }
     __syncthreads();
-  }
-}
-
-// ------------------------------------------------------------------ K5: lost-slot ranks
-// zflag_j = [offspring_j == 0]; zcum = inclusive scan over the GLOBAL particle range
-__device__ __forceinline__ u32 offspring(const u32* __restrict__ ncum, long long j) {
-  return ncum[j] - (j > 0 ? ncum[j - 1] : 0u);
-}
-__global__ void __launch_bounds__(MCL_BLOCK) k_zero_tile_sums(const u32* __restrict__ ncum, long long n,
-                                                              u32* __restrict__ tile_sum) {
-  __shared__ u32 sh[16];
-  for (long long tile = blockIdx.x; tile * MCL_SCAN_TILE < n; tile += gridDim.x) {
-    const long long base = tile * MCL_SCAN_TILE;
-    u32 acc = 0;
-#pragma unroll
-    for (int k = 0; k < MCL_SCAN_ITEMS; ++k) {
-      long long j = base + (long long)k * MCL_BLOCK + threadIdx.x;
-      if (j < n) acc += offspring(ncum, j) == 0u ? 1u : 0u;
-    }
-    acc = block_sum(acc, sh);
-    if (threadIdx.x == 0) tile_sum[tile] = acc;
-    __syncthreads();
-  }
-}
-__global__ void __launch_bounds__(MCL_BLOCK) k_zero_scan(const u32* __restrict__ ncum, long long n,
-                                                         const u32* __restrict__ tile_off,
-                                                         u32* __restrict__ zcum) {
-  __shared__ u32 sh[16];
-  for (long long tile = blockIdx.x; tile * MCL_SCAN_TILE < n; tile += gridDim.x) {
-    const long long base = tile * MCL_SCAN_TILE + (long long)threadIdx.x * MCL_SCAN_ITEMS;
-    u32 v[MCL_SCAN_ITEMS];
-    u32 prev = (base > 0 && base - 1 < n) ? ncum[base - 1] : 0u;
-#pragma unroll
-    for (int k = 0; k < MCL_SCAN_ITEMS; ++k) {
-      u32 cur = (base + k < n) ? ncum[base + k] : prev;
-      v[k] = (base + k < n && cur == prev) ? 1u : 0u;
-      prev = cur;
-    }
-    tile_scan_blocked(v, sh);
-    const u32 off = tile_off[tile];
-#pragma unroll
-    for (int k = 0; k < MCL_SCAN_ITEMS; ++k)
-      if (base + k < n) zcum[base + k] = v[k] + off;
-    __syncthreads();
-  }
-}
-
-// a12 + a2: keep/lost/dupes reassign (auv_pf.py:183-198) then add_noise (auv_pf.py:191-192).
-// Survivors stay in their slot; the k-th lost slot (ascending) takes the k-th entry of the dupes
-// list = ancestor j with  d_{j-1} <= k < d_j,  d_j = ncum_j - (j+1) + zcum_j  (cumulative surplus
-// copies).  src reads the pre-resample state (global copy), dst is this shard's slice.
-struct ReassignArgs {
-  StatePtrs src;       // n_global particles (pre-resample), global indexing
-  StatePtrs dst;       // n local particles
-  long long n, n_global, goff;
-  NoiseArgs nz;
-  int add_noise;
-};
-__global__ void __launch_bounds__(MCL_BLOCK) k_reassign_noise(ReassignArgs a, const u32* __restrict__ ncum,
-                                                              const u32* __restrict__ zcum,
-                                                              const double* __restrict__ replay) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < a.n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long g = a.goff + i;
-    long long src = g;
-    if (offspring(ncum, g) == 0u) {
-      const u32 k = zcum[g] - 1u;
-      long long lo = 0, hi = a.n_global;  // first j with d_j > k
-      while (lo < hi) {
-        long long mid = lo + ((hi - lo) >> 1);
-        u32 d = ncum[mid] - (u32)(mid + 1) + zcum[mid];
-        if (d > k)
-          hi = mid;
-        else
-          lo = mid + 1;
-      }
-      src = lo < a.n_global ? lo : a.n_global - 1;
-    }
-    double z[6] = {0, 0, 0, 0, 0, 0};
-    if (a.add_noise) {
-      if (replay) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) z[c] = replay[i * 6 + c];
-      } else {
-        native_normals6(g, a.nz, z);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) a.dst.c[c][i] = a.src.c[c][src] + a.nz.sq[c] * z[c];
   }
 }
 

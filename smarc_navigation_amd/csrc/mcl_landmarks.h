@@ -236,8 +236,7 @@ __global__ void __launch_bounds__(256) k_landmark_update(LandmarkArgs a) {
   if (a.max_slots) {
 #pragma unroll
     for (int o2 = 32; o2 > 0; o2 >>= 1) wmax = fmax(wmax, __shfl_xor(wmax, o2, 64));
-    if (lane == 0 && wmax > -__builtin_inf())
-      atomicMax((unsigned long long*)&a.max_slots[(blockIdx.x * 4 + w) & (MCL_MAX_SLOTS - 1)], ordered_key(wmax));
+    if (lane == 0) publish_wave_max(a.max_slots, blockIdx.x * 4 + w, wmax);
   }
 }
 

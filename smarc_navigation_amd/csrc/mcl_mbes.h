@@ -2,7 +2,9 @@
 // map -> expected ranges -> Gaussian log-likelihood (north_star; no reference symbol).  Since round 2 the
 // default on regular meshes, height grids and height-field TINs is the fan sweep (mcl_sweep.h); these kernels cast
 // what the sweep does not cover (triangle soups with vertical faces / folds / non-manifold edges, unsorted beam tables,
-// small clouds) and the particles it hands over.  Shared by both: the pose records, MbesArgs, cast_clear.
+// small clouds) and the particles it hands over.  Shared by both: the pose records, MbesArgs, cast_clear.  Shared with the
+// fan slice (mcl_slice.h) and the range update (mcl_ranges.h): the scoring of a particle's beams (BeamScore), the pinned
+// pose record (uniform_pose), one ray against the map (cast_lattice_ray / cast_records_ray), own_cell and pose_frame.
 //
 //   k_mbes_pose / k_predict_pose : one thread per particle, fp64 -> sensor pose record (origin in map cell units,
 //                 two columns of R_map_sensor) in HBM (48 B/particle); <true>: also the tile window and fast-path
@@ -28,6 +30,7 @@
 #include <hip/hip_fp16.h>
 
 #include "mcl_device.h"
+#include "mcl_host_pure.h"
 #include "mcl_kernels.h"
 
 #ifndef MBES_WAVES
@@ -42,9 +45,6 @@
 #define MBES_THREADS (MBES_WAVES * 64)
 #ifndef MBES_TILE_FLOATS
 #define MBES_TILE_FLOATS 8192                // 32 KiB tile in LDS
-#endif
-#ifndef MBES_DIR_BINS
-#define MBES_DIR_BINS 16                     // fan-direction bins of the Morton visiting order (<= 16: 4 key bits)
 #endif
 #ifndef MBES_DIR_BINS
 #define MBES_DIR_BINS 16                     // fan-direction bins of the Morton visiting order (<= 16: 4 key bits)
@@ -168,6 +168,20 @@ __device__ __forceinline__ double uniform_f64(double x) {
   const unsigned hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
+// a pose record every lane of the wave has loaded from the same address: pinned in scalar registers, field by field
+__device__ __forceinline__ MbesPose uniform_pose(const MbesPose& Pv) {
+  MbesPose P;
+  P.um = uniform_f64(Pv.um);
+  P.vm = uniform_f64(Pv.vm);
+  P.oz = uniform_f32(Pv.oz);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    P.c1[r] = uniform_f32(Pv.c1[r]);
+    P.c2[r] = uniform_f32(Pv.c2[r]);
+  }
+  P.slot = (u32)__builtin_amdgcn_readfirstlane((int)Pv.slot);
+  return P;
+}
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 
@@ -179,31 +193,40 @@ struct PoseXform {
   double off_R[9];
   double ox, oy, inv_res;
 };
-__device__ __forceinline__ MbesPose make_pose(const PoseXform& T, double x, double y, double z, double sr, double cr,
-                                              double sp, double cp, double sy, double cy) {
+// the vehicle's rotation in the map, Rmp = Rm R(roll, pitch, yaw), and the sensor's origin o = m2o [x y z 1] + Rmp t_off:
+// what the fan's pose record and the range update's per-beam pose (mcl_ranges.h) are both built on
+struct PoseFrame {
+  double Rmp[9], o[3];
+};
+__device__ __forceinline__ PoseFrame pose_frame(const double (&m2o)[12], const double (&off_t)[3], double x, double y, double z,
+                                                double sr, double cr, double sp, double cp, double sy, double cy) {
   const double Rp[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr,
                         sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr,
                         -sp,     cp * sr,                cp * cr};
-  double Rmp[9];
+  PoseFrame F;
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-      Rmp[r * 3 + c] = T.m2o[r * 4 + 0] * Rp[c] + T.m2o[r * 4 + 1] * Rp[3 + c] + T.m2o[r * 4 + 2] * Rp[6 + c];
-  double o[3];
+      F.Rmp[r * 3 + c] = m2o[r * 4 + 0] * Rp[c] + m2o[r * 4 + 1] * Rp[3 + c] + m2o[r * 4 + 2] * Rp[6 + c];
 #pragma unroll
   for (int r = 0; r < 3; ++r)
-    o[r] = (T.m2o[r * 4 + 0] * x + T.m2o[r * 4 + 1] * y + T.m2o[r * 4 + 2] * z + T.m2o[r * 4 + 3]) +
-           (Rmp[r * 3 + 0] * T.off_t[0] + Rmp[r * 3 + 1] * T.off_t[1] + Rmp[r * 3 + 2] * T.off_t[2]);
+    F.o[r] = (m2o[r * 4 + 0] * x + m2o[r * 4 + 1] * y + m2o[r * 4 + 2] * z + m2o[r * 4 + 3]) +
+             (F.Rmp[r * 3 + 0] * off_t[0] + F.Rmp[r * 3 + 1] * off_t[1] + F.Rmp[r * 3 + 2] * off_t[2]);
+  return F;
+}
+__device__ __forceinline__ MbesPose make_pose(const PoseXform& T, double x, double y, double z, double sr, double cr,
+                                              double sp, double cp, double sy, double cy) {
+  const PoseFrame F = pose_frame(T.m2o, T.off_t, x, y, z, sr, cr, sp, cp, sy, cy);
   MbesPose P;
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    P.c1[r] = (float)(Rmp[r * 3 + 0] * T.off_R[1] + Rmp[r * 3 + 1] * T.off_R[4] + Rmp[r * 3 + 2] * T.off_R[7]);
-    P.c2[r] = (float)(Rmp[r * 3 + 0] * T.off_R[2] + Rmp[r * 3 + 1] * T.off_R[5] + Rmp[r * 3 + 2] * T.off_R[8]);
+    P.c1[r] = (float)(F.Rmp[r * 3 + 0] * T.off_R[1] + F.Rmp[r * 3 + 1] * T.off_R[4] + F.Rmp[r * 3 + 2] * T.off_R[7]);
+    P.c2[r] = (float)(F.Rmp[r * 3 + 0] * T.off_R[2] + F.Rmp[r * 3 + 1] * T.off_R[5] + F.Rmp[r * 3 + 2] * T.off_R[8]);
   }
-  P.um = (o[0] - T.ox) * T.inv_res;
-  P.vm = (o[1] - T.oy) * T.inv_res;
-  P.oz = (float)o[2];
+  P.um = (F.o[0] - T.ox) * T.inv_res;
+  P.vm = (F.o[1] - T.oy) * T.inv_res;
+  P.oz = (float)F.o[2];
   P.slot = 0u;
   return P;
 }
@@ -226,21 +249,29 @@ __device__ __forceinline__ PoseXform pose_xform(const MbesArgs& a) {
 // both of them point downward and reach z_min inside r_max, and the window -- one node of margin -- is not clipped by
 // the map border: the clearance walk (cast_clear / cast_fast) then needs no bounds test, and the sensor lies inside
 // the window with a cell of margin by construction.
-struct OwnFan {
+struct OwnCell {
   int I0, J0;              // the sensor's cell (floor of its position in cell units)
   float ul, vl;            // position inside that cell, [0, 1)
-  int wx0, wy0, wx1, wy1;  // window: nodes (grid / structured mesh) or cells (a.cells), inclusive
   bool sane;               // finite position within +-1e9 cells
+};
+struct OwnFan : OwnCell {
+  int wx0, wy0, wx1, wy1;  // window: nodes (grid / structured mesh) or cells (a.cells), inclusive
   bool simple;
 };
+// (um, vm): a sensor's position in global cell units (MbesPose)
+__device__ __forceinline__ OwnCell own_cell(double um, double vm) {
+  OwnCell C;
+  C.sane = fabs(um) < 1e9 && fabs(vm) < 1e9;  // (NaN: false)
+  const double fu = C.sane ? floor(um) : 0.0, fv = C.sane ? floor(vm) : 0.0;
+  C.I0 = (int)fu;
+  C.J0 = (int)fv;
+  C.ul = C.sane ? (float)(um - fu) : 0.f;
+  C.vl = C.sane ? (float)(vm - fv) : 0.f;
+  return C;
+}
 __device__ __forceinline__ OwnFan own_fan(const MbesArgs& a, const MbesPose& P) {
   OwnFan F;
-  F.sane = fabs(P.um) < 1e9 && fabs(P.vm) < 1e9;  // (NaN: false)
-  const double fu = F.sane ? floor(P.um) : 0.0, fv = F.sane ? floor(P.vm) : 0.0;
-  F.I0 = (int)fu;
-  F.J0 = (int)fv;
-  F.ul = F.sane ? (float)(P.um - fu) : 0.f;
-  F.vl = F.sane ? (float)(P.vm - fv) : 0.f;
+  static_cast<OwnCell&>(F) = own_cell(P.um, P.vm);
   const float inv_res = (float)a.inv_res;
   float umin = F.ul, umax = F.ul, vmin = F.vl, vmax = F.vl;
   bool simple = F.sane && a.b_lo >= 0;
@@ -921,6 +952,88 @@ __device__ __forceinline__ float cast_clear(const float* __restrict__ tile, int 
   return root <= r_max ? fmaxf(root, 0.f) : r_max;
 }
 
+// ------------------------------------------------------------------ one ray against the map, whatever it is
+// What the general cast kernel and the range update (mcl_ranges.h) both do with a ray that starts in the particle's own
+// cell (I0, J0) at the fraction (ul, vl) and height oz, with the direction (dx, dy, dz) in the map frame, metres.
+// Nothing here assumes that the rays of a wave have anything in common.
+// Lattice maps (height grids MAP 0, structured meshes MAP 2): where the ray is over the map's rectangle -- t_min = 0 for a
+// sensor over the map --, then the clearance walk on the NaN-ringed heights, the surface by MAP and diag_mode.
+template <int MAP>
+__device__ __forceinline__ float cast_lattice_ray(const MbesArgs& a, int I0, int J0, float ul, float vl, float oz, float dx,
+                                                  float dy, float dz) {
+  const float inv_res = (float)a.inv_res;
+  // the map's cells and nodes relative to the particle's own cell (small integers: exact in fp32)
+  const float cu_lo = (float)(-I0), cu_hi = (float)(a.nx - 2 - I0), cv_lo = (float)(-J0), cv_hi = (float)(a.ny - 2 - J0);
+  const float du = dx * inv_res, dv = dy * inv_res;
+  float t0 = 0.f, t1 = a.r_max;
+  bool miss = false;
+  if (du == 0.f) {
+    miss = ul < cu_lo || ul > cu_hi + 1.f;
+  } else {
+    const float r = fast_rcp(du), ta = (cu_lo - ul) * r, tb = (cu_hi + 1.f - ul) * r;
+    t0 = fmaxf(t0, fminf(ta, tb));
+    t1 = fminf(t1, fmaxf(ta, tb));
+  }
+  if (dv == 0.f) {
+    miss = miss || vl < cv_lo || vl > cv_hi + 1.f;
+  } else {
+    const float r = fast_rcp(dv), ta = (cv_lo - vl) * r, tb = (cv_hi + 1.f - vl) * r;
+    t0 = fmaxf(t0, fminf(ta, tb));
+    t1 = fminf(t1, fmaxf(ta, tb));
+  }
+  if (miss || !(t0 <= t1)) return a.r_max;
+  const float* gpp = a.grid_pad + ((long long)(I0 + 1) * a.nyp + (J0 + 1));   // node (I0, J0) inside the ring (only ever dereferenced at map cells)
+  if (MAP == 0) return cast_clear<0, true>(gpp, a.nyp, a, ul, vl, oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
+  return a.diag_mode == 1 ? cast_clear<2, true>(gpp, a.nyp, a, ul, vl, oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi)
+       : a.diag_mode == 2 ? cast_clear<3, true>(gpp, a.nyp, a, ul, vl, oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi)
+                          : cast_clear<1, true>(gpp, a.nyp, a, ul, vl, oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
+}
+// Triangle records: the clipped general march over the whole cell grid, the water column above the map's highest point
+// skipped.
+__device__ __forceinline__ float cast_records_ray(const MbesArgs& a, int I0, int J0, float ul, float vl, float oz, float dx,
+                                                  float dy, float dz, RayStats& rs) {
+  const float inv_res = (float)a.inv_res;
+  float t_lo = 0.f;
+  if (dz < 0.f && oz > a.zmax_map) t_lo = fmaxf((a.zmax_map - oz) * fast_rcp(dz) - 1e-3f, 0.f);
+  return cast_ray(a.mesh.cell_info, a.mesh.gy, a, I0, J0, a.mesh.gx, a.mesh.gy, ul, vl, oz, dx * inv_res, dy * inv_res, dx, dy,
+                  dz, t_lo, a.r_max, rs);
+}
+
+// ------------------------------------------------------------------ scoring one particle's beams
+// What the cast, fast, slice and slice-group kernels do with the expected range e of a beam -- the determinism rule's
+// other half: a particle's log-likelihood does not depend on which of them cast it.  One wave per particle, lanes =
+// beams b = lane, lane + 64, ...: a lane adds the squared residuals of its valid beams in fp32, in beam order; the
+// lanes' sums are added in fp64 (wave_sum); lw = -1/2 sum - n_valid lognorm.  (The fan sweep folds its sum into the
+// beam table, mcl_sweep.h; the range update adds fp64 terms per particle, mcl_ranges.h.)
+struct BeamScore {
+  float acc = 0.f;
+  int nvalid = 0;
+  __device__ __forceinline__ void add(const MbesArgs& a, float e, float range) {
+    if (beam_valid(range)) {
+      const float d = (range - e) * a.inv_sigma;
+      acc += d * d;
+      ++nvalid;
+    }
+  }
+  // whole wave: lane 0 writes the particle's log-likelihood and keeps the largest one it has written in wmax
+  __device__ __forceinline__ void finish(const MbesArgs& a, long long slot, int lane, double& wmax) const {
+    const double accd = wave_sum((double)acc);
+    const int nv = wave_sum(nvalid);
+    if (lane == 0) {
+      const double v = -0.5 * accd - (double)nv * a.lognorm;
+      a.lw[slot] = v;
+      wmax = v > wmax ? v : wmax;  // NaN never wins
+    }
+  }
+};
+// expected-range calls: is particle i inside the caller's window, and the store of beam b's range into its row
+__device__ __forceinline__ bool expected_wanted(const MbesArgs& a, long long i) {
+  return i >= a.exp_first && i < a.exp_first + a.exp_count;
+}
+__device__ __forceinline__ void expected_store(const MbesArgs& a, long long i, int b, float e) {
+  a.exp_out[(size_t)(i - a.exp_first) * a.n_beams + b] = e;
+}
+
 // ------------------------------------------------------------------ the general cast kernel
 // One wavefront per particle, lanes = consecutive beams, the map in global memory (L2); no LDS, no barriers.
 // MODE 1: the groups k_mbes_fast left on a.worklist (window larger than LDS, a fan that is not simple).
@@ -943,28 +1056,11 @@ __global__ void __launch_bounds__(MBES_THREADS, MAP == 1 ? MBES_MIN_WAVES_MESH -
     const long long j = grp * MBES_WAVES + w;  // position in the visiting order
     if (j >= n_eff) continue;
     const long long ip = perm ? (long long)perm[j] : j;  // the particle's pose record
-    MbesPose P;
-    long long i;   // its state slot (== ip unless the records lie in visiting order)
-    {
-      // the record is wave-uniform: pin it in SGPRs
-      const MbesPose Pv = a.pose[ip];
-      i = (long long)(u32)__builtin_amdgcn_readfirstlane((int)Pv.slot);
-      P.um = uniform_f64(Pv.um);
-      P.vm = uniform_f64(Pv.vm);
-      P.oz = uniform_f32(Pv.oz);
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        P.c1[r] = uniform_f32(Pv.c1[r]);
-        P.c2[r] = uniform_f32(Pv.c2[r]);
-      }
-    }
+    const MbesPose P = uniform_pose(a.pose[ip]);
+    const long long i = (long long)P.slot;   // its state slot (== ip unless the records lie in visiting order)
     const OwnFan F = own_fan(a, P);
-    float acc = 0.f;
-    int nvalid = 0;
+    BeamScore score;
     RayStats rs = {0, 0, 0, 0};
-    // lattice maps: the map's cells and nodes relative to the particle's own cell (small integers: exact in fp32)
-    const float cu_lo = (float)(-F.I0), cu_hi = (float)(a.nx - 2 - F.I0), cv_lo = (float)(-F.J0), cv_hi = (float)(a.ny - 2 - F.J0);
-    const float* gpp = a.grid_pad + ((long long)(F.I0 + 1) * a.nyp + (F.J0 + 1));   // node (I0, J0) inside the ring (only ever dereferenced at map cells)
     for (int b = lane; b < a.n_beams; b += 64) {
       const float2 sc = a.beam_sc[b];
       const float dx = sc.x * P.c1[0] - sc.y * P.c2[0];
@@ -974,52 +1070,17 @@ __global__ void __launch_bounds__(MBES_THREADS, MAP == 1 ? MBES_MIN_WAVES_MESH -
       if (!F.sane) {
         e = a.r_max;  // (NaN / absurd position: every beam misses)
       } else if (MAP != 1) {
-        // where the ray enters the map's rectangle (t_min = 0 for a sensor over the map), if at all
-        const float du = dx * inv_res, dv = dy * inv_res;
-        float t0 = 0.f, t1 = a.r_max;
-        bool miss = false;
-        if (du == 0.f) {
-          miss = F.ul < cu_lo || F.ul > cu_hi + 1.f;
-        } else {
-          const float r = fast_rcp(du), ta = (cu_lo - F.ul) * r, tb = (cu_hi + 1.f - F.ul) * r;
-          t0 = fmaxf(t0, fminf(ta, tb));
-          t1 = fminf(t1, fmaxf(ta, tb));
-        }
-        if (dv == 0.f) {
-          miss = miss || F.vl < cv_lo || F.vl > cv_hi + 1.f;
-        } else {
-          const float r = fast_rcp(dv), ta = (cv_lo - F.vl) * r, tb = (cv_hi + 1.f - F.vl) * r;
-          t0 = fmaxf(t0, fminf(ta, tb));
-          t1 = fminf(t1, fmaxf(ta, tb));
-        }
-        if (miss || !(t0 <= t1)) {
-          e = a.r_max;
-        } else if (MAP == 0) {
-          e = cast_clear<0, true>(gpp, a.nyp, a, F.ul, F.vl, P.oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
-        } else {
-          e = a.diag_mode == 1 ? cast_clear<2, true>(gpp, a.nyp, a, F.ul, F.vl, P.oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi)
-            : a.diag_mode == 2 ? cast_clear<3, true>(gpp, a.nyp, a, F.ul, F.vl, P.oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi)
-                               : cast_clear<1, true>(gpp, a.nyp, a, F.ul, F.vl, P.oz, du, dv, dz, a.zmax_map, a.r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
-        }
+        e = cast_lattice_ray<MAP>(a, F.I0, F.J0, F.ul, F.vl, P.oz, dx, dy, dz);
       } else if (F.simple) {
         e = cast_fast<1>((const float*)(a.mesh.cell_info + ((size_t)F.I0 * a.mesh.gy + F.J0)), a.mesh.gy, a, F.I0, F.J0, F.ul, F.vl,
                          P.oz, dx * inv_res, dy * inv_res, dz, a.zmax_map, a.r_max, rs);
       } else {
-        float t_lo = 0.f;  // skip the water column above the map's highest point
-        if (dz < 0.f && P.oz > a.zmax_map) t_lo = fmaxf((a.zmax_map - P.oz) * fast_rcp(dz) - 1e-3f, 0.f);
-        e = cast_ray(a.mesh.cell_info, a.mesh.gy, a, F.I0, F.J0, a.mesh.gx, a.mesh.gy, F.ul, F.vl, P.oz, dx * inv_res,
-                     dy * inv_res, dx, dy, dz, t_lo, a.r_max, rs);
+        e = cast_records_ray(a, F.I0, F.J0, F.ul, F.vl, P.oz, dx, dy, dz, rs);
       }
       if (EXPECT_ONLY) {
-        if (i >= a.exp_first && i < a.exp_first + a.exp_count)
-          a.exp_out[(size_t)(i - a.exp_first) * a.n_beams + b] = e;
+        if (expected_wanted(a, i)) expected_store(a, i, b, e);
       } else {
-        const float rm = a.ranges[b];
-        if (rm > 0.f) {  // NaN fails the test
-          const float d = (rm - e) * a.inv_sigma;
-          acc += d * d;
-          ++nvalid;
-        }
+        score.add(a, e, a.ranges[b]);
       }
     }
 #ifdef MBES_STATS
@@ -1033,19 +1094,9 @@ __global__ void __launch_bounds__(MBES_THREADS, MAP == 1 ? MBES_MIN_WAVES_MESH -
       }
     }
 #endif
-    if (!EXPECT_ONLY) {
-      const double accd = wave_sum((double)acc);
-      const int nv = wave_sum(nvalid);
-      if (lane == 0) {
-        const double v = -0.5 * accd - (double)nv * a.lognorm;
-        a.lw[i] = v;
-        wmax = v > wmax ? v : wmax;  // NaN never wins
-      }
-    }
+    if (!EXPECT_ONLY) score.finish(a, i, lane, wmax);
   }
-  // the normalisation needs max lw: one atomic per wave on an order-preserving key, spread over the slots
-  if (!EXPECT_ONLY && lane == 0 && a.max_slots && wmax > -__builtin_inf())
-    atomicMax((unsigned long long*)&a.max_slots[(blockIdx.x * MBES_WAVES + w) & (MCL_MAX_SLOTS - 1)], ordered_key(wmax));
+  if (!EXPECT_ONLY && lane == 0) publish_wave_max(a.max_slots, blockIdx.x * MBES_WAVES + w, wmax);
 }
 
 // ------------------------------------------------------------------ the fast cast kernel
@@ -1119,8 +1170,7 @@ __global__ void __launch_bounds__(MBES_THREADS, SURF == 4 ? MBES_MIN_WAVES_MESH 
     const MbesPose P = a.pose[i];
     const OwnFan F = own_fan(a, P);
     const int toff = (F.I0 - cx0) * th + (F.J0 - cy0);
-    float acc = 0.f;
-    int nvalid = 0;
+    BeamScore score;
     for (int b = lane; b < a.n_beams; b += 64) {
       const float2 sc = a.beam_sc[b];
       const float dx = sc.x * P.c1[0] - sc.y * P.c2[0];
@@ -1135,28 +1185,12 @@ __global__ void __launch_bounds__(MBES_THREADS, SURF == 4 ? MBES_MIN_WAVES_MESH 
         e = cast_clear<(CELLS ? 0 : SURF)>(tile + toff, th, a, F.ul, F.vl, P.oz, dx * inv_res, dy * inv_res, dz, a.zmax_map, a.r_max);
       }
       if (EXPECT_ONLY) {
-        if (i >= a.exp_first && i < a.exp_first + a.exp_count)
-          a.exp_out[(size_t)(i - a.exp_first) * a.n_beams + b] = e;
+        if (expected_wanted(a, i)) expected_store(a, i, b, e);
       } else {
-        const float rm = a.ranges[b];
-        if (rm > 0.f) {  // NaN fails the test
-          const float d = (rm - e) * a.inv_sigma;
-          acc += d * d;
-          ++nvalid;
-        }
+        score.add(a, e, a.ranges[b]);
       }
     }
-    if (!EXPECT_ONLY) {
-      const double accd = wave_sum((double)acc);
-      const int nv = wave_sum(nvalid);
-      if (lane == 0) {
-        const double v = -0.5 * accd - (double)nv * a.lognorm;
-        a.lw[i] = v;
-        wmax = v > wmax ? v : wmax;  // NaN never wins
-      }
-    }
+    if (!EXPECT_ONLY) score.finish(a, i, lane, wmax);
   }
-  // the normalisation needs max lw: one atomic per wave on an order-preserving key, spread over the slots
-  if (!EXPECT_ONLY && lane == 0 && a.max_slots && wmax > -__builtin_inf())
-    atomicMax((unsigned long long*)&a.max_slots[(blockIdx.x * MBES_WAVES + w) & (MCL_MAX_SLOTS - 1)], ordered_key(wmax));
+  if (!EXPECT_ONLY && lane == 0) publish_wave_max(a.max_slots, blockIdx.x * MBES_WAVES + w, wmax);
 }

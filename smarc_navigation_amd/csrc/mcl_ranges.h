@@ -45,7 +45,6 @@ __global__ void __launch_bounds__(RANGES_THREADS) k_ranges_update(RangesArgs a) 
   const int lead = lane & ~(bp - 1);   // the particle's first lane
   const long long per_block = RANGES_THREADS >> lg;
   const MbesArgs& m = a.m;
-  const float inv_res = (float)m.inv_res;
   const float r_max = m.r_max;
   // (whole waves run every iteration: the shuffles below need all lanes)
   for (long long first = a.i0 + (long long)blockIdx.x * per_block; first < a.i1; first += (long long)gridDim.x * per_block) {
@@ -55,86 +54,35 @@ __global__ void __launch_bounds__(RANGES_THREADS) k_ranges_update(RangesArgs a) 
     const float4 bt = a.beam[b];
     float e = r_max;
     if (cast) {
-      // ---- the sensor pose of particle i and the direction of beam b in the map, fp64 (make_pose, all three columns)
+      // ---- the sensor pose of particle i and the direction of beam b in the map, fp64 (make_pose's frame, all three columns)
       double sr, cr, sp, cp, sy, cy;
       sincos(m.st[3][i], &sr, &cr);
       sincos(m.st[4][i], &sp, &cp);
       sincos(m.st[5][i], &sy, &cy);
-      const double x = m.st[0][i], y = m.st[1][i], z = m.st[2][i];
-      const double Rp[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr,
-                            sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr,
-                            -sp,     cp * sr,                cp * cr};
-      double Rmp[9];
+      const PoseFrame F = pose_frame(m.m2o, m.off_t, m.st[0][i], m.st[1][i], m.st[2][i], sr, cr, sp, cp, sy, cy);
+      double v[3], d[3];
 #pragma unroll
       for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          Rmp[r * 3 + c] = m.m2o[r * 4 + 0] * Rp[c] + m.m2o[r * 4 + 1] * Rp[3 + c] + m.m2o[r * 4 + 2] * Rp[6 + c];
-      double o[3], v[3], d[3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        o[r] = (m.m2o[r * 4 + 0] * x + m.m2o[r * 4 + 1] * y + m.m2o[r * 4 + 2] * z + m.m2o[r * 4 + 3]) +
-               (Rmp[r * 3 + 0] * m.off_t[0] + Rmp[r * 3 + 1] * m.off_t[1] + Rmp[r * 3 + 2] * m.off_t[2]);
         v[r] = m.off_R[r * 3 + 0] * (double)bt.x + m.off_R[r * 3 + 1] * (double)bt.y + m.off_R[r * 3 + 2] * (double)bt.z;
-      }
 #pragma unroll
-      for (int r = 0; r < 3; ++r) d[r] = Rmp[r * 3 + 0] * v[0] + Rmp[r * 3 + 1] * v[1] + Rmp[r * 3 + 2] * v[2];
+      for (int r = 0; r < 3; ++r) d[r] = F.Rmp[r * 3 + 0] * v[0] + F.Rmp[r * 3 + 1] * v[1] + F.Rmp[r * 3 + 2] * v[2];
       const float dx = (float)d[0], dy = (float)d[1], dz = (float)d[2];
-      const double um = (o[0] - m.ox) * m.inv_res, vm = (o[1] - m.oy) * m.inv_res;
-      const float oz = (float)o[2];
-      // ---- its own cell and the fraction inside it (own_fan without the fan's footprint)
-      const bool sane = fabs(um) < 1e9 && fabs(vm) < 1e9;  // (NaN: false)
-      const double fu = sane ? floor(um) : 0.0, fv = sane ? floor(vm) : 0.0;
-      const int I0 = (int)fu, J0 = (int)fv;
-      const float ul = sane ? (float)(um - fu) : 0.f, vl = sane ? (float)(vm - fv) : 0.f;
-      if (!sane) {
+      const float oz = (float)F.o[2];
+      // ---- its own cell and the fraction inside it, then the map walk of the MBES traversal
+      const OwnCell C = own_cell((F.o[0] - m.ox) * m.inv_res, (F.o[1] - m.oy) * m.inv_res);
+      if (!C.sane) {
         e = r_max;  // (NaN / absurd position: the ray misses)
       } else if (MAP != 1) {
-        // lattice maps (k_mbes_cast): where the ray is over the map's rectangle, cells relative to the particle's own
-        const float cu_lo = (float)(-I0), cu_hi = (float)(m.nx - 2 - I0), cv_lo = (float)(-J0), cv_hi = (float)(m.ny - 2 - J0);
-        const float du = dx * inv_res, dv = dy * inv_res;
-        float t0 = 0.f, t1 = r_max;
-        bool miss = false;
-        if (du == 0.f) {
-          miss = ul < cu_lo || ul > cu_hi + 1.f;
-        } else {
-          const float r = fast_rcp(du), ta = (cu_lo - ul) * r, tb = (cu_hi + 1.f - ul) * r;
-          t0 = fmaxf(t0, fminf(ta, tb));
-          t1 = fminf(t1, fmaxf(ta, tb));
-        }
-        if (dv == 0.f) {
-          miss = miss || vl < cv_lo || vl > cv_hi + 1.f;
-        } else {
-          const float r = fast_rcp(dv), ta = (cv_lo - vl) * r, tb = (cv_hi + 1.f - vl) * r;
-          t0 = fmaxf(t0, fminf(ta, tb));
-          t1 = fminf(t1, fmaxf(ta, tb));
-        }
-        if (miss || !(t0 <= t1)) {
-          e = r_max;
-        } else {
-          const float* gpp = m.grid_pad + ((long long)(I0 + 1) * m.nyp + (J0 + 1));   // node (I0, J0) inside the ring (dereferenced at map cells only)
-          if (MAP == 0)
-            e = cast_clear<0, true>(gpp, m.nyp, m, ul, vl, oz, du, dv, dz, m.zmax_map, r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
-          else if (m.diag_mode == 1)
-            e = cast_clear<2, true>(gpp, m.nyp, m, ul, vl, oz, du, dv, dz, m.zmax_map, r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
-          else if (m.diag_mode == 2)
-            e = cast_clear<3, true>(gpp, m.nyp, m, ul, vl, oz, du, dv, dz, m.zmax_map, r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
-          else
-            e = cast_clear<1, true>(gpp, m.nyp, m, ul, vl, oz, du, dv, dz, m.zmax_map, r_max, t0, t1, cu_lo, cu_hi, cv_lo, cv_hi);
-        }
+        e = cast_lattice_ray<MAP>(m, C.I0, C.J0, C.ul, C.vl, oz, dx, dy, dz);
       } else {
-        // triangle records: the clipped general march over the whole cell grid, water column skipped
         RayStats rs = {0, 0, 0, 0};
-        float t_lo = 0.f;
-        if (dz < 0.f && oz > m.zmax_map) t_lo = fmaxf((m.zmax_map - oz) * fast_rcp(dz) - 1e-3f, 0.f);
-        e = cast_ray(m.mesh.cell_info, m.mesh.gy, m, I0, J0, m.mesh.gx, m.mesh.gy, ul, vl, oz, dx * inv_res, dy * inv_res, dx,
-                     dy, dz, t_lo, r_max, rs);
+        e = cast_records_ray(m, C.I0, C.J0, C.ul, C.vl, oz, dx, dy, dz, rs);
       }
     }
     if (EXPECT_ONLY) {
       if (cast) a.exp_out[(size_t)(i - a.i0) * a.n_beams + b] = e;
     } else {
-      const bool valid = cast && bt.w > 0.f;   // (NaN fails the test)
+      const bool valid = cast && beam_valid(bt.w);
       double term = 0.0;
       if (valid) {
         const double dr = ((double)bt.w - (double)e) / a.sigma;

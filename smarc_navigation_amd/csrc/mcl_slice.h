@@ -151,21 +151,10 @@ __global__ void __launch_bounds__(SLICE_THREADS, 4) k_mbes_slice(MbesArgs a) {
     const long long p_in = listed ? (long long)a.slice_loose[it / SLICE_G] * SLICE_G + it % SLICE_G : it;
     if (p_in >= n_in) continue;
     const long long i = a.in_list ? (long long)a.in_list[p_in] : p_in;
-    if (EXPECT_ONLY && (i < a.exp_first || i >= a.exp_first + a.exp_count)) continue;
-    MbesPose P;
-    u32 slot;   // the particle's state slot: the records may lie in visiting order (mcl_kernels.h: VisitArgs)
-    {
-      const MbesPose Pv = a.pose[i];   // wave-uniform: scalar registers
-      slot = EXPECT_ONLY ? (u32)i : (u32)__builtin_amdgcn_readfirstlane((int)Pv.slot);
-      P.um = uniform_f64(Pv.um);
-      P.vm = uniform_f64(Pv.vm);
-      P.oz = uniform_f32(Pv.oz);
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        P.c1[r] = uniform_f32(Pv.c1[r]);
-        P.c2[r] = uniform_f32(Pv.c2[r]);
-      }
-    }
+    if (EXPECT_ONLY && !expected_wanted(a, i)) continue;
+    const MbesPose P = uniform_pose(a.pose[i]);
+    // the particle's state slot: the records may lie in visiting order (mcl_kernels.h: VisitArgs)
+    const u32 slot = EXPECT_ONLY ? (u32)i : P.slot;
     const float c2z = P.c2[2];
     const float h1 = P.c1[0] * P.c1[0] + P.c1[1] * P.c1[1];   // squared horizontal part of the across-track axis
     const bool sane = fabs(P.um) < 1e9 && fabs(P.vm) < 1e9;
@@ -364,33 +353,18 @@ __global__ void __launch_bounds__(SLICE_THREADS, 4) k_mbes_slice(MbesArgs a) {
     }
     // (the LDS operations of one wave complete in order: no barrier between its lanes' minima and the reads below)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    float acc = 0.f;
-    int nvalid = 0;
+    BeamScore score;
     for (int b = lane; b < B; b += 64) {
       const float e = __uint_as_float(rng[b]);
       if (EXPECT_ONLY) {
-        a.exp_out[(size_t)(i - a.exp_first) * B + b] = e;
+        expected_store(a, i, b, e);
       } else {
-        const float rm = a.ranges[b];
-        if (rm > 0.f) {  // NaN fails the test
-          const float d = (rm - e) * a.inv_sigma;
-          acc += d * d;
-          ++nvalid;
-        }
+        score.add(a, e, a.ranges[b]);
       }
     }
-    if (!EXPECT_ONLY) {
-      const double accd = wave_sum((double)acc);
-      const int nv = wave_sum(nvalid);
-      if (lane == 0) {
-        const double v = -0.5 * accd - (double)nv * a.lognorm;
-        a.lw[slot] = v;
-        wmax = v > wmax ? v : wmax;  // NaN never wins
-      }
-    }
+    if (!EXPECT_ONLY) score.finish(a, slot, lane, wmax);
   }
-  if (!EXPECT_ONLY && lane == 0 && a.max_slots && wmax > -__builtin_inf())
-    atomicMax((unsigned long long*)&a.max_slots[(blockIdx.x * SLICE_WAVES + w) & (MCL_MAX_SLOTS - 1)], ordered_key(wmax));
+  if (!EXPECT_ONLY && lane == 0) publish_wave_max(a.max_slots, blockIdx.x * SLICE_WAVES + w, wmax);
 }
 
 // ------------------------------------------------------------------ the fan slice over GROUPS of spatial neighbours
@@ -684,20 +658,7 @@ __global__ void __launch_bounds__(SLICE_G_THREADS, 6) k_mbes_slice_group(MbesArg
       if (lane == 0) a.lw[a.pose[i].slot] = 0.0;
       if (i >= 0) continue;
 #endif
-      MbesPose P;
-      u32 slot;
-      {
-        const MbesPose Pv = g_pose[mbr];   // wave-uniform: scalar registers
-        slot = (u32)__builtin_amdgcn_readfirstlane((int)Pv.slot);
-        P.um = uniform_f64(Pv.um);
-        P.vm = uniform_f64(Pv.vm);
-        P.oz = uniform_f32(Pv.oz);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          P.c1[r] = uniform_f32(Pv.c1[r]);
-          P.c2[r] = uniform_f32(Pv.c2[r]);
-        }
-      }
+      const MbesPose P = uniform_pose(g_pose[mbr]);
       const float c2z = P.c2[2];
       const float h1 = P.c1[0] * P.c1[0] + P.c1[1] * P.c1[1];
       const bool sane = fabs(P.um) < 1e9 && fabs(P.vm) < 1e9;
@@ -807,26 +768,10 @@ __global__ void __launch_bounds__(SLICE_G_THREADS, 6) k_mbes_slice_group(MbesArg
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      float acc = 0.f;
-      int nvalid = 0;
-      for (int b = lane; b < B; b += 64) {
-        const float e = __uint_as_float(rng[b]);
-        const float rm = rmeas[b];
-        if (rm > 0.f) {  // NaN fails the test
-          const float d = (rm - e) * a.inv_sigma;
-          acc += d * d;
-          ++nvalid;
-        }
-      }
-      const double accd = wave_sum((double)acc);
-      const int nv = wave_sum(nvalid);
-      if (lane == 0) {
-        const double v = -0.5 * accd - (double)nv * a.lognorm;
-        a.lw[slot] = v;
-        wmax = v > wmax ? v : wmax;  // NaN never wins
-      }
+      BeamScore score;
+      for (int b = lane; b < B; b += 64) score.add(a, __uint_as_float(rng[b]), rmeas[b]);
+      score.finish(a, P.slot, lane, wmax);
     }
   }
-  if (lane == 0 && a.max_slots && wmax > -__builtin_inf())
-    atomicMax((unsigned long long*)&a.max_slots[(blockIdx.x * SLICE_G_WAVES + w) & (MCL_MAX_SLOTS - 1)], ordered_key(wmax));
+  if (lane == 0) publish_wave_max(a.max_slots, blockIdx.x * SLICE_G_WAVES + w, wmax);
 }

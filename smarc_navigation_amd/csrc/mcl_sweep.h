@@ -1746,9 +1746,7 @@ __device__ __forceinline__ void sweep_kernel(const MbesArgs& a) {
   if (!EXPECT_ONLY && a.max_slots) {
     // the normalisation needs max lw: one atomic per wave that wrote log-likelihoods, on an order-preserving key
     const double m = wave_max(vmax);
-    if ((threadIdx.x & 63) == 0 && m > -__builtin_inf())
-      atomicMax((unsigned long long*)&a.max_slots[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (MCL_MAX_SLOTS - 1)],
-                ordered_key(m));
+    if ((threadIdx.x & 63) == 0) publish_wave_max(a.max_slots, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), m);
   }
 #ifdef SWEEP_TIMELINE
   {
