@@ -1,5 +1,5 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
-mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h and mcl_quantile.h).
+mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h and mcl_innovation.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -109,6 +109,23 @@ class QuantileResult(C.Structure):
     """mcl_quantile_result (include/mcl_quantile.h)"""
     _fields_ = [('value', C.c_double), ('key', C.c_uint64), ('mass', C.c_uint64), ('total', C.c_uint64),
                 ('n_used', C.c_int64)]
+
+
+class InnovationGateConfig(C.Structure):
+    """mcl_innovation_gate_config (include/mcl_innovation.h)"""
+    _fields_ = [('nis_gate', C.c_double), ('min_support', C.c_double), ('max_gated_fraction', C.c_double)]
+
+
+class InnovationVerdict(C.Structure):
+    """mcl_innovation_verdict (include/mcl_innovation.h)"""
+    _fields_ = [('n_valid', C.c_int32), ('n_candidates', C.c_int32), ('n_gated', C.c_int32), ('inconsistent', C.c_int32),
+                ('nis_sum', C.c_double), ('mean_nu', C.c_double)]
+
+
+# mcl_innovation_beam and mcl_innovation_derived travel as numpy record arrays (40 bytes each): (name, format) pairs
+INNOVATION_BEAM_FIELDS = [('n', '<i8'), ('n_miss', '<i8'), ('n_within', '<i8'), ('s1', '<i8'), ('s2', '<u8')]
+INNOVATION_DERIVED_FIELDS = [('nu', '<f8'), ('var', '<f8'), ('nis', '<f8'), ('support', '<f8'), ('valid', '<i4'),
+                             ('gated', '<i4')]
 
 
 # every symbol include/mcl.h, mcl_dr.h and mcl_map.h declare: name -> (restype, argtypes)
@@ -276,6 +293,17 @@ QUANTILE_SYMBOLS = {
                                             C.POINTER(QuantileResult)]),
 }
 
+# include/mcl_innovation.h: ping innovation statistics and the per-beam outlier gate
+INNOVATION_SYMBOLS = {
+    'mcl_innovation_dirs': (C.c_int, [_vp, _i32, _vp]),
+    'mcl_innovation_sample': (C.c_int, [_i64, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'mcl_innovation_merge': (C.c_int, [_vp, _i32, _i32, _vp]),
+    'mcl_innovation_gate': (C.c_int, [_vp, _i32, _d, C.POINTER(InnovationGateConfig), _vp, C.POINTER(InnovationVerdict)]),
+    'mcl_ping_innovation': (C.c_int, [_vp, _vp, _vp, _i32, _d, _d, _d, _vp, _i32, _vp, _vp, C.POINTER(C.c_int64)]),
+    'mcl_group_ping_innovation': (C.c_int, [C.POINTER(_vp), _i32, _vp, _vp, _i32, _d, _d, _d, _vp, _i32, _vp,
+                                            C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -291,7 +319,8 @@ def load():
     for name, (res, args) in (list(SYMBOLS.items()) + list(RECOVERY_SYMBOLS.items()) + list(MODES_SYMBOLS.items()) +
                               list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items()) +
                               list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
-                              list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items())):
+                              list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items()) +
+                              list(INNOVATION_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

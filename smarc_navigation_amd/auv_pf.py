@@ -109,6 +109,14 @@ DEFAULT_PARAMS = {
     # order statistics, kept in `last_credible`.  There is no standard message for it: nothing more is published.  0 = off:
     # the call is never made and the node computes what it computed without the parameter.
     'credible_prob': 0.0,
+    # Per-beam outlier gate (include/mcl_innovation.h): > 0: every MBES ping is first held against the cloud as it is -- the
+    # innovation of each beam over a strided sample of 4096 particles -- and the beams whose normalised innovation squared
+    # exceeds this value while under 1 % of the sample explains them (fish, a bottom-detection failure) are marked invalid
+    # (range 0) before the unchanged update; 10.83 is chi^2_1 at 0.999.  When more than a quarter of the beams qualify
+    # nothing is gated: the ping disagrees with the cloud as a whole (`last_innovation.inconsistent`).  The verdict of the
+    # last ping is kept in `last_innovation`.  0 = off: the call is never made and the node computes what it computed
+    # without the parameter.
+    'mbes_gate_nis': 0.0,
 }
 
 
@@ -377,6 +385,13 @@ class auv_pf(object):
         self.last_credible = None       # dict(prob, radius, yaw_halfwidth, n_used, centre) of the last loc_loop
         self.credible_calls = 0
         self.regularise_hs = []         # the bandwidth h of each, in order (host arithmetic: regularise_bandwidth)
+        # per-beam outlier gate in front of every MBES update
+        self.mbes_gate_nis = float(p['mbes_gate_nis'])
+        if not self.mbes_gate_nis >= 0.0 or math.isinf(self.mbes_gate_nis):
+            raise ValueError('mbes_gate_nis must be finite and >= 0, not %r' % self.mbes_gate_nis)
+        self.last_innovation = None     # the GateVerdict of the last ping
+        self.gate_calls = 0
+        self.gated_beams = 0            # beams marked invalid so far
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
@@ -544,6 +559,17 @@ class auv_pf(object):
         self.particles.update_landmarks(det, self.landmark_std, k=self.landmark_k, gate=self.landmark_gate,
                                         accumulate=True)
 
+    def _gate(self, ranges, angles, r_max):
+        """the ping's ranges as the update takes them: with mbes_gate_nis > 0 the beams the cloud cannot explain set to 0"""
+        if not self.mbes_gate_nis > 0.0:
+            return ranges
+        ranges, verdict = self.particles.gate_ping(ranges, angles, self.mbes_std, r_max, self.mbes_sensor_offset,
+                                                   nis_gate=self.mbes_gate_nis)
+        self.last_innovation = verdict
+        self.gate_calls += 1
+        self.gated_beams += int(verdict.n_gated)
+        return ranges
+
     def mbes_pc_cb(self, cloud):
         """One ping as a sensor_msgs/PointCloud2 (or msgs.PointCloud2): every point is a beam's hit.  In the sensor
         frame beam b looks along (0, sin a_b, -cos a_b) (include/mcl.h), so a point gives a_b = atan2(y, -z) and the
@@ -562,8 +588,9 @@ class auv_pf(object):
         with self.lock:
             if not (self.old_time and self.has_map):
                 return
-            self.particles.update_mbes(rng[order].astype(np.float32), ang[order].astype(np.float32), self.mbes_std,
-                                       self.mbes_range_max, self.mbes_sensor_offset)
+            ang32 = ang[order].astype(np.float32)
+            self.particles.update_mbes(self._gate(rng[order].astype(np.float32), ang32, self.mbes_range_max), ang32,
+                                       self.mbes_std, self.mbes_range_max, self.mbes_sensor_offset)
             self._accumulate_pending_detections(self._stamp_of(cloud))
             self.resample(self.particles)
 
@@ -573,8 +600,9 @@ class auv_pf(object):
                 return
             n = len(scan.ranges)
             angles = scan.angle_min + scan.angle_increment * np.arange(n)
-            self.particles.update_mbes(np.asarray(scan.ranges, dtype=np.float32), angles.astype(np.float32),
-                                       self.mbes_std, float(scan.range_max), self.mbes_sensor_offset)
+            ang32 = angles.astype(np.float32)
+            self.particles.update_mbes(self._gate(np.asarray(scan.ranges, dtype=np.float32), ang32, float(scan.range_max)),
+                                       ang32, self.mbes_std, float(scan.range_max), self.mbes_sensor_offset)
             self._accumulate_pending_detections(self._stamp_of(scan))
             self.resample(self.particles)
 

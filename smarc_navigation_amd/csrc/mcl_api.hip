@@ -15,6 +15,7 @@
 #include "mcl_host_drift.h"
 #include "mcl_host_regularise.h"
 #include "mcl_host_quantile.h"
+#include "mcl_host_innovation.h"
 #include "mcl_host_recovery.h"
 #include "mcl_host_modes.h"
 
@@ -119,6 +120,7 @@ int mcl_create(const mcl_config* cfg, mcl_handle** out) {
       if (r >= 0.5 && r <= 16.0) h->visit_range = (float)r;
     }
     if (const char* sv = getenv("MCL_VISIT_MIN_N")) h->visit_min_n = std::max(1ll, atoll(sv));
+    if (const char* sv = getenv("MCL_INNOVATION_GROUP")) h->env_innov_group = std::max(0, atoi(sv));
     if (const char* sv = getenv("MCL_SWEEP_NSUB")) h->env_nsub = (sv[0] == '2' || sv[0] == '4') ? sv[0] - '0' : 1;
     h->env_force_comm = on("MCL_FORCE_COMM");
     if (const char* ex = getenv("MCL_EXCHANGE")) h->exch_allgather = strcmp(ex, "allgather") == 0;
@@ -1323,6 +1325,43 @@ int mcl_group_cloud_quantiles(mcl_handle** shards, int32_t ns, const mcl_quantil
     if (!shards[s]) return MCL_ERR_INVALID;
   if (!query || !probs || !out) return fail(shards[0], MCL_ERR_INVALID, "group_cloud_quantiles: null argument");
   return group_quant_run(shards, ns, query, probs, n_probs, out);
+}
+
+// ---- ping innovation statistics and the per-beam gate (include/mcl_innovation.h; host: mcl_host_innovation.h, kernel:
+// csrc/mcl_innovation.h)
+int mcl_innovation_dirs(const float* beam_angles, int32_t B, float* dirs_out) { return innovation_dirs_impl(beam_angles, B, dirs_out); }
+
+int mcl_innovation_sample(int64_t n_global, int32_t max_samples, int64_t* stride, int64_t* count) {
+  return innovation_sample_impl(n_global, max_samples, stride, count);
+}
+
+int mcl_innovation_merge(const mcl_innovation_beam* parts, int32_t n_parts, int32_t B, mcl_innovation_beam* out) {
+  return innovation_merge_impl(parts, n_parts, B, out);
+}
+
+int mcl_innovation_gate(const mcl_innovation_beam* beams, int32_t B, double sigma, const mcl_innovation_gate_config* cfg,
+                        mcl_innovation_derived* per_beam, mcl_innovation_verdict* verdict) {
+  return innovation_gate_impl(beams, B, sigma, cfg, per_beam, verdict);
+}
+
+int mcl_ping_innovation(mcl_handle* h, const float* ranges, const float* beam_angles, int32_t B, double sigma,
+                        double support_k, double r_max, const double sensor_offset[6], int32_t max_samples,
+                        mcl_innovation_beam* beams_out, float* exp_out, int64_t* n_sampled) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!beams_out || !n_sampled) return fail(h, MCL_ERR_INVALID, "ping_innovation: null argument");
+  const InnovPing p = {ranges, beam_angles, B, sigma, support_k, r_max, sensor_offset, max_samples};
+  return innovation_run(h, p, beams_out, exp_out, n_sampled);
+}
+
+int mcl_group_ping_innovation(mcl_handle** shards, int32_t ns, const float* ranges, const float* beam_angles, int32_t B,
+                              double sigma, double support_k, double r_max, const double sensor_offset[6],
+                              int32_t max_samples, mcl_innovation_beam* beams_out, int64_t* n_sampled) {
+  if (!shards || ns < 1) return MCL_ERR_INVALID;
+  for (int s = 0; s < ns; ++s)
+    if (!shards[s]) return MCL_ERR_INVALID;
+  if (!beams_out || !n_sampled) return fail(shards[0], MCL_ERR_INVALID, "group_ping_innovation: null argument");
+  const InnovPing p = {ranges, beam_angles, B, sigma, support_k, r_max, sensor_offset, max_samples};
+  return group_innovation_run(shards, ns, p, beams_out, n_sampled);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

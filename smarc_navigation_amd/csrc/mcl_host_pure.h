@@ -6,7 +6,8 @@
 // mcl_history_bracket), and the lattice, predicate
 // and round plan of mcl_temper (also run by its pick kernel: MCL_HD), and the rules, bandwidth and factor of
 // mcl_regularise (the factor also run by its kernel), and the keys, threshold, predicate,
-// start and bin choice of mcl_cloud_quantiles (include/mcl_quantile.h; the kernels run the same functions).  No HIP header: the
+// start and bin choice of mcl_cloud_quantiles (include/mcl_quantile.h; the kernels run the same functions), and the
+// quantised residual, sample, merge and gate of mcl_ping_innovation (include/mcl_innovation.h).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -25,6 +26,7 @@
 #include "../../include/mcl_drift.h"
 #include "../../include/mcl_regularise.h"
 #include "../../include/mcl_quantile.h"
+#include "../../include/mcl_innovation.h"
 
 namespace {
 
@@ -641,6 +643,133 @@ const char* quantile_query_why(const mcl_quantile_query* q) {
   for (int k = 0; k < 3; ++k)
     if (!std::isfinite(q->centre[k])) return "the centre is not finite";
   return nullptr;
+}
+
+// ---- ping innovation statistics (include/mcl_innovation.h): the quantised residual (the kernel, csrc/mcl_innovation.h,
+// runs innov_quantise itself), the sample, the direction table, the legality of a record, its derived quantities, the
+// merge and the gate.
+constexpr long long INNOV_Q_MAX = 1ll << 24;
+constexpr long long INNOV_MAX_N = MCL_INNOVATION_MAX_SAMPLES;
+// q = rint((r - e) 2^12) clamped to +-2^24 (the bounds are integers: clamping first gives the same number, and keeps the
+// conversion inside the integer's range whatever the measured range is)
+MCL_HD inline long long innov_quantise(float r, float e) {
+  double x = ((double)r - (double)e) * 4096.0;
+  x = x < -16777216.0 ? -16777216.0 : (x > 16777216.0 ? 16777216.0 : x);
+  return (long long)rint(x);
+}
+// |q| <= this counts in n_within
+inline long long innov_q_support(double support_k, double sigma) {
+  const double s = std::floor(support_k * sigma * 4096.0);
+  return s >= 16777216.0 ? INNOV_Q_MAX : (long long)s;   // (the callers refuse NaN and negatives)
+}
+int innovation_sample_impl(int64_t n_global, int32_t max_samples, int64_t* stride, int64_t* count) {
+  if (!stride || !count || n_global < 1 || max_samples < 1 || max_samples > MCL_INNOVATION_MAX_SAMPLES) return MCL_ERR_INVALID;
+  const int64_t s = (n_global - 1) / max_samples + 1;
+  *stride = s;
+  *count = (n_global - 1) / s + 1;
+  return MCL_OK;
+}
+// the slots of a shard [goff, goff + n) whose global id is a multiple of stride: first, first + stride, ...; returns how many
+inline long long innov_shard_sample(long long goff, long long n, long long stride, long long* first) {
+  const long long f = (stride - goff % stride) % stride;
+  *first = f;
+  return f < n ? (n - f - 1) / stride + 1 : 0;
+}
+int innovation_dirs_impl(const float* angles, int32_t B, float* dirs_out) {
+  if (!angles || !dirs_out || B < 1 || B > MCL_INNOVATION_MAX_BEAMS) return MCL_ERR_INVALID;
+  for (int b = 0; b < B; ++b) {
+    if (!std::isfinite(angles[b])) return MCL_ERR_INVALID;
+    const float raw[3] = {0.f, (float)std::sin((double)angles[b]), (float)-std::cos((double)angles[b])};
+    float unit[4];
+    if (normalise_beams(raw, nullptr, 1, unit) != MCL_OK) return MCL_ERR_INVALID;
+    for (int c = 0; c < 3; ++c) dirs_out[3 * b + c] = unit[c];
+  }
+  return MCL_OK;
+}
+// can the record be a sum of the definition?
+inline bool innov_legal(const mcl_innovation_beam& r) {
+  typedef unsigned __int128 u128;
+  if (r.n < 0 || r.n > INNOV_MAX_N || r.n_miss < 0 || r.n_miss > r.n || r.n_within < 0 || r.n_within > r.n) return false;
+  if (r.s1 == INT64_MIN) return false;   // (has no absolute value)
+  const long long a1 = r.s1 < 0 ? -r.s1 : r.s1;
+  if (a1 > r.n * INNOV_Q_MAX) return false;
+  if ((u128)r.s2 > (u128)r.n << 48) return false;
+  return (u128)a1 * (u128)a1 <= (u128)r.n * (u128)r.s2;   // Cauchy-Schwarz
+}
+// the nearest double of a 128-bit integer, ties to even: the leading 64 bits with the rest folded into the last one (a
+// sticky bit, eleven places below the double's last), converted by the hardware, scaled exactly
+inline double innov_u128_to_double(unsigned __int128 v) {
+  const uint64_t hi = (uint64_t)(v >> 64);
+  if (hi == 0) return (double)(uint64_t)v;
+  int sh = 0;
+  while (sh < 64 && (hi >> sh) != 0) ++sh;   // 1 ... 64: bits above the low word
+  const uint64_t top = (uint64_t)(v >> sh);
+  const bool sticky = (v & (((unsigned __int128)1 << sh) - 1)) != 0;
+  return std::ldexp((double)(top | (sticky ? 1ull : 0ull)), sh);
+}
+inline mcl_innovation_derived innov_derive(const mcl_innovation_beam& r, double sigma) {
+  typedef unsigned __int128 u128;
+  mcl_innovation_derived d = {0.0, 0.0, 0.0, 0.0, 0, 0};
+  if (r.n <= 0) return d;
+  const double n = (double)r.n;
+  const unsigned long long a1 = (unsigned long long)(r.s1 < 0 ? -r.s1 : r.s1);
+  const u128 num = (u128)r.n * (u128)r.s2 - (u128)a1 * (u128)a1;
+  d.nu = (double)r.s1 / (n * 4096.0);
+  d.var = innov_u128_to_double(num) / (n * n) * (1.0 / 16777216.0);
+  const double nu2 = d.nu * d.nu, s2 = sigma * sigma, den = d.var + s2;
+  d.nis = nu2 / den;
+  d.support = (double)r.n_within / n;
+  d.valid = 1;
+  return d;
+}
+int innovation_merge_impl(const mcl_innovation_beam* parts, int32_t n_parts, int32_t B, mcl_innovation_beam* out) {
+  if (!parts || !out || n_parts < 1 || B < 1) return MCL_ERR_INVALID;
+  for (int b = 0; b < B; ++b) {
+    mcl_innovation_beam acc = {0, 0, 0, 0, 0};
+    for (int p = 0; p < n_parts; ++p) {
+      const mcl_innovation_beam& r = parts[(size_t)p * B + b];
+      if (!innov_legal(r) || acc.n + r.n > INNOV_MAX_N) return MCL_ERR_INVALID;   // (n within 2^15 keeps every other sum in range)
+      acc.n += r.n;
+      acc.n_miss += r.n_miss;
+      acc.n_within += r.n_within;
+      acc.s1 += r.s1;
+      acc.s2 += r.s2;
+    }
+    out[b] = acc;
+  }
+  return MCL_OK;
+}
+inline mcl_innovation_gate_config innov_default_gate() { return mcl_innovation_gate_config{10.83, 0.01, 0.25}; }
+int innovation_gate_impl(const mcl_innovation_beam* beams, int32_t B, double sigma, const mcl_innovation_gate_config* cfg,
+                         mcl_innovation_derived* per_beam, mcl_innovation_verdict* verdict) {
+  if (!beams || !verdict || B < 1 || !(sigma > 0.0) || !std::isfinite(sigma)) return MCL_ERR_INVALID;
+  const mcl_innovation_gate_config c = cfg ? *cfg : innov_default_gate();
+  if (!(c.nis_gate >= 0.0) || !(c.min_support >= 0.0 && c.min_support <= 1.0) ||
+      !(c.max_gated_fraction >= 0.0 && c.max_gated_fraction <= 1.0))
+    return MCL_ERR_INVALID;
+  for (int b = 0; b < B; ++b)
+    if (!innov_legal(beams[b])) return MCL_ERR_INVALID;
+  mcl_innovation_verdict v = {0, 0, 0, 0, 0.0, 0.0};
+  double nu_sum = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const mcl_innovation_derived d = innov_derive(beams[b], sigma);
+    if (!d.valid) continue;
+    ++v.n_valid;
+    v.nis_sum += d.nis;
+    nu_sum += d.nu;
+    if (d.nis > c.nis_gate && d.support < c.min_support) ++v.n_candidates;
+  }
+  v.mean_nu = v.n_valid > 0 ? nu_sum / (double)v.n_valid : 0.0;
+  v.inconsistent = (double)v.n_candidates > c.max_gated_fraction * (double)v.n_valid ? 1 : 0;
+  v.n_gated = v.inconsistent ? 0 : v.n_candidates;
+  if (per_beam)
+    for (int b = 0; b < B; ++b) {
+      mcl_innovation_derived d = innov_derive(beams[b], sigma);
+      d.gated = d.valid && !v.inconsistent && d.nis > c.nis_gate && d.support < c.min_support ? 1 : 0;
+      per_beam[b] = d;
+    }
+  *verdict = v;
+  return MCL_OK;
 }
 
 }  // namespace

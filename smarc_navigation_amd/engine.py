@@ -145,6 +145,97 @@ class Credible(object):
     centre: tuple
 
 
+INNOVATION_BEAM = np.dtype(_lib.INNOVATION_BEAM_FIELDS)
+INNOVATION_DERIVED = np.dtype(_lib.INNOVATION_DERIVED_FIELDS)
+INNOVATION_QUANTUM = 2.0 ** -12          # metres per unit of the quantised residual
+INNOVATION_DEFAULT_SAMPLES = 4096
+
+
+def innovation_derived(beams, sigma):
+    """the Python mirror of the derived quantities of include/mcl_innovation.h, in Python integers and one rounding per IEEE
+    operation: (nu, var, nis, support) as float64 arrays over the records `beams` (zeros where n = 0)"""
+    b = np.asarray(beams, dtype=INNOVATION_BEAM).reshape(-1)
+    out = np.zeros((4, b.size))
+    s2g = float(sigma) * float(sigma)
+    nf = b['n'].astype(np.float64)
+    if b.size and np.all(b['n'] >= 0) and float(np.max(nf * b['s2'].astype(np.float64))) < 2.0 ** 62:
+        # every numerator fits 64 bits (the usual case: residuals of metres, thousands of samples): the same roundings in numpy
+        live = b['n'] > 0
+        n, s1 = b['n'][live], b['s1'][live]
+        num = n * b['s2'][live].astype(np.int64) - s1 * s1
+        nl = nf[live]
+        nu = s1.astype(np.float64) / (nl * 4096.0)
+        var = num.astype(np.float64) / (nl * nl) * (1.0 / 16777216.0)
+        out[0, live], out[1, live] = nu, var
+        out[2, live], out[3, live] = (nu * nu) / (var + s2g), b['n_within'][live].astype(np.float64) / nl
+        return out[0], out[1], out[2], out[3]
+    for k in range(b.size):
+        n, s1, s2, nw = int(b['n'][k]), int(b['s1'][k]), int(b['s2'][k]), int(b['n_within'][k])
+        if n <= 0:
+            continue
+        nf = float(n)
+        nu = float(s1) / (nf * 4096.0)
+        var = float(n * s2 - s1 * s1) / (nf * nf) * (1.0 / 16777216.0)
+        out[:, k] = (nu, var, (nu * nu) / (var + s2g), float(nw) / nf)
+    return out[0], out[1], out[2], out[3]
+
+
+class PingInnovation(object):
+    """what Engine.ping_innovation returns: the integer records of include/mcl_innovation.h (`beams`, a record array with the
+    fields n, n_miss, n_within, s1, s2, one per beam), the sampled particles (n_sampled), the sigma they are held against,
+    the derived nu (m), var (m^2), nis and support per beam (zeros where n = 0), and with dump=True `expected`, the
+    (n_sampled, B) expected ranges (entries of invalid beams are NaN)"""
+
+    def __init__(self, beams, n_sampled, sigma, expected=None):
+        self.beams = beams
+        self.n_sampled = int(n_sampled)
+        self.sigma = float(sigma)
+        self.expected = expected
+        self.nu, self.var, self.nis, self.support = innovation_derived(beams, sigma)
+
+    n = property(lambda self: self.beams['n'])
+    n_miss = property(lambda self: self.beams['n_miss'])
+    n_within = property(lambda self: self.beams['n_within'])
+    s1 = property(lambda self: self.beams['s1'])
+    s2 = property(lambda self: self.beams['s2'])
+
+    @property
+    def valid(self):
+        return self.beams['n'] > 0
+
+    def mean_nis(self):
+        """mean NIS per valid beam (about 1 on a consistent run; NaN without a valid beam)"""
+        v = self.valid
+        return float(self.nis[v].sum() / v.sum()) if v.any() else math.nan
+
+
+@dataclasses.dataclass
+class GateVerdict(object):
+    """mcl_innovation_verdict and the per-beam output of mcl_innovation_gate as a Python object: mask (bool per beam: gate
+    it), n_gated, inconsistent, n_valid, n_candidates, nis_sum (its degrees of freedom: n_valid), mean_nu, and the derived
+    nu, var, nis, support per beam as the library computed them"""
+    mask: np.ndarray
+    n_gated: int
+    inconsistent: bool
+    n_valid: int
+    n_candidates: int
+    nis_sum: float
+    mean_nu: float
+    nu: np.ndarray
+    var: np.ndarray
+    nis: np.ndarray
+    support: np.ndarray
+
+    def mean_nis(self):
+        return self.nis_sum / self.n_valid if self.n_valid else math.nan
+
+
+def make_gate_config(nis_gate=10.83, min_support=0.01, max_gated_fraction=0.25):
+    c = _lib.InnovationGateConfig()
+    c.nis_gate, c.min_support, c.max_gated_fraction = float(nis_gate), float(min_support), float(max_gated_fraction)
+    return c
+
+
 def make_quantile_query(quantity, centre=None, weighted=False):
     q = _lib.QuantileQuery()
     q.quantity = int(_QUANTITIES.get(quantity, quantity)) if isinstance(quantity, str) else int(quantity)
@@ -609,6 +700,39 @@ class Engine(object):
                                               _ptr(out)))
         return out
 
+    # ---- ping innovation statistics and the per-beam gate (include/mcl_innovation.h)
+    def ping_innovation(self, ranges, beam_angles, sigma, r_max, sensor_offset=None, max_samples=INNOVATION_DEFAULT_SAMPLES,
+                        support_k=3.0, dump=False):
+        """hold a ping against the cloud as it is (after predict, before the update): per beam the integer sums of the
+        quantised residual over a strided sample of at most max_samples particles (mcl_ping_innovation) -- a PingInnovation
+        of THIS shard's sampled particles.  Nothing of the filter changes."""
+        r, a, so = _f32(ranges).reshape(-1), _f32(beam_angles).reshape(-1), _f64(sensor_offset)
+        if r.size != a.size:
+            raise ValueError('ping_innovation: %d ranges for %d beam angles' % (r.size, a.size))
+        beams = np.zeros(max(a.size, 1), INNOVATION_BEAM)
+        exp = None
+        if dump:
+            stride, _ = innovation_sample(self.n_global, max_samples)
+            exp = np.full(((self.n + stride - 1) // stride, a.size), np.nan, np.float32)
+        ns = C.c_int64(0)
+        self._ck(self.lib.mcl_ping_innovation(self.h, _ptr(r), _ptr(a), a.size, float(sigma), float(support_k), float(r_max),
+                                              _ptr(so), int(max_samples), _ptr(beams), _ptr(exp), C.byref(ns)))
+        if exp is not None:
+            exp = exp[:ns.value]
+            exp[:, ~(r > 0)] = np.nan   # (the library leaves the entries of invalid beams unwritten)
+        return PingInnovation(beams[:a.size], ns.value, sigma, exp)
+
+    def gate_ping(self, ranges, beam_angles, sigma, r_max, sensor_offset=None, max_samples=INNOVATION_DEFAULT_SAMPLES,
+                  support_k=3.0, nis_gate=10.83, min_support=0.01, max_gated_fraction=0.25):
+        """(ranges_masked, verdict): ping_innovation, then innovation_gate; the gated beams' ranges are set to 0 -- the mark
+        update_mbes skips -- in a float32 copy.  verdict.innovation is the PingInnovation."""
+        inn = self.ping_innovation(ranges, beam_angles, sigma, r_max, sensor_offset, max_samples, support_k)
+        verdict = innovation_gate(inn.beams, sigma, nis_gate, min_support, max_gated_fraction)
+        verdict.innovation = inn
+        masked = np.array(_f32(ranges).reshape(-1), copy=True)
+        masked[verdict.mask] = 0.0
+        return masked, verdict
+
     def set_landmarks(self, xyz):
         a = _f64(xyz)
         self._ck(self.lib.mcl_set_landmarks(self.h, _ptr(a), a.shape[0]))
@@ -943,6 +1067,72 @@ def group_cloud_quantiles(engines, quantity, probs, centre=None, weighted=False)
     out = (_lib.QuantileResult * max(p.size, 1))()
     _lib.check(lib.mcl_group_cloud_quantiles(hs, ns, C.byref(q), _ptr(p), p.size, out), engines[0].h)
     return [Quantile.from_c(out[k]) for k in range(p.size)]
+
+
+def innovation_sample(n_global, max_samples=INNOVATION_DEFAULT_SAMPLES):
+    """(stride, count) of the strided sample (mcl_innovation_sample: host arithmetic)"""
+    st, ct = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().mcl_innovation_sample(int(n_global), int(max_samples), C.byref(st), C.byref(ct)))
+    return int(st.value), int(ct.value)
+
+
+def innovation_dirs(beam_angles):
+    """(B, 3) float32: the unit directions the innovation kernel casts along (mcl_innovation_dirs: host arithmetic)"""
+    a = _f32(beam_angles).reshape(-1)
+    out = np.zeros((max(a.size, 1), 3), np.float32)
+    _lib.check(_lib.load().mcl_innovation_dirs(_ptr(a), a.size, _ptr(out)))
+    return out[:a.size]
+
+
+def _innovation_records(beams):
+    if isinstance(beams, PingInnovation):
+        beams = beams.beams
+    return np.ascontiguousarray(beams, dtype=INNOVATION_BEAM).reshape(-1)
+
+
+def merge_innovation(parts):
+    """the records of the union of several shards' samples (mcl_innovation_merge: host arithmetic): parts are
+    PingInnovation objects or record arrays of equal length; returns a record array"""
+    recs = [_innovation_records(p) for p in parts]
+    B = recs[0].size if recs else 0
+    if any(r.size != B for r in recs):
+        raise ValueError('merge_innovation: the parts differ in their beam count')
+    stack = np.ascontiguousarray(np.stack(recs)) if recs else np.zeros((0, 0), INNOVATION_BEAM)
+    out = np.zeros(max(B, 1), INNOVATION_BEAM)
+    _lib.check(_lib.load().mcl_innovation_merge(_ptr(stack), len(recs), B, _ptr(out)))
+    return out[:B]
+
+
+def innovation_gate(beams, sigma, nis_gate=10.83, min_support=0.01, max_gated_fraction=0.25):
+    """the derived quantities and the gate of include/mcl_innovation.h over the records `beams` (a PingInnovation or a
+    record array): a GateVerdict (mcl_innovation_gate: host arithmetic)"""
+    rec = _innovation_records(beams)
+    cfg = make_gate_config(nis_gate, min_support, max_gated_fraction)
+    per = np.zeros(max(rec.size, 1), INNOVATION_DERIVED)
+    v = _lib.InnovationVerdict()
+    _lib.check(_lib.load().mcl_innovation_gate(_ptr(rec), rec.size, float(sigma), C.byref(cfg), _ptr(per), C.byref(v)))
+    per = per[:rec.size]
+    return GateVerdict(mask=per['gated'] != 0, n_gated=int(v.n_gated), inconsistent=bool(v.inconsistent),
+                       n_valid=int(v.n_valid), n_candidates=int(v.n_candidates), nis_sum=float(v.nis_sum),
+                       mean_nu=float(v.mean_nu), nu=per['nu'].copy(), var=per['var'].copy(), nis=per['nis'].copy(),
+                       support=per['support'].copy())
+
+
+def group_ping_innovation(engines, ranges, beam_angles, sigma, r_max, sensor_offset=None,
+                          max_samples=INNOVATION_DEFAULT_SAMPLES, support_k=3.0):
+    """Engine.ping_innovation over shards that together hold the cloud (mcl_group_ping_innovation): the unsharded call's
+    records bit for bit, for any split.  A PingInnovation (no dump)."""
+    lib = _lib.load()
+    ns = len(engines)
+    hs = (C.c_void_p * ns)(*[e.h for e in engines])
+    r, a, so = _f32(ranges).reshape(-1), _f32(beam_angles).reshape(-1), _f64(sensor_offset)
+    if r.size != a.size:
+        raise ValueError('group_ping_innovation: %d ranges for %d beam angles' % (r.size, a.size))
+    beams = np.zeros(max(a.size, 1), INNOVATION_BEAM)
+    n = C.c_int64(0)
+    _lib.check(lib.mcl_group_ping_innovation(hs, ns, _ptr(r), _ptr(a), a.size, float(sigma), float(support_k), float(r_max),
+                                             _ptr(so), int(max_samples), _ptr(beams), C.byref(n)), engines[0].h)
+    return PingInnovation(beams[:a.size], n.value, sigma)
 
 
 def merge_weight_stats(parts):

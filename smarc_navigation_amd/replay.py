@@ -10,7 +10,8 @@ plus the RMSE between the PF mean pose and a reference track (the "pose RMSE vs 
 
 Stream file (np.savez): stamp[n], v[n,3], wz[n], q[n,4], z[n]  (odometry, /sam/dr/odom);
 optional gps_idx[k], gps_xy_utm[k,2]; optional mbes_idx[m], mbes_ranges[m,B], mbes_angles[B],
-mbes_range_max; optional dr_xyz[n,3] (dead-reckoning track), truth_xyz[n,3]; t0.
+mbes_range_max; optional dr_xyz[n,3] (dead-reckoning track), truth_xyz[n,3]; t0; optional map_z, map_origin,
+map_res (a height grid the stream carries: replayed over when no map is given).
 A raw-sensor file (ev_t, ev_kind, ev_data as synth.raw_sensor_events makes them; optional gps_map,
 pressure_tf) is first run through the dead-reckoning integrator (--raw).
 
@@ -250,16 +251,50 @@ SYNTH_PARAMS = dict(measurement_std=0.5, init_covariance='[0.01, 0.01, 0.0, 0.0,
                     resampling_noise_covariance='[0.0, 0.0, 0.0, 0.0, 0.0, 0.0]')
 
 
-def synthetic_stream(n_steps=3000, current=(0.0, 0.0), yaw_rate_bias=0.0, gps_every=50, gps_sigma=0.5, seed=0):
+def synthetic_stream(n_steps=3000, current=(0.0, 0.0), yaw_rate_bias=0.0, gps_every=50, gps_sigma=0.5, seed=0, mbes_every=0,
+                     beams=64, mbes_sigma=0.1, mbes_range_max=100.0, outliers=None):
     """A stream made here instead of read from a file (`synth` / `synth:N` on the command line): synth.odom_stream with a
     water current and a yaw-rate bias the odometry does not see, the truth track, and a GPS fix of gps_sigma metres every
-    gps_every samples (identity frames: utm = map = odom).  drift_truth = (cx, cy, bw) is what drift states should find."""
+    gps_every samples (identity frames: utm = map = odom).  drift_truth = (cx, cy, bw) is what drift states should find.
+    mbes_every = K > 0 (needs the GPU): also a multibeam ping of `beams` beams every K samples over synth.bathymetry_grid's
+    default map, which the stream then carries (map_z, map_origin, map_res): the ranges the library expects at the truth,
+    with mbes_sigma metres of noise and, outliers = (fraction, shorten_m), that share of the beams shorten_m short
+    (synth.noisy_pings: both from seeds of their own, so the rest of the stream keeps its numbers; mbes_outliers marks them)."""
     from . import synth
     st = synth.odom_stream(int(n_steps), current=current, yaw_rate_bias=yaw_rate_bias)
     idx, xy = synth.gps_fixes(st['truth'], np.identity(4), every=int(gps_every), sigma=float(gps_sigma), seed=int(seed) + 2)
     st.update(truth_xyz=st['truth'][:, :3].copy(), gps_idx=idx, gps_xy_utm=xy,
               drift_truth=np.array([float(current[0]), float(current[1]), float(yaw_rate_bias)]))
+    if mbes_every > 0:
+        from . import engine
+        origin, res = (-64.0, -256.0), 1.0
+        z = synth.bathymetry_grid(512, 512, res, origin)
+        at = np.arange(int(mbes_every) - 1, int(n_steps), int(mbes_every))
+        ba = synth.beam_angles(int(beams))
+        cast = engine.Engine(at.size, rng_mode=engine.RNG_REPLAY)
+        cast.set_map_grid(z, origin, res)
+        cast.set_particles(np.ascontiguousarray(st['truth'][at].T))
+        clean = cast.mbes_expected(0, at.size, ba, float(mbes_range_max))
+        cast.close()
+        ranges, hit = synth.noisy_pings(clean, mbes_sigma, mbes_range_max, outliers, seed=int(seed) + 4)
+        st.update(mbes_idx=at, mbes_ranges=ranges, mbes_angles=ba, mbes_range_max=float(mbes_range_max), mbes_outliers=hit,
+                  map_z=z, map_origin=np.array(origin), map_res=res)
     return st
+
+
+def innovation_summary(nis_rows, nu_rows):
+    """what --innovation adds to a summary, from the per-beam NIS and nu of every ping (NaN: the beam had no return): the
+    run's mean NIS per beam -- about 1 when sigma is right, well above when it is too small --, their mean, the mean nu"""
+    nis, nu = np.asarray(nis_rows, dtype=np.float64), np.asarray(nu_rows, dtype=np.float64)
+    out = dict(innovation_pings=int(nis.shape[0]))
+    seen = np.isfinite(nis)
+    if seen.any():
+        count = seen.sum(axis=0)
+        per_beam = np.where(seen, nis, 0.0).sum(axis=0) / np.maximum(count, 1)     # (0 for a beam that never had a return)
+        out['innovation_nis_per_beam'] = [float(v) for v in per_beam]
+        out['innovation_mean_nis'] = float(per_beam[count > 0].mean())
+        out['innovation_mean_nu'] = float(nu[seen].mean())
+    return out
 
 
 def credible_summary(prob, radii, est_xyz, truth_xyz=None):
@@ -277,24 +312,31 @@ def credible_summary(prob, radii, est_xyz, truth_xyz=None):
 
 
 def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0,
-           fix_period=0.0, fix_latency=0.0, fix_seed=0):
+           fix_period=0.0, fix_latency=0.0, fix_seed=0, innovation=False):
     """Drive the node with a recorded stream; returns dict(pf_xyz[n_pub,3], pub_idx, summary).  smooth_lag > 0: also
     out['smooth'], the lag-smooth_lag smoothed track beside the filtered one, one entry per resample of the node
     (SmoothTrack; the node's particle genealogy: include/mcl_history.h).  fix_period > 0 (a stream with truth_xyz): acoustic
     fixes every fix_period seconds with the node's `fix_std` of noise, delivered fix_latency seconds late to fix_cb
     (make_fixes); the node's `fix_history_depth` decides whether they are applied to the past or to the present; the
-    summary gains fixes_applied, fixes_dropped and fix_mean_lag (mean age of the applied fixes, seconds)."""
+    summary gains fixes_applied, fixes_dropped and fix_mean_lag (mean age of the applied fixes, seconds).  innovation: every
+    ping is first held against the cloud (Engine.ping_innovation, include/mcl_innovation.h; nothing of the filter changes)
+    and the summary gains innovation_summary's keys: what to tune the node's mbes_std with.  A node with mbes_gate_nis > 0
+    adds gate_pings, gate_n_gated, gate_inconsistent.  A stream that carries its map (map_z, map_origin, map_res) is
+    replayed over it when neither grid nor mesh is given."""
     from . import auv_pf as node
     from . import msgs
     if smooth_lag > 0 and fix_period > 0:
         raise ValueError(FIX_SMOOTH_CLASH)
     tr = node.RecordingTransport(utm2map)
     pf = node.auv_pf(params or {}, m2o_mat=m2o, transport=tr)
+    if grid is None and mesh is None and 'map_z' in stream:
+        grid = dict(z=stream['map_z'], origin=tuple(float(v) for v in stream['map_origin']), res=stream['map_res'])
     if grid is not None:
         pf.set_map_grid(grid['z'], grid['origin'], float(grid['res']))
     if mesh is not None:
         pf.set_map_mesh(mesh['verts'], mesh['tris'])
     n = len(stream['stamp'])
+    inn_nis, inn_nu, n_inconsistent = [], [], 0
     pf.start_timing(float(stream['t0']) if 't0' in stream else float(stream['stamp'][0]) - 0.02)
     gps_at = {int(k): j for j, k in enumerate(stream['gps_idx'])} if 'gps_idx' in stream else {}
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])} if 'mbes_idx' in stream else {}
@@ -334,7 +376,15 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
             scan = msgs.LaserScan(stream['mbes_ranges'][mbes_at[k]], float(ang[0]),
                                   float(ang[1] - ang[0]) if ang.size > 1 else 0.0,
                                   float(stream['mbes_range_max']) if 'mbes_range_max' in stream else 100.0)
+            if innovation and pf.old_time and pf.has_map:
+                inn = pf.particles.ping_innovation(np.asarray(scan.ranges, dtype=np.float32), ang.astype(np.float32),
+                                                   pf.mbes_std, float(scan.range_max), pf.mbes_sensor_offset)
+                inn_nis.append(np.where(inn.valid, inn.nis, np.nan))
+                inn_nu.append(np.where(inn.valid, inn.nu, np.nan))
+            calls = pf.gate_calls
             pf.mbes_cb(scan)
+            if pf.gate_calls > calls and pf.last_innovation.inconsistent:
+                n_inconsistent += 1
         while next_fix < len(fixes) and fixes[next_fix][0] <= stream['stamp'][k]:
             f = msgs.Odometry()
             f.header = msgs.Header(pf.map_frame, msgs.Time(fixes[next_fix][1]))
@@ -380,6 +430,12 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
         out_cred = np.array(cred_r)
         summary.update(credible_summary(pf.credible_prob, out_cred, pf_xyz,
                                         np.asarray(stream['truth_xyz'])[pub_idx] if 'truth_xyz' in stream else None))
+    if innovation:
+        summary.update(innovation_summary(inn_nis, inn_nu))
+    if pf.mbes_gate_nis > 0.0:
+        # per-beam outlier gate (include/mcl_innovation.h): pings gated, beams marked invalid, pings that disagreed as a whole
+        summary['mbes_gate_nis'], summary['gate_pings'] = float(pf.mbes_gate_nis), int(pf.gate_calls)
+        summary['gate_n_gated'], summary['gate_inconsistent'] = int(pf.gated_beams), int(n_inconsistent)
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -600,7 +656,20 @@ def main(argv=None):
     ap.add_argument('--recover', action='store_true',
                     help='global localisation with kidnap recovery (replay_recover): uniform start over the map, '
                          'augmented-MCL injection; needs --map-grid and MBES pings in the stream')
-    ap.add_argument('--sigma', type=float, default=1.0, help='--recover: MBES range sigma')
+    ap.add_argument('--sigma', type=float, default=None,
+                    help='MBES range sigma: of --recover (default 1.0), or the node\'s mbes_std of the plain replay (default: the '
+                         'node\'s own, 0.2)')
+    ap.add_argument('--innovation', action='store_true',
+                    help='hold every ping against the cloud before its update (include/mcl_innovation.h) and add the run\'s mean '
+                         'normalised innovation squared per beam and the mean innovation to the summary: about 1 and about 0 '
+                         'when --sigma is right')
+    ap.add_argument('--gate-nis', type=float, default=0.0, metavar='G',
+                    help='the node\'s mbes_gate_nis: beams whose normalised innovation squared exceeds G while almost no particle '
+                         'explains them are marked invalid before the update (10.83: chi^2_1 at 0.999); 0: off')
+    ap.add_argument('--mbes-every', type=int, default=0, metavar='K',
+                    help='synthetic streams: a multibeam ping every K samples over a synthetic map the stream carries')
+    ap.add_argument('--outliers', type=float, nargs=2, default=None, metavar=('FRACTION', 'SHORTEN_M'),
+                    help='synthetic streams with --mbes-every: that share of the beams comes back SHORTEN_M metres short')
     ap.add_argument('--credible', type=float, default=0.0, metavar='P',
                     help='after every published pose also ask the cloud for the radius that holds the share P of the posterior '
                          'about it (the node\'s credible_prob, include/mcl_quantile.h); with a truth the summary gains '
@@ -658,6 +727,16 @@ def main(argv=None):
         ap.error('--no-regularise-shrink needs --regularise SCALE')
     if not 0.0 <= a.credible <= 1.0:
         ap.error('--credible: P must lie in [0, 1]')
+    if not (a.gate_nis >= 0.0 and np.isfinite(a.gate_nis)):
+        ap.error('--gate-nis: G must be finite and >= 0')
+    if (a.gate_nis > 0 or a.innovation) and (a.bag or a.recover):
+        ap.error('--gate-nis / --innovation: only with the plain stream replay')
+    if a.sigma is not None and not (a.sigma > 0.0 and np.isfinite(a.sigma)):
+        ap.error('--sigma must be finite and > 0')
+    if (a.mbes_every != 0 or a.outliers is not None) and not synthetic:
+        ap.error('--mbes-every / --outliers: only with a synthetic stream (synth[:N])')
+    if a.mbes_every < 0 or (a.outliers is not None and not (a.mbes_every > 0 and 0.0 <= a.outliers[0] <= 1.0 and a.outliers[1] >= 0.0)):
+        ap.error('--mbes-every K > 0; --outliers FRACTION in [0, 1] and SHORTEN_M >= 0, with --mbes-every')
     if a.credible > 0 and a.bag:
         ap.error('--credible: not with --bag')
     if not 0.0 <= a.temper_ess <= 1.0:
@@ -681,7 +760,8 @@ def main(argv=None):
         print(json.dumps(res['summary']))
         return
     if synthetic:
-        stream = synthetic_stream(int(a.stream[6:]) if a.stream[5:6] == ':' else 3000, a.current, a.yaw_rate_bias, seed=a.seed)
+        stream = synthetic_stream(int(a.stream[6:]) if a.stream[5:6] == ':' else 3000, a.current, a.yaw_rate_bias, seed=a.seed,
+                                  mbes_every=a.mbes_every, outliers=a.outliers)
     else:
         stream = dict(np.load(a.stream, allow_pickle=False))
     m2o = None
@@ -693,7 +773,7 @@ def main(argv=None):
                                            gps_map=stream.get('gps_map'), pressure_tf=ptf)
     grid = dict(np.load(a.map_grid)) if a.map_grid else None
     if a.recover:
-        res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=a.sigma, m2o=m2o,
+        res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=1.0 if a.sigma is None else a.sigma, m2o=m2o,
                              estimate=a.estimate, smooth_lag=a.smooth, credible=a.credible)
         if a.out:
             np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz'], res['fractions']]), delimiter=',',
@@ -714,13 +794,17 @@ def main(argv=None):
             params.update(drift_walk_std=str([float(x) for x in a.drift_walk_std]))
     if a.credible > 0:
         params.update(credible_prob=a.credible)
+    if a.gate_nis > 0:
+        params.update(mbes_gate_nis=a.gate_nis)
+    if a.sigma is not None:
+        params.update(mbes_std=a.sigma)
     if a.regularise > 0:
         params.update(regularise_scale=a.regularise, regularise_shrink=not a.no_regularise_shrink)
     if a.fix_period > 0:
         params.update(fix_topic='/sam/external/uw_gps_odom', fix_std=a.fix_std, fix_history_depth=a.fix_history_depth,
                       fix_max_age=max(10.0, 2.0 * a.fix_latency))
     res = replay(stream, params, m2o=m2o, grid=grid, smooth_lag=a.smooth, fix_period=a.fix_period,
-                 fix_latency=a.fix_latency, fix_seed=a.seed)
+                 fix_latency=a.fix_latency, fix_seed=a.seed, innovation=a.innovation)
     if a.out:
         np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz']]), delimiter=',', header='step,x,y,z')
         save_smooth(a.out, res)

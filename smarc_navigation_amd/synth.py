@@ -259,6 +259,26 @@ def beam_angles(n_beams, half_swath=math.pi / 3):
     return np.linspace(-half_swath, half_swath, n_beams).astype(np.float32)
 
 
+def noisy_pings(clean, sigma=0.0, r_max=None, outliers=None, seed=4):
+    """Measured ranges from the clean ranges of m pings (m x B): Gaussian noise of `sigma` metres, and with outliers =
+    (fraction, shorten_m) that share of the beams -- fish in the water column, a bottom-detection failure -- comes back
+    shorten_m metres short (never below 0.1 m).  A beam at or beyond r_max has no return (0).  The noise and the outliers
+    are drawn from generators of their own (seed, seed + 1): switching the outliers on changes no other number.
+    Returns (ranges float32, outlier mask)."""
+    clean = np.asarray(clean, dtype=np.float64)
+    out = clean + (float(sigma) * np.random.RandomState(int(seed)).randn(*clean.shape) if sigma > 0 else 0.0)
+    hit = np.zeros(clean.shape, bool)
+    if outliers is not None:
+        fraction, shorten = float(outliers[0]), float(outliers[1])
+        hit = np.random.RandomState(int(seed) + 1).random_sample(clean.shape) < fraction
+        out = np.where(hit, np.maximum(out - shorten, 0.1), out)
+    if r_max is not None:
+        lost = clean >= float(r_max)
+        out = np.where(lost, 0.0, out)
+        hit &= ~lost
+    return out.astype(np.float32), hit
+
+
 # ---------------------------------------------------------------- raw sensor events for the DR integrator
 EV_IMU, EV_HEADING, EV_GPS, EV_DVL, EV_DEPTH, EV_THRUST, EV_THRUST_CMD, EV_TICK = range(8)
 
