@@ -1,5 +1,6 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
-mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h and mcl_innovation.h).
+mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h, mcl_innovation.h
+and mcl_information.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -126,6 +127,19 @@ class InnovationVerdict(C.Structure):
 INNOVATION_BEAM_FIELDS = [('n', '<i8'), ('n_miss', '<i8'), ('n_within', '<i8'), ('s1', '<i8'), ('s2', '<u8')]
 INNOVATION_DERIVED_FIELDS = [('nu', '<f8'), ('var', '<f8'), ('nis', '<f8'), ('support', '<f8'), ('valid', '<i4'),
                              ('gated', '<i4')]
+
+
+class InformationSteps(C.Structure):
+    """mcl_information_steps (include/mcl_information.h)"""
+    _fields_ = [('delta_xy', C.c_double), ('delta_yaw', C.c_double), ('jump_max', C.c_double)]
+
+
+# mcl_information_sums (72 bytes) and mcl_information_result (104 bytes) travel as numpy record arrays
+INFORMATION_SUMS_FIELDS = [('n', '<i8'), ('n_miss', '<i8'), ('n_jump', '<i8'), ('sxx', '<u8'), ('syy', '<u8'), ('sww', '<u8'),
+                           ('sxy', '<i8'), ('sxw', '<i8'), ('syw', '<i8')]
+INFORMATION_RESULT_FIELDS = [('J', '<f8', (6,)), ('lambda_max', '<f8'), ('lambda_min', '<f8'), ('weak_axis', '<f8'),
+                             ('crlb_strong', '<f8'), ('crlb_weak', '<f8'), ('hit_share', '<f8'), ('rank_pos', '<i4'),
+                             ('reserved', '<i4')]
 
 
 # every symbol include/mcl.h, mcl_dr.h and mcl_map.h declare: name -> (restype, argtypes)
@@ -304,6 +318,17 @@ INNOVATION_SYMBOLS = {
                                             C.POINTER(C.c_int64)]),
 }
 
+# include/mcl_information.h: ping information, per cloud and per pose
+INFORMATION_SYMBOLS = {
+    'mcl_information_merge': (C.c_int, [_vp, _i32, _i32, _vp]),
+    'mcl_information_matrix': (C.c_int, [_vp, _i32, _i32, _d, _d, _d, _vp]),
+    'mcl_ping_information': (C.c_int, [_vp, _vp, _i32, _d, _vp, _i32, C.POINTER(InformationSteps), _vp, _vp,
+                                       C.POINTER(C.c_int64)]),
+    'mcl_group_ping_information': (C.c_int, [C.POINTER(_vp), _i32, _vp, _i32, _d, _vp, _i32, C.POINTER(InformationSteps), _vp,
+                                             C.POINTER(C.c_int64)]),
+    'mcl_pose_information': (C.c_int, [_vp, _vp, _i64, _vp, _i32, _d, _vp, C.POINTER(InformationSteps), _vp]),
+}
+
 _lib = None
 
 
@@ -320,7 +345,7 @@ def load():
                               list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items()) +
                               list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
                               list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items()) +
-                              list(INNOVATION_SYMBOLS.items())):
+                              list(INNOVATION_SYMBOLS.items()) + list(INFORMATION_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,7 @@ Divergences from the reference, all documented in INTEGRATION.md:
 """
 import bisect
 import collections
+import logging
 import math
 import threading
 
@@ -117,6 +118,12 @@ DEFAULT_PARAMS = {
     # last ping is kept in `last_innovation`.  0 = off: the call is never made and the node computes what it computed
     # without the parameter.
     'mbes_gate_nis': 0.0,
+    # Ping information (include/mcl_information.h): K > 0: every K-th MBES ping, before anything else is done with it, the
+    # node asks how much a ping of that geometry can tell the cloud as it is -- the Cramer-Rao bounds of one ping along
+    # the direction the terrain fixes best and worst, and that worst direction -- keeps the answer in `last_information`
+    # and logs it (logger 'auv_pf', at most once per `information_log_period` seconds of filter time).  Nothing of the
+    # filter changes.  0 = off: the call is never made and the node computes what it computed without the parameter.
+    'mbes_information_every': 0,
 }
 
 
@@ -392,6 +399,16 @@ class auv_pf(object):
         self.last_innovation = None     # the GateVerdict of the last ping
         self.gate_calls = 0
         self.gated_beams = 0            # beams marked invalid so far
+        # ping information in front of every K-th MBES ping
+        self.mbes_information_every = int(p['mbes_information_every'])
+        if self.mbes_information_every < 0 or self.mbes_information_every != p['mbes_information_every']:
+            raise ValueError('mbes_information_every must be an integer >= 0, not %r' % (p['mbes_information_every'],))
+        self.information_log_period = 5.0
+        self.last_information = None    # the PingInformation of the last ping that was asked
+        self.information_calls = 0
+        self.information_log = []       # (stamp, crlb_strong, crlb_weak, weak_axis, rank_pos, hit_share) of every call
+        self._mbes_pings = 0
+        self._information_logged = None
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
@@ -559,6 +576,25 @@ class auv_pf(object):
         self.particles.update_landmarks(det, self.landmark_std, k=self.landmark_k, gate=self.landmark_gate,
                                         accumulate=True)
 
+    def _information(self, angles, r_max):
+        """with mbes_information_every = K > 0: what pings 0, K, 2 K, ... can tell the cloud as it stands before their update"""
+        if not self.mbes_information_every > 0:
+            return
+        k = self._mbes_pings
+        self._mbes_pings += 1
+        if k % self.mbes_information_every:
+            return
+        inf = self.particles.ping_information(angles, self.mbes_std, r_max, self.mbes_sensor_offset)
+        self.last_information = inf
+        self.information_calls += 1
+        self.information_log.append((self.time, inf.crlb_strong, inf.crlb_weak, inf.weak_axis, inf.rank_pos, inf.hit_share))
+        if self._information_logged is None or self.time - self._information_logged >= self.information_log_period:
+            self._information_logged = self.time
+            logging.getLogger('auv_pf').info(
+                'ping information: one ping fixes %.3g m along its strong axis, %.3g m along its weak axis (%.1f deg), '
+                'rank %d, %.0f %% of the rays usable', inf.crlb_strong, inf.crlb_weak, math.degrees(inf.weak_axis),
+                inf.rank_pos, 100.0 * inf.hit_share)
+
     def _gate(self, ranges, angles, r_max):
         """the ping's ranges as the update takes them: with mbes_gate_nis > 0 the beams the cloud cannot explain set to 0"""
         if not self.mbes_gate_nis > 0.0:
@@ -589,6 +625,7 @@ class auv_pf(object):
             if not (self.old_time and self.has_map):
                 return
             ang32 = ang[order].astype(np.float32)
+            self._information(ang32, self.mbes_range_max)
             self.particles.update_mbes(self._gate(rng[order].astype(np.float32), ang32, self.mbes_range_max), ang32,
                                        self.mbes_std, self.mbes_range_max, self.mbes_sensor_offset)
             self._accumulate_pending_detections(self._stamp_of(cloud))
@@ -601,6 +638,7 @@ class auv_pf(object):
             n = len(scan.ranges)
             angles = scan.angle_min + scan.angle_increment * np.arange(n)
             ang32 = angles.astype(np.float32)
+            self._information(ang32, float(scan.range_max))
             self.particles.update_mbes(self._gate(np.asarray(scan.ranges, dtype=np.float32), ang32, float(scan.range_max)),
                                        ang32, self.mbes_std, float(scan.range_max), self.mbes_sensor_offset)
             self._accumulate_pending_detections(self._stamp_of(scan))

@@ -16,6 +16,7 @@
 #include "mcl_host_regularise.h"
 #include "mcl_host_quantile.h"
 #include "mcl_host_innovation.h"
+#include "mcl_host_information.h"
 #include "mcl_host_recovery.h"
 #include "mcl_host_modes.h"
 
@@ -121,6 +122,7 @@ int mcl_create(const mcl_config* cfg, mcl_handle** out) {
     }
     if (const char* sv = getenv("MCL_VISIT_MIN_N")) h->visit_min_n = std::max(1ll, atoll(sv));
     if (const char* sv = getenv("MCL_INNOVATION_GROUP")) h->env_innov_group = std::max(0, atoi(sv));
+    if (const char* sv = getenv("MCL_INFORMATION_GROUP")) h->env_info_group = std::max(0, atoi(sv));
     if (const char* sv = getenv("MCL_SWEEP_NSUB")) h->env_nsub = (sv[0] == '2' || sv[0] == '4') ? sv[0] - '0' : 1;
     h->env_force_comm = on("MCL_FORCE_COMM");
     if (const char* ex = getenv("MCL_EXCHANGE")) h->exch_allgather = strcmp(ex, "allgather") == 0;
@@ -1362,6 +1364,44 @@ int mcl_group_ping_innovation(mcl_handle** shards, int32_t ns, const float* rang
   if (!beams_out || !n_sampled) return fail(shards[0], MCL_ERR_INVALID, "group_ping_innovation: null argument");
   const InnovPing p = {ranges, beam_angles, B, sigma, support_k, r_max, sensor_offset, max_samples};
   return group_innovation_run(shards, ns, p, beams_out, n_sampled);
+}
+
+// ---- ping information (include/mcl_information.h; host: mcl_host_information.h, kernel: csrc/mcl_information.h)
+int mcl_information_merge(const mcl_information_sums* parts, int32_t n_parts, int32_t B, mcl_information_sums* out) {
+  return information_merge_impl(parts, n_parts, B, out);
+}
+
+int mcl_information_matrix(const mcl_information_sums* recs, int32_t count, int32_t per_pose, double sigma, double delta_xy,
+                           double delta_yaw, mcl_information_result* out) {
+  return information_matrix_impl(recs, count, per_pose, sigma, delta_xy, delta_yaw, out);
+}
+
+int mcl_ping_information(mcl_handle* h, const float* beam_angles, int32_t B, double r_max, const double sensor_offset[6],
+                         int32_t max_samples, const mcl_information_steps* steps, mcl_information_sums* beams_out,
+                         float* ranges_out, int64_t* n_sampled) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!beams_out || !n_sampled) return fail(h, MCL_ERR_INVALID, "ping_information: null argument");
+  const InfoPing p = {beam_angles, B, r_max, sensor_offset, steps};
+  return information_run(h, p, max_samples, beams_out, ranges_out, n_sampled);
+}
+
+int mcl_group_ping_information(mcl_handle** shards, int32_t ns, const float* beam_angles, int32_t B, double r_max,
+                               const double sensor_offset[6], int32_t max_samples, const mcl_information_steps* steps,
+                               mcl_information_sums* beams_out, int64_t* n_sampled) {
+  if (!shards || ns < 1) return MCL_ERR_INVALID;
+  for (int s = 0; s < ns; ++s)
+    if (!shards[s]) return MCL_ERR_INVALID;
+  if (!beams_out || !n_sampled) return fail(shards[0], MCL_ERR_INVALID, "group_ping_information: null argument");
+  const InfoPing p = {beam_angles, B, r_max, sensor_offset, steps};
+  return group_information_run(shards, ns, p, max_samples, beams_out, n_sampled);
+}
+
+int mcl_pose_information(mcl_handle* h, const double* poses, int64_t M, const float* beam_angles, int32_t B, double r_max,
+                         const double sensor_offset[6], const mcl_information_steps* steps, mcl_information_sums* poses_out) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!poses_out) return fail(h, MCL_ERR_INVALID, "pose_information: null argument");
+  const InfoPing p = {beam_angles, B, r_max, sensor_offset, steps};
+  return pose_information_run(h, p, poses, M, poses_out);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

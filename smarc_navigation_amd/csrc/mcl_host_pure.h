@@ -7,7 +7,8 @@
 // and round plan of mcl_temper (also run by its pick kernel: MCL_HD), and the rules, bandwidth and factor of
 // mcl_regularise (the factor also run by its kernel), and the keys, threshold, predicate,
 // start and bin choice of mcl_cloud_quantiles (include/mcl_quantile.h; the kernels run the same functions), and the
-// quantised residual, sample, merge and gate of mcl_ping_innovation (include/mcl_innovation.h).  No HIP header: the
+// quantised residual, sample, merge and gate of mcl_ping_innovation (include/mcl_innovation.h), and the quantised
+// difference, steps, merge and matrix of mcl_ping_information (include/mcl_information.h).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -15,6 +16,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <limits>
 #include <vector>
 
 #include "../../include/mcl.h"
@@ -27,6 +30,7 @@
 #include "../../include/mcl_regularise.h"
 #include "../../include/mcl_quantile.h"
 #include "../../include/mcl_innovation.h"
+#include "../../include/mcl_information.h"
 
 namespace {
 
@@ -769,6 +773,148 @@ int innovation_gate_impl(const mcl_innovation_beam* beams, int32_t B, double sig
       per_beam[b] = d;
     }
   *verdict = v;
+  return MCL_OK;
+}
+
+// ---- ping information (include/mcl_information.h): the quantised central difference (the kernel, csrc/mcl_information.h,
+// runs info_difference itself), the legality of the steps and of a record, the merge and the derived quantities.
+constexpr long long INFO_MAX_N = MCL_INFORMATION_MAX_SAMPLES;
+// d = rint((e+ - e-) 2^12): both ranges lie in [0, r_max], r_max <= 4096 m, so |d| <= 2^24 without a clamp
+MCL_HD inline long long info_difference(float e_plus, float e_minus) {
+  return (long long)rint(((double)e_plus - (double)e_minus) * 4096.0);
+}
+// |d| above this is a jump (the callers have refused what info_steps_why refuses: the product is below 2^23 + 1)
+inline long long info_jump_q(double jump_max) { return (long long)std::floor(jump_max * 4096.0); }
+// nullptr when the steps are legal for this r_max, else the sentence that says what is wrong
+const char* info_steps_why(const mcl_information_steps* s, double r_max) {
+  if (!s) return "null steps";
+  if (!(r_max > 0.0) || !(r_max <= MCL_INFORMATION_MAX_RANGE)) return "r_max outside (0, 4096] m (the quantised difference's range)";
+  if (!(s->delta_xy > 0.0) || !std::isfinite(s->delta_xy)) return "delta_xy must be positive and finite";
+  if (!(s->delta_yaw > 0.0) || !std::isfinite(s->delta_yaw)) return "delta_yaw must be positive and finite";
+  if (!(s->jump_max > 0.0) || !(s->jump_max <= r_max)) return "jump_max outside (0, r_max]";
+  if (!(s->jump_max <= MCL_INFORMATION_MAX_JUMP)) return "jump_max above 2048 m (the products' range)";
+  return nullptr;
+}
+// can the record be a sum of the definition?
+inline bool info_legal(const mcl_information_sums& r) {
+  typedef unsigned __int128 u128;
+  if (r.n < 0 || r.n > INFO_MAX_N || r.n_miss < 0 || r.n_jump < 0 || r.n_miss > r.n || r.n_jump > r.n - r.n_miss) return false;
+  const u128 cap = (u128)(r.n - r.n_miss - r.n_jump) << 46;
+  if ((u128)r.sxx > cap || (u128)r.syy > cap || (u128)r.sww > cap) return false;
+  if (r.sxy == INT64_MIN || r.sxw == INT64_MIN || r.syw == INT64_MIN) return false;   // (have no absolute value)
+  const u128 axy = (u128)(r.sxy < 0 ? -r.sxy : r.sxy), axw = (u128)(r.sxw < 0 ? -r.sxw : r.sxw), ayw = (u128)(r.syw < 0 ? -r.syw : r.syw);
+  return axy * axy <= (u128)r.sxx * (u128)r.syy && axw * axw <= (u128)r.sxx * (u128)r.sww &&
+         ayw * ayw <= (u128)r.syy * (u128)r.sww;   // Cauchy-Schwarz
+}
+int information_merge_impl(const mcl_information_sums* parts, int32_t n_parts, int32_t B, mcl_information_sums* out) {
+  if (!parts || !out || n_parts < 1 || B < 1) return MCL_ERR_INVALID;
+  for (int b = 0; b < B; ++b) {
+    mcl_information_sums acc = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int p = 0; p < n_parts; ++p) {
+      const mcl_information_sums& r = parts[(size_t)p * B + b];
+      if (!info_legal(r) || acc.n + r.n > INFO_MAX_N) return MCL_ERR_INVALID;   // (n within 2^15 keeps every other sum in range)
+      acc.n += r.n;
+      acc.n_miss += r.n_miss;
+      acc.n_jump += r.n_jump;
+      acc.sxx += r.sxx;
+      acc.syy += r.syy;
+      acc.sww += r.sww;
+      acc.sxy += r.sxy;
+      acc.sxw += r.sxw;
+      acc.syw += r.syw;
+    }
+    out[b] = acc;
+  }
+  return MCL_OK;
+}
+// the six sums of a record in the packed order xx, xy, xw, yy, yw, ww, each as the nearest double
+inline void info_sums6(const mcl_information_sums& r, double s[6]) {
+  s[0] = (double)r.sxx;
+  s[1] = (double)r.sxy;
+  s[2] = (double)r.sxw;
+  s[3] = (double)r.syy;
+  s[4] = (double)r.syw;
+  s[5] = (double)r.sww;
+}
+// everything behind J: the Schur complement, its eigenvalues in closed form, the weak axis, the bounds, the rank
+inline void info_eigen(mcl_information_result& o) {
+  const double inf = std::numeric_limits<double>::infinity();
+  const double* J = o.J;
+  double a = J[0], b = J[1], c = J[3];
+  if (J[5] != 0.0) {
+    a = J[0] - (J[2] * J[2]) / J[5];
+    b = J[1] - (J[2] * J[4]) / J[5];
+    c = J[3] - (J[4] * J[4]) / J[5];
+    // what is left of a position information that yaw explains altogether is rounding, not information
+    if (a + c <= (J[0] + J[3]) * (1.0 / 1099511627776.0)) a = b = c = 0.0;
+  }
+  const double h = 0.5 * (a + c), g = 0.5 * (a - c);
+  const double lmax = h + std::sqrt(g * g + b * b);
+  if (!(lmax > 0.0)) {
+    o.lambda_max = o.lambda_min = 0.0;
+    o.weak_axis = 0.0;
+    o.crlb_strong = o.crlb_weak = inf;
+    o.rank_pos = 0;
+    return;
+  }
+  const double det = a * c - b * b;
+  const double lmin = det > 0.0 ? det / lmax : 0.0;
+  const double pi = 3.14159265358979323846;
+  double w = 0.5 * std::atan2(2.0 * b, a - c) + pi / 2;
+  if (w >= pi) w -= pi;
+  if (w < 0.0) w = 0.0;
+  o.lambda_max = lmax;
+  o.lambda_min = lmin;
+  o.weak_axis = w;
+  o.crlb_strong = 1.0 / std::sqrt(lmax);
+  const bool weak = lmin <= lmax * (1.0 / 1099511627776.0);
+  o.crlb_weak = weak ? inf : 1.0 / std::sqrt(lmin);
+  o.rank_pos = weak ? 1 : 2;
+}
+int information_matrix_impl(const mcl_information_sums* recs, int32_t count, int32_t per_pose, double sigma, double delta_xy,
+                            double delta_yaw, mcl_information_result* out) {
+  if (!recs || !out || count < 1) return MCL_ERR_INVALID;
+  if (!(sigma > 0.0) || !std::isfinite(sigma) || !(delta_xy > 0.0) || !std::isfinite(delta_xy) || !(delta_yaw > 0.0) ||
+      !std::isfinite(delta_yaw))
+    return MCL_ERR_INVALID;
+  for (int k = 0; k < count; ++k)
+    if (!info_legal(recs[k])) return MCL_ERR_INVALID;
+  const double dl[3] = {delta_xy, delta_xy, delta_yaw};
+  const int ja[6] = {0, 0, 0, 1, 1, 2}, ka[6] = {0, 1, 2, 1, 2, 2};
+  double q[6];
+  for (int e = 0; e < 6; ++e) q[e] = (4.0 * dl[ja[e]]) * dl[ka[e]];
+  const double s2 = sigma * sigma;
+  if (per_pose) {
+    for (int k = 0; k < count; ++k) {
+      mcl_information_result o;
+      memset(&o, 0, sizeof o);
+      double s[6];
+      info_sums6(recs[k], s);
+      for (int e = 0; e < 6; ++e) o.J[e] = s[e] / ((16777216.0 * q[e]) * s2);
+      const long long m = recs[k].n - recs[k].n_miss - recs[k].n_jump;
+      o.hit_share = recs[k].n > 0 ? (double)m / (double)recs[k].n : 0.0;
+      info_eigen(o);
+      out[k] = o;
+    }
+    return MCL_OK;
+  }
+  mcl_information_result o;
+  memset(&o, 0, sizeof o);
+  long long sum_m = 0, sum_n = 0;
+  for (int k = 0; k < count; ++k) {
+    const long long m = recs[k].n - recs[k].n_miss - recs[k].n_jump;
+    sum_n += recs[k].n;
+    if (m <= 0) continue;
+    sum_m += m;
+    double s[6];
+    info_sums6(recs[k], s);
+    const double mm = (double)m * 16777216.0;
+    for (int e = 0; e < 6; ++e) o.J[e] += s[e] / (mm * q[e]);
+  }
+  for (int e = 0; e < 6; ++e) o.J[e] = o.J[e] / s2;
+  o.hit_share = sum_n > 0 ? (double)sum_m / (double)sum_n : 0.0;
+  info_eigen(o);
+  *out = o;
   return MCL_OK;
 }
 

@@ -230,6 +230,68 @@ class GateVerdict(object):
         return self.nis_sum / self.n_valid if self.n_valid else math.nan
 
 
+INFORMATION_SUMS = np.dtype(_lib.INFORMATION_SUMS_FIELDS)
+INFORMATION_RESULT = np.dtype(_lib.INFORMATION_RESULT_FIELDS)
+INFORMATION_DEFAULT_SAMPLES = 4096
+INFORMATION_MAX_JUMP = 2048.0
+
+
+def make_information_steps(r_max, delta_xy=0.5, delta_yaw=0.01, jump_max=None):
+    """mcl_information_steps; jump_max=None: min(r_max, 2048).  The defaults are policy, not tolerances."""
+    s = _lib.InformationSteps()
+    s.delta_xy, s.delta_yaw = float(delta_xy), float(delta_yaw)
+    s.jump_max = min(float(r_max), INFORMATION_MAX_JUMP) if jump_max is None else float(jump_max)
+    return s
+
+
+def _matrix3(J):
+    """the packed xx, xy, xw, yy, yw, ww as the symmetric 3 x 3 (the last axis of J holds the six)"""
+    J = np.asarray(J, np.float64)
+    return np.stack([J[..., [0, 1, 2]], J[..., [1, 3, 4]], J[..., [2, 4, 5]]], axis=-2)
+
+
+class PingInformation(object):
+    """what Engine.ping_information returns: the integer records of include/mcl_information.h per beam (`beams`, a record
+    array with the fields n, n_miss, n_jump, sxx, syy, sww, sxy, sxw, syw), the sampled particles (n_sampled), and the
+    quantities mcl_information_matrix derives from them: `matrix` (3 x 3 over x, y, yaw: the sample mean of the ping's
+    Fisher information), lambda_max / lambda_min of the position information with yaw marginalised, crlb_strong and
+    crlb_weak (metres; inf where the ping fixes nothing), weak_axis (radians in [0, pi), state coordinates), rank_pos and
+    hit_share.  With dump=True `ranges` holds the six ranges of every pair, shaped (n_sampled, 6, B)."""
+
+    def __init__(self, beams, n_sampled, sigma, delta_xy, delta_yaw, ranges=None):
+        self.beams = beams
+        self.n_sampled = int(n_sampled)
+        self.sigma, self.delta_xy, self.delta_yaw = float(sigma), float(delta_xy), float(delta_yaw)
+        self.ranges = ranges
+        r = information_matrix(beams, sigma, delta_xy, delta_yaw)
+        self.result = r
+        self.J = r['J'].copy()
+        self.matrix = _matrix3(self.J)
+        self.lambda_max, self.lambda_min = float(r['lambda_max']), float(r['lambda_min'])
+        self.crlb_strong, self.crlb_weak = float(r['crlb_strong']), float(r['crlb_weak'])
+        self.weak_axis, self.rank_pos, self.hit_share = float(r['weak_axis']), int(r['rank_pos']), float(r['hit_share'])
+
+    def as_dict(self):
+        return dict(n_sampled=self.n_sampled, crlb_strong=self.crlb_strong, crlb_weak=self.crlb_weak,
+                    weak_axis=self.weak_axis, rank_pos=self.rank_pos, hit_share=self.hit_share)
+
+
+class PoseInformation(object):
+    """what Engine.pose_information returns: one integer record per pose (`poses`, fields as PingInformation.beams) and
+    arrays of the derived quantities, one entry per pose: J (M x 6, packed xx, xy, xw, yy, yw, ww), matrix (M x 3 x 3),
+    lambda_max, lambda_min, crlb_strong, crlb_weak, weak_axis, rank_pos, hit_share"""
+
+    def __init__(self, records, sigma, delta_xy, delta_yaw):
+        self.poses = records
+        self.sigma, self.delta_xy, self.delta_yaw = float(sigma), float(delta_xy), float(delta_yaw)
+        r = information_matrix(records, sigma, delta_xy, delta_yaw, per_pose=True)
+        self.result = r
+        self.J = r['J'].copy()
+        self.matrix = _matrix3(self.J)
+        for f in ('lambda_max', 'lambda_min', 'crlb_strong', 'crlb_weak', 'weak_axis', 'rank_pos', 'hit_share'):
+            setattr(self, f, r[f].copy())
+
+
 def make_gate_config(nis_gate=10.83, min_support=0.01, max_gated_fraction=0.25):
     c = _lib.InnovationGateConfig()
     c.nis_gate, c.min_support, c.max_gated_fraction = float(nis_gate), float(min_support), float(max_gated_fraction)
@@ -733,6 +795,39 @@ class Engine(object):
         masked[verdict.mask] = 0.0
         return masked, verdict
 
+    # ---- ping information: what the terrain can fix (include/mcl_information.h)
+    def ping_information(self, beam_angles, sigma, r_max, sensor_offset=None, max_samples=INFORMATION_DEFAULT_SAMPLES,
+                         delta_xy=0.5, delta_yaw=0.01, jump_max=None, dump=False):
+        """how much a ping of this geometry can tell the cloud as it is: per beam the integer sums of the quantised central
+        differences of the expected range in x, y and yaw over a strided sample of at most max_samples particles
+        (mcl_ping_information) -- a PingInformation of THIS shard's sampled particles.  Nothing of the filter changes."""
+        a, so = _f32(beam_angles).reshape(-1), _f64(sensor_offset)
+        steps = make_information_steps(r_max, delta_xy, delta_yaw, jump_max)
+        beams = np.zeros(max(a.size, 1), INFORMATION_SUMS)
+        rng = None
+        if dump:
+            stride, _ = innovation_sample(self.n_global, max_samples)
+            rng = np.full(((self.n + stride - 1) // stride, 6, max(a.size, 1)), np.nan, np.float32)
+        ns = C.c_int64(0)
+        self._ck(self.lib.mcl_ping_information(self.h, _ptr(a), a.size, float(r_max), _ptr(so), int(max_samples),
+                                               C.byref(steps), _ptr(beams), _ptr(rng), C.byref(ns)))
+        if rng is not None:
+            rng = rng.reshape(-1)[:ns.value * 6 * a.size].reshape(ns.value, 6, a.size)
+        return PingInformation(beams[:a.size], ns.value, sigma, delta_xy, delta_yaw, rng)
+
+    def pose_information(self, poses, beam_angles, sigma, r_max, sensor_offset=None, delta_xy=0.5, delta_yaw=0.01,
+                         jump_max=None):
+        """how much a ping of this geometry can tell at each of M given poses (6 x M: x, y, z, roll, pitch, yaw in the
+        coordinates the particle state is stored in; mcl_pose_information) -- a PoseInformation.  Needs a map, no
+        particles; the cloud is neither read nor written."""
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(6, -1))
+        a, so = _f32(beam_angles).reshape(-1), _f64(sensor_offset)
+        steps = make_information_steps(r_max, delta_xy, delta_yaw, jump_max)
+        out = np.zeros(max(p.shape[1], 1), INFORMATION_SUMS)
+        self._ck(self.lib.mcl_pose_information(self.h, _ptr(p), p.shape[1], _ptr(a), a.size, float(r_max), _ptr(so),
+                                               C.byref(steps), _ptr(out)))
+        return PoseInformation(out[:p.shape[1]], sigma, delta_xy, delta_yaw)
+
     def set_landmarks(self, xyz):
         a = _f64(xyz)
         self._ck(self.lib.mcl_set_landmarks(self.h, _ptr(a), a.shape[0]))
@@ -1133,6 +1228,95 @@ def group_ping_innovation(engines, ranges, beam_angles, sigma, r_max, sensor_off
     _lib.check(lib.mcl_group_ping_innovation(hs, ns, _ptr(r), _ptr(a), a.size, float(sigma), float(support_k), float(r_max),
                                              _ptr(so), int(max_samples), _ptr(beams), C.byref(n)), engines[0].h)
     return PingInnovation(beams[:a.size], n.value, sigma)
+
+
+def _information_records(recs):
+    if isinstance(recs, PingInformation):
+        recs = recs.beams
+    elif isinstance(recs, PoseInformation):
+        recs = recs.poses
+    return np.ascontiguousarray(recs, dtype=INFORMATION_SUMS).reshape(-1)
+
+
+def information_matrix(records, sigma, delta_xy=0.5, delta_yaw=0.01, per_pose=False):
+    """the derived quantities of include/mcl_information.h (mcl_information_matrix: host arithmetic) as records of
+    INFORMATION_RESULT: one for the beams of a cloud sample, or with per_pose=True an array, one per record"""
+    rec = _information_records(records)
+    out = np.zeros(max(rec.size, 1) if per_pose else 1, INFORMATION_RESULT)
+    _lib.check(_lib.load().mcl_information_matrix(_ptr(rec), rec.size, 1 if per_pose else 0, float(sigma), float(delta_xy),
+                                                  float(delta_yaw), _ptr(out)))
+    return out[:rec.size] if per_pose else out[0]
+
+
+def merge_information(parts):
+    """the records of the union of several shards' samples (mcl_information_merge: host arithmetic): parts are
+    PingInformation objects or record arrays of equal length; returns a record array"""
+    recs = [_information_records(p) for p in parts]
+    B = recs[0].size if recs else 0
+    if any(r.size != B for r in recs):
+        raise ValueError('merge_information: the parts differ in their beam count')
+    stack = np.ascontiguousarray(np.stack(recs)) if recs else np.zeros((0, 0), INFORMATION_SUMS)
+    out = np.zeros(max(B, 1), INFORMATION_SUMS)
+    _lib.check(_lib.load().mcl_information_merge(_ptr(stack), len(recs), B, _ptr(out)))
+    return out[:B]
+
+
+def group_ping_information(engines, beam_angles, sigma, r_max, sensor_offset=None, max_samples=INFORMATION_DEFAULT_SAMPLES,
+                           delta_xy=0.5, delta_yaw=0.01, jump_max=None):
+    """Engine.ping_information over shards that together hold the cloud (mcl_group_ping_information): the unsharded call's
+    records bit for bit, for any split.  A PingInformation (no dump)."""
+    lib = _lib.load()
+    ns = len(engines)
+    hs = (C.c_void_p * ns)(*[e.h for e in engines])
+    a, so = _f32(beam_angles).reshape(-1), _f64(sensor_offset)
+    steps = make_information_steps(r_max, delta_xy, delta_yaw, jump_max)
+    beams = np.zeros(max(a.size, 1), INFORMATION_SUMS)
+    n = C.c_int64(0)
+    _lib.check(lib.mcl_group_ping_information(hs, ns, _ptr(a), a.size, float(r_max), _ptr(so), int(max_samples),
+                                              C.byref(steps), _ptr(beams), C.byref(n)), engines[0].h)
+    return PingInformation(beams[:a.size], n.value, sigma, delta_xy, delta_yaw)
+
+
+def localisability_map(engine, cell, z, yaws, beam_angles, sigma, r_max, sensor_offset=None, roll=0.0, pitch=0.0,
+                       delta_xy=0.5, delta_yaw=0.01, jump_max=None, margin=0.0):
+    """Where on the engine's map can a vehicle localise?  A lattice of poses over map_bounds() -- cell centres `cell`
+    metres apart, in map coordinates, at height z and each heading of `yaws` -- through Engine.pose_information.  Returns a
+    dict of (ny, nx) rasters crlb_strong, crlb_weak, weak_axis, hit_share (row = y, column = x) and the lattice's x, y.
+    With several yaws a cell reports the heading with the worst (largest) crlb_weak: its other rasters belong to that
+    heading.  margin > 0 lets the lattice run that many metres past the map's edge on every side (cells from which no ray
+    finds the map have hit_share 0 and infinite bounds).  The map frame is the state's frame only for an identity m2o;
+    otherwise the lattice is carried into it."""
+    x0, x1, y0, y1 = engine.map_bounds()
+    x0, x1, y0, y1 = x0 - float(margin), x1 + float(margin), y0 - float(margin), y1 + float(margin)
+    cell = float(cell)
+    if not cell > 0.0:
+        raise ValueError('localisability_map: cell must be positive')
+    nx, ny = max(int(math.floor((x1 - x0) / cell)), 1), max(int(math.floor((y1 - y0) / cell)), 1)
+    xs, ys = x0 + cell * (np.arange(nx) + 0.5), y0 + cell * (np.arange(ny) + 0.5)
+    gx, gy = np.meshgrid(xs, ys)                      # (ny, nx)
+    yaws = np.atleast_1d(np.asarray(yaws, np.float64))
+    # map -> state coordinates (the inverse of m2o: a rigid motion about z for every configuration the node builds)
+    m2o = np.asarray(engine.m2o, np.float64).reshape(-1)
+    T = np.identity(4)
+    T[:3, :] = m2o[:12].reshape(3, 4)
+    Ti = np.linalg.inv(T)
+    pts = Ti @ np.stack([gx.ravel(), gy.ravel(), np.full(gx.size, float(z)), np.ones(gx.size)])
+    dyaw = math.atan2(Ti[1, 0], Ti[0, 0])
+    best = None
+    for yaw in yaws:
+        poses = np.stack([pts[0], pts[1], pts[2], np.full(gx.size, float(roll)), np.full(gx.size, float(pitch)),
+                          np.full(gx.size, float(yaw) + dyaw)])
+        r = engine.pose_information(poses, beam_angles, sigma, r_max, sensor_offset, delta_xy, delta_yaw, jump_max)
+        cur = dict(crlb_strong=r.crlb_strong, crlb_weak=r.crlb_weak, weak_axis=r.weak_axis, hit_share=r.hit_share)
+        if best is None:
+            best = cur
+        else:
+            worse = cur['crlb_weak'] > best['crlb_weak']
+            for k in best:
+                best[k] = np.where(worse, cur[k], best[k])
+    out = dict((k, v.reshape(ny, nx)) for k, v in best.items())
+    out['x'], out['y'] = xs, ys
+    return out
 
 
 def merge_weight_stats(parts):

@@ -311,6 +311,25 @@ def credible_summary(prob, radii, est_xyz, truth_xyz=None):
     return out
 
 
+def information_summary(log):
+    """what a node with mbes_information_every > 0 adds to a summary, from its information_log (one row per asked ping:
+    stamp, crlb_strong, crlb_weak, weak_axis, rank_pos, hit_share): the pings asked, the medians of the one-ping Cramer-Rao
+    bounds (metres; None -- JSON has no infinity -- where more than half of the pings fix nothing along that axis), the
+    share of pings whose position information is rank-deficient, and the rows themselves"""
+    def num(v):
+        return float(v) if np.isfinite(v) else None
+    rows = np.asarray(log, dtype=np.float64).reshape(-1, 6)
+    out = dict(information_pings=int(rows.shape[0]))
+    if rows.shape[0]:
+        out['information_crlb_strong_median'] = num(np.median(rows[:, 1]))
+        out['information_crlb_weak_median'] = num(np.median(rows[:, 2]))
+        out['information_rank_deficient_share'] = float(np.mean(rows[:, 4] < 2))
+        out['information_hit_share_mean'] = float(np.mean(rows[:, 5]))
+        out['information_per_ping'] = [dict(stamp=float(r[0]), crlb_strong=num(r[1]), crlb_weak=num(r[2]),
+                                            weak_axis=float(r[3]), rank_pos=int(r[4]), hit_share=float(r[5])) for r in rows]
+    return out
+
+
 def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0,
            fix_period=0.0, fix_latency=0.0, fix_seed=0, innovation=False):
     """Drive the node with a recorded stream; returns dict(pf_xyz[n_pub,3], pub_idx, summary).  smooth_lag > 0: also
@@ -321,8 +340,8 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
     summary gains fixes_applied, fixes_dropped and fix_mean_lag (mean age of the applied fixes, seconds).  innovation: every
     ping is first held against the cloud (Engine.ping_innovation, include/mcl_innovation.h; nothing of the filter changes)
     and the summary gains innovation_summary's keys: what to tune the node's mbes_std with.  A node with mbes_gate_nis > 0
-    adds gate_pings, gate_n_gated, gate_inconsistent.  A stream that carries its map (map_z, map_origin, map_res) is
-    replayed over it when neither grid nor mesh is given."""
+    adds gate_pings, gate_n_gated, gate_inconsistent; one with mbes_information_every > 0 adds information_summary's keys.
+    A stream that carries its map (map_z, map_origin, map_res) is replayed over it when neither grid nor mesh is given."""
     from . import auv_pf as node
     from . import msgs
     if smooth_lag > 0 and fix_period > 0:
@@ -436,6 +455,10 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
         # per-beam outlier gate (include/mcl_innovation.h): pings gated, beams marked invalid, pings that disagreed as a whole
         summary['mbes_gate_nis'], summary['gate_pings'] = float(pf.mbes_gate_nis), int(pf.gate_calls)
         summary['gate_n_gated'], summary['gate_inconsistent'] = int(pf.gated_beams), int(n_inconsistent)
+    if pf.mbes_information_every > 0:
+        # ping information (include/mcl_information.h): what every K-th ping could tell the cloud where it stood
+        summary['mbes_information_every'] = int(pf.mbes_information_every)
+        summary.update(information_summary(pf.information_log))
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -666,6 +689,11 @@ def main(argv=None):
     ap.add_argument('--gate-nis', type=float, default=0.0, metavar='G',
                     help='the node\'s mbes_gate_nis: beams whose normalised innovation squared exceeds G while almost no particle '
                          'explains them are marked invalid before the update (10.83: chi^2_1 at 0.999); 0: off')
+    ap.add_argument('--information', type=int, nargs='?', const=1, default=0, metavar='EVERY',
+                    help='the node\'s mbes_information_every: before every EVERY-th ping (default: every ping) ask how much a ping '
+                         'of that geometry can tell the cloud where it stands (include/mcl_information.h); the summary gains a '
+                         'row per asked ping, the medians of the one-ping Cramer-Rao bounds along the strong and the weak axis '
+                         'and the share of pings whose position information is rank-deficient; 0: off')
     ap.add_argument('--mbes-every', type=int, default=0, metavar='K',
                     help='synthetic streams: a multibeam ping every K samples over a synthetic map the stream carries')
     ap.add_argument('--outliers', type=float, nargs=2, default=None, metavar=('FRACTION', 'SHORTEN_M'),
@@ -731,6 +759,8 @@ def main(argv=None):
         ap.error('--gate-nis: G must be finite and >= 0')
     if (a.gate_nis > 0 or a.innovation) and (a.bag or a.recover):
         ap.error('--gate-nis / --innovation: only with the plain stream replay')
+    if a.information < 0 or (a.information > 0 and (a.bag or a.recover)):
+        ap.error('--information: EVERY >= 0, and only with the plain stream replay')
     if a.sigma is not None and not (a.sigma > 0.0 and np.isfinite(a.sigma)):
         ap.error('--sigma must be finite and > 0')
     if (a.mbes_every != 0 or a.outliers is not None) and not synthetic:
@@ -796,6 +826,8 @@ def main(argv=None):
         params.update(credible_prob=a.credible)
     if a.gate_nis > 0:
         params.update(mbes_gate_nis=a.gate_nis)
+    if a.information > 0:
+        params.update(mbes_information_every=a.information)
     if a.sigma is not None:
         params.update(mbes_std=a.sigma)
     if a.regularise > 0:

@@ -10,7 +10,9 @@ update of BASELINE config 5; `~dvl_topic` (smarc_msgs/DVL) the DVL altitude as a
 resampling (include/mcl_temper.h); `~regularise_scale` > 0 jitters every resampled cloud with its own covariance
 (`~regularise_shrink`; include/mcl_regularise.h); `~credible_prob` > 0 keeps the radius and heading half-width that hold that
 share of the posterior about every published pose (include/mcl_quantile.h); `~mbes_gate_nis` > 0 marks the beams of a
-ping that the cloud cannot explain invalid before the MBES update (include/mcl_innovation.h).
+ping that the cloud cannot explain invalid before the MBES update (include/mcl_innovation.h); `~mbes_information_every`
+K > 0 logs what every K-th ping can tell the cloud: the one-ping Cramer-Rao bounds and the direction the terrain cannot fix
+(include/mcl_information.h).
 
 ROS is not installed in the build container: the module imports whatever `rospy` / `tf` / `tf2_ros` / `*_msgs` are on
 the path -- a ROS 1 installation, or the stand-ins of tests/ros_stubs that tests/test_ros_node_stub.py drives main()
