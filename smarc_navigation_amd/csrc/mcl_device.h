@@ -39,21 +39,25 @@ __device__ __forceinline__ T dpp_move(T v) {
     return r.t;
   }
 }
+// lane `lane`'s v in every lane (v_readlane_b32 per word; `lane` wave-uniform)
 template <class T>
-__device__ __forceinline__ T readlane63(T v) {
+__device__ __forceinline__ T read_lane(T v, int lane) {
+  static_assert(sizeof(T) == 8 || sizeof(T) == 4, "32- or 64-bit values");
   if constexpr (sizeof(T) == 8) {
     union { T t; int w[2]; } a, r;
     a.t = v;
-    r.w[0] = __builtin_amdgcn_readlane(a.w[0], 63);
-    r.w[1] = __builtin_amdgcn_readlane(a.w[1], 63);
+    r.w[0] = __builtin_amdgcn_readlane(a.w[0], lane);
+    r.w[1] = __builtin_amdgcn_readlane(a.w[1], lane);
     return r.t;
   } else {
     union { T t; int w; } a, r;
     a.t = v;
-    r.w = __builtin_amdgcn_readlane(a.w, 63);
+    r.w = __builtin_amdgcn_readlane(a.w, lane);
     return r.t;
   }
 }
+template <class T>
+__device__ __forceinline__ T readlane63(T v) { return read_lane(v, 63); }
 // inclusive scan across the 64 lanes of a wave (additions in a fixed order)
 template <class T>
 __device__ __forceinline__ T wave_scan_incl_dpp(T v) {

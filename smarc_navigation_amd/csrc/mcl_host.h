@@ -2,8 +2,8 @@
 // the helpers every other part uses (error macros, launch geometry, timing regions, Philox on the host, uploads).
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
 // mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h,
-// mcl_host_drift.h, mcl_host_regularise.h, mcl_host_quantile.h, mcl_host_innovation.h, mcl_host_information.h, mcl_host_recovery.h,
-// mcl_host_modes.h
+// mcl_host_drift.h, mcl_host_regularise.h, mcl_host_quantile.h, mcl_host_innovation.h (with the pipeline of the two ping
+// statistics), mcl_host_information.h (which includes it), mcl_host_recovery.h, mcl_host_modes.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -250,10 +250,10 @@ struct mcl_handle {
   DevBuf<double> reg_part;     // per-workgroup sums [REG_SUMS_MAX][grid]
   DevBuf<double> reg_res;      // REG_RES_WORDS: the record of the last call (sums, shift, mean, cov, factor, dead mask)
   DevBuf<u64> quant_dev;       // order statistics (include/mcl_quantile.h): the state block of csrc/mcl_quantile.h, QS_WORDS (lazily)
-  DevBuf<u64> innov_dev;       // ping innovation (include/mcl_innovation.h): B beam records of 16 bytes, then the 5 x B accumulators (lazily)
+  DevBuf<u64> beamstat_dev;    // ping innovation and ping information (mcl_host_innovation.h: beamstat_prepare): B beam records of 16 bytes, then
+                               // the 5 x B, 9 x B or 9 x M accumulators of the call in flight (lazily; dead once that call has fetched)
   int env_innov_group = 0;     // MCL_INNOVATION_GROUP=n: particles per workgroup of k_innovation (A/B; 0: innovation_group decides)
-  DevBuf<u64> info_dev;        // ping information (include/mcl_information.h): B beam records of 16 bytes, then the 9 x B or 9 x M accumulators (lazily)
-  DevBuf<double> info_pose;    // ... the 6 x M poses of mcl_pose_information (lazily)
+  DevBuf<double> info_pose;    // ping information: the 6 x M poses of mcl_pose_information (lazily)
   int env_info_group = 0;      // MCL_INFORMATION_GROUP=n: poses per workgroup of k_information (A/B; 0: information_group decides)
   bool timing = false;
   std::vector<TimedRegion> regions;

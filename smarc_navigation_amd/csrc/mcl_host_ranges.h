@@ -4,13 +4,6 @@
 
 namespace {
 
-template <int MAP>
-void launch_ranges(mcl_handle* h, unsigned grid, const RangesArgs& ra) {
-  if (ra.exp_out)
-    k_ranges_update<MAP, true><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);
-  else
-    k_ranges_update<MAP, false><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);
-}
 // the beam table (normalise_beams) and the map go into the kernel's argument block; one launch over the particles
 // [first, first + count): log-likelihoods into lw_out, or (exp_out) the expected ranges instead
 int ranges_launch(mcl_handle* h, const float* ranges, const float* dirs, int B, double sigma, double r_max,
@@ -38,13 +31,13 @@ int ranges_launch(mcl_handle* h, const float* ranges, const float* dirs, int B, 
   const long long per_block = RANGES_THREADS >> lg;
   const unsigned grid = (unsigned)std::min<long long>((count + per_block - 1) / per_block, 1ll << 16);
   if (!exp_out) t_begin(h, MCL_K_UPDATE_MBES);
-  // the map walk: 0 the height grid, 2 the node heights of a triangulated regular grid, 1 triangle records
-  if (h->map_kind == 0)
-    launch_ranges<0>(h, grid, ra);
-  else if (structured_mesh(h))
-    launch_ranges<2>(h, grid, ra);
-  else
-    launch_ranges<1>(h, grid, ra);
+  map_dispatch(h, [&](auto map) {
+    constexpr int MAP = decltype(map)::value;
+    if (exp_out)
+      k_ranges_update<MAP, true><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);
+    else
+      k_ranges_update<MAP, false><<<grid, RANGES_THREADS, 0, h->stream>>>(ra);
+  });
   if (!exp_out) t_end(h);
   HIPCHK(h, hipGetLastError());
   return MCL_OK;

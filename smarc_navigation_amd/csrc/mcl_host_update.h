@@ -225,6 +225,20 @@ int sort_visiting_order(mcl_handle* h, const MbesArgs& a) {
 // a triangulated regular height grid, cast from its node heights (mesh_build uploads heights and the NaN-ringed
 // heights_pad together or fails: one test covers both arrays)
 bool structured_mesh(const mcl_handle* h) { return h->map_kind == 1 && h->mesh->heights && !h->force_general_mesh; }
+// the map walk of the single-ray kernels (mcl_mbes.h: cast_map_ray): 0 the height grid, 2 the node heights of a
+// triangulated regular grid, 1 triangle records
+int map_walk(const mcl_handle* h) { return h->map_kind == 0 ? 0 : (structured_mesh(h) ? 2 : 1); }
+// f(std::integral_constant<int, MAP>()) for that walk: the one place a launcher's MAP template argument is chosen
+template <class F>
+void map_dispatch(const mcl_handle* h, F&& f) {
+  const int map = map_walk(h);
+  if (map == 0)
+    f(std::integral_constant<int, 0>());
+  else if (map == 2)
+    f(std::integral_constant<int, 2>());
+  else
+    f(std::integral_constant<int, 1>());
+}
 
 // Frames and map of a beam update: st, n, m2o, off_t, off_R, r_max and every map field of an MbesArgs whose other
 // fields the caller has zeroed.  The MBES update (plan_mbes) and the DVL range update (mcl_host_ranges.h: ranges_launch) both

@@ -4,7 +4,8 @@
 // what the sweep does not cover (triangle soups with vertical faces / folds / non-manifold edges, unsorted beam tables,
 // small clouds) and the particles it hands over.  Shared by both: the pose records, MbesArgs, cast_clear.  Shared with the
 // fan slice (mcl_slice.h) and the range update (mcl_ranges.h): the scoring of a particle's beams (BeamScore), the pinned
-// pose record (uniform_pose), one ray against the map (cast_lattice_ray / cast_records_ray), own_cell and pose_frame.
+// pose record (uniform_pose), one ray against the map (cast_lattice_ray / cast_records_ray; cast_map_ray chooses for the
+// single-ray kernels), a beam's direction in the vehicle frame (beam_in_vehicle), own_cell and pose_frame.
 //
 //   k_mbes_pose / k_predict_pose : one thread per particle, fp64 -> sensor pose record (origin in map cell units,
 //                 two columns of R_map_sensor) in HBM (48 B/particle); <true>: also the tile window and fast-path
@@ -997,6 +998,29 @@ __device__ __forceinline__ float cast_records_ray(const MbesArgs& a, int I0, int
   if (dz < 0.f && oz > a.zmax_map) t_lo = fmaxf((a.zmax_map - oz) * fast_rcp(dz) - 1e-3f, 0.f);
   return cast_ray(a.mesh.cell_info, a.mesh.gy, a, I0, J0, a.mesh.gx, a.mesh.gy, ul, vl, oz, dx * inv_res, dy * inv_res, dx, dy,
                   dz, t_lo, a.r_max, rs);
+}
+// The map walk of a kernel that casts single rays (mcl_ranges.h, mcl_innovation.h, mcl_information.h) -- MAP 0 the height
+// grid, 2 the node heights of a triangulated regular grid, 1 triangle records (the march's statistics are not wanted).
+// sane: OwnCell's; the ray of a NaN / absurd position misses.
+template <int MAP>
+__device__ __forceinline__ float cast_map_ray(const MbesArgs& a, bool sane, int I0, int J0, float ul, float vl, float oz, float dx,
+                                              float dy, float dz) {
+  float e;
+  if (!sane) {
+    e = a.r_max;
+  } else if (MAP != 1) {
+    e = cast_lattice_ray<MAP>(a, I0, J0, ul, vl, oz, dx, dy, dz);
+  } else {
+    RayStats rs = {0, 0, 0, 0};
+    e = cast_records_ray(a, I0, J0, ul, vl, oz, dx, dy, dz, rs);
+  }
+  return e;
+}
+// the direction of a beam record (x, y, z: unit direction in the sensor frame) in the vehicle frame: v = off_R dir, fp64
+__device__ __forceinline__ void beam_in_vehicle(const MbesArgs& a, const float4& bt, double (&v)[3]) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    v[r] = a.off_R[r * 3 + 0] * (double)bt.x + a.off_R[r * 3 + 1] * (double)bt.y + a.off_R[r * 3 + 2] * (double)bt.z;
 }
 
 // ------------------------------------------------------------------ scoring one particle's beams

@@ -68,13 +68,6 @@ __device__ __forceinline__ u64 quant_mass(double lw, double m, bool have_m) {
   d = d < 0.0 ? d : 0.0;   // (a caller's maximum below a log-weight: that weight counts as the maximum)
   return (u64)(det_exp(d) * 4294967296.0);
 }
-__device__ __forceinline__ u64 quant_lane_u64(u64 v, int l) {   // (l wave-uniform)
-  union { u64 t; int w[2]; } a, r;
-  a.t = v;
-  r.w[0] = __builtin_amdgcn_readlane(a.w[0], l);
-  r.w[1] = __builtin_amdgcn_readlane(a.w[1], l);
-  return r.t;
-}
 
 // ------------------------------------------------------------------ range
 template <bool W>
@@ -241,8 +234,8 @@ __global__ void __launch_bounds__(MCL_BLOCK) k_quant_pick(u64* __restrict__ st, 
     if (hit) {   // (always, unless S = 0: the last bin's cumulative mass is S and P <= 2^32)
       const int l = __ffsll((long long)hit) - 1;
       const int f = __builtin_amdgcn_readlane(first, l);
-      cum = quant_lane_u64(f == 0 ? c0 : (f == 1 ? c1 : (f == 2 ? c2 : c3)), l);
-      below = cum - quant_lane_u64(f == 0 ? h0 : (f == 1 ? h1 : (f == 2 ? h2 : h3)), l);
+      cum = read_lane(f == 0 ? c0 : (f == 1 ? c1 : (f == 2 ? c2 : c3)), l);
+      below = cum - read_lane(f == 0 ? h0 : (f == 1 ? h1 : (f == 2 ? h2 : h3)), l);
       bin = (u64)(4 * l + f);
     }
     if (lane == 0) {

@@ -61,23 +61,14 @@ __global__ void __launch_bounds__(RANGES_THREADS) k_ranges_update(RangesArgs a) 
       sincos(m.st[5][i], &sy, &cy);
       const PoseFrame F = pose_frame(m.m2o, m.off_t, m.st[0][i], m.st[1][i], m.st[2][i], sr, cr, sp, cp, sy, cy);
       double v[3], d[3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-        v[r] = m.off_R[r * 3 + 0] * (double)bt.x + m.off_R[r * 3 + 1] * (double)bt.y + m.off_R[r * 3 + 2] * (double)bt.z;
+      beam_in_vehicle(m, bt, v);
 #pragma unroll
       for (int r = 0; r < 3; ++r) d[r] = F.Rmp[r * 3 + 0] * v[0] + F.Rmp[r * 3 + 1] * v[1] + F.Rmp[r * 3 + 2] * v[2];
       const float dx = (float)d[0], dy = (float)d[1], dz = (float)d[2];
       const float oz = (float)F.o[2];
       // ---- its own cell and the fraction inside it, then the map walk of the MBES traversal
       const OwnCell C = own_cell((F.o[0] - m.ox) * m.inv_res, (F.o[1] - m.oy) * m.inv_res);
-      if (!C.sane) {
-        e = r_max;  // (NaN / absurd position: the ray misses)
-      } else if (MAP != 1) {
-        e = cast_lattice_ray<MAP>(m, C.I0, C.J0, C.ul, C.vl, oz, dx, dy, dz);
-      } else {
-        RayStats rs = {0, 0, 0, 0};
-        e = cast_records_ray(m, C.I0, C.J0, C.ul, C.vl, oz, dx, dy, dz, rs);
-      }
+      e = cast_map_ray<MAP>(m, C.sane, C.I0, C.J0, C.ul, C.vl, oz, dx, dy, dz);
     }
     if (EXPECT_ONLY) {
       if (cast) a.exp_out[(size_t)(i - a.i0) * a.n_beams + b] = e;

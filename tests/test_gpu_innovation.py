@@ -106,6 +106,18 @@ def test_dumped_ranges_against_the_oracle_under_the_precision_contract(world, or
     outliers_explained(orc, omap, sub, ba, got, ref, R_MAX, m2o=M2O, off=OFF, label='innovation ' + kind)
 
 
+@pytest.mark.parametrize('kind', ['grid', 'tin'])
+def test_the_dump_is_the_range_updates_expected_range_byte_for_byte(world, eng, kind):
+    """k_innovation and k_ranges_update share the direction, the frame's arithmetic and the map-ray entry (mcl_mbes.h:
+    beam_in_vehicle, cast_map_ray): the same rays from the same particles give the same floats"""
+    e, _ = world[kind]
+    ba = synth.beam_angles(16)
+    inn = e.ping_innovation(np.full(16, 10.0, np.float32), ba, SIGMA, R_MAX, OFF, max_samples=MAX_SAMPLES, dump=True)
+    exp = e.ranges_expected(0, N, eng.innovation_dirs(ba), R_MAX, OFF)[world['slots']]
+    assert inn.expected.shape == exp.shape == (COUNT, 16) and np.any(exp < np.float32(R_MAX))
+    assert inn.expected.tobytes() == np.ascontiguousarray(exp).tobytes()
+
+
 # ------------------------------------------------------------------ 3. determinism
 def test_two_runs_give_the_same_bytes_and_the_handle_is_left_untouched(world, eng):
     e, _ = world['tin']
