@@ -1,6 +1,6 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
-mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h, mcl_innovation.h
-and mcl_information.h).
+mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h, mcl_innovation.h,
+mcl_information.h and mcl_match.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -133,6 +133,25 @@ class InformationSteps(C.Structure):
     """mcl_information_steps (include/mcl_information.h)"""
     _fields_ = [('delta_xy', C.c_double), ('delta_yaw', C.c_double), ('jump_max', C.c_double)]
 
+
+class MatchConfig(C.Structure):
+    """mcl_match_config (include/mcl_match.h)"""
+    _fields_ = [('dims', C.c_int32), ('max_iter', C.c_int32), ('min_beams', C.c_int32), ('grad_floor_q', C.c_int32),
+                ('step_max_xy', C.c_double), ('step_max_yaw', C.c_double), ('tol_xy', C.c_double), ('tol_yaw', C.c_double),
+                ('steps', InformationSteps)]
+
+
+# mcl_match_sums (152 bytes), mcl_match_result (360), mcl_match_trace (192) and mcl_match_derived_t (192) travel as numpy
+# record arrays
+MATCH_SUMS_FIELDS = [('n', '<i8'), ('n_miss', '<i8'), ('n_jump', '<i8'), ('S', '<i8', (10,)), ('C', '<i8', (4,)),
+                     ('s_rho', '<i8'), ('s_rho2', '<i8')]
+MATCH_RESULT_FIELDS = [('x', '<f8'), ('y', '<f8'), ('yaw', '<f8'), ('z', '<f8'), ('status', '<i4'), ('evaluations', '<i4'),
+                       ('accepted', '<i4'), ('j', '<i4'), ('dead', '<i4'), ('reserved', '<i4'),
+                       ('start', MATCH_SUMS_FIELDS), ('final', MATCH_SUMS_FIELDS)]
+MATCH_TRACE_FIELDS = [('x', '<f8'), ('y', '<f8'), ('yaw', '<f8'), ('z', '<f8'), ('sums', MATCH_SUMS_FIELDS), ('j', '<i4'),
+                      ('accepted', '<i4')]
+MATCH_DERIVED_FIELDS = [('rms', '<f8'), ('mean', '<f8'), ('chi2', '<f8'), ('J', '<f8', (10,)), ('cov', '<f8', (10,)),
+                        ('dead', '<i4'), ('m', '<i4')]
 
 # mcl_information_sums (72 bytes) and mcl_information_result (104 bytes) travel as numpy record arrays
 INFORMATION_SUMS_FIELDS = [('n', '<i8'), ('n_miss', '<i8'), ('n_jump', '<i8'), ('sxx', '<u8'), ('syy', '<u8'), ('sww', '<u8'),
@@ -329,6 +348,15 @@ INFORMATION_SYMBOLS = {
     'mcl_pose_information': (C.c_int, [_vp, _vp, _i64, _vp, _i32, _d, _vp, C.POINTER(InformationSteps), _vp]),
 }
 
+# include/mcl_match.h: ping matching, the pose fix of one ping on the map
+MATCH_SYMBOLS = {
+    'mcl_match_config_check': (C.c_int, [C.POINTER(MatchConfig), _d, C.POINTER(C.c_char_p)]),
+    'mcl_match_solve': (C.c_int, [_vp, C.POINTER(MatchConfig), _i32, _vp, C.POINTER(C.c_int32)]),
+    'mcl_match_better': (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_int32)]),
+    'mcl_match_derived': (C.c_int, [_vp, C.POINTER(MatchConfig), _d, _vp]),
+    'mcl_match_ping': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _d, _d, _vp, C.POINTER(MatchConfig), _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -345,7 +373,8 @@ def load():
                               list(HISTORY_SYMBOLS.items()) + list(ACOUSTIC_SYMBOLS.items()) +
                               list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
                               list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items()) +
-                              list(INNOVATION_SYMBOLS.items()) + list(INFORMATION_SYMBOLS.items())):
+                              list(INNOVATION_SYMBOLS.items()) + list(INFORMATION_SYMBOLS.items()) +
+                              list(MATCH_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

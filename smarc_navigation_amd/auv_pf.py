@@ -124,6 +124,14 @@ DEFAULT_PARAMS = {
     # and logs it (logger 'auv_pf', at most once per `information_log_period` seconds of filter time).  Nothing of the
     # filter changes.  0 = off: the call is never made and the node computes what it computed without the parameter.
     'mbes_information_every': 0,
+    # Ping matching (include/mcl_match.h): K > 0: after the update (and resampling) of every K-th MBES ping the node asks
+    # where that ping alone says the vehicle is -- a Levenberg-Marquardt fix of the ping on the map, started from the pose
+    # the node would publish -- keeps the answer in `last_match`, appends a row to `match_log` and logs it (logger
+    # 'auv_pf', at most once per `match_log_period` seconds of filter time).  Nothing is fed back into the filter: the
+    # ping has been used once already.  0 = off: the call is never made and the node computes what it computed without
+    # the parameter.  A call the library refuses (a ping of more than 2048 beams, say) is logged and counted in
+    # `match_errors`; the callback goes on.
+    'mbes_match_every': 0,
 }
 
 
@@ -409,6 +417,17 @@ class auv_pf(object):
         self.information_log = []       # (stamp, crlb_strong, crlb_weak, weak_axis, rank_pos, hit_share) of every call
         self._mbes_pings = 0
         self._information_logged = None
+        # ping matching behind every K-th MBES ping
+        self.mbes_match_every = int(p['mbes_match_every'])
+        if self.mbes_match_every < 0 or self.mbes_match_every != p['mbes_match_every']:
+            raise ValueError('mbes_match_every must be an integer >= 0, not %r' % (p['mbes_match_every'],))
+        self.match_log_period = 5.0
+        self.last_match = None          # dict: the start, the fix (or None), its status and rms residual
+        self.match_calls = 0
+        self.match_errors = 0           # calls the library refused (logged; the filter is not affected)
+        self.match_log = []             # (stamp, status, x, y, yaw, rms, evaluations, start x, start y, start yaw) of every call
+        self._match_pings = 0
+        self._match_logged = None
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
@@ -595,6 +614,36 @@ class auv_pf(object):
                 'rank %d, %.0f %% of the rays usable', inf.crlb_strong, inf.crlb_weak, math.degrees(inf.weak_axis),
                 inf.rank_pos, 100.0 * inf.hit_share)
 
+    def _match(self, ranges, angles, r_max):
+        """with mbes_match_every = K > 0: where pings 0, K, 2 K, ... say the vehicle is, asked after their update from the pose
+        the node would publish.  The filter is not told."""
+        if not self.mbes_match_every > 0:
+            return
+        k = self._match_pings
+        self._match_pings += 1
+        if k % self.mbes_match_every:
+            return
+        mean, yaw, _ = self.particles.mean_cov()
+        start = [float(mean[0]), float(mean[1]), float(mean[2]), float(mean[3]), float(mean[4]), float(yaw)]
+        try:
+            match, best = self.particles.match_estimate(ranges, angles, self.mbes_std, r_max, self.mbes_sensor_offset, start=start)
+        except _engine.MclError as err:
+            # a diagnostic that feeds nothing back must not take the callback down after the filter has been updated
+            self.match_errors += 1
+            logging.getLogger('auv_pf').warning('ping match refused (%s): the filter goes on without it', err)
+            return
+        i = 0 if best is None else best
+        fix = match.pose(i)
+        self.last_match = dict(start=start, converged=best is not None, match=match, **fix)
+        self.match_calls += 1
+        self.match_log.append((self.time, fix['status'], fix['x'], fix['y'], fix['yaw'], fix['rms'], fix['evaluations'],
+                               start[0], start[1], start[5]))
+        if self._match_logged is None or self.time - self._match_logged >= self.match_log_period:
+            self._match_logged = self.time
+            logging.getLogger('auv_pf').info(
+                'ping match: %s after %d evaluations, %.3f m from the published pose, rms residual %.3g m', fix['status'],
+                fix['evaluations'], math.hypot(fix['x'] - start[0], fix['y'] - start[1]), fix['rms'])
+
     def _gate(self, ranges, angles, r_max):
         """the ping's ranges as the update takes them: with mbes_gate_nis > 0 the beams the cloud cannot explain set to 0"""
         if not self.mbes_gate_nis > 0.0:
@@ -625,11 +674,13 @@ class auv_pf(object):
             if not (self.old_time and self.has_map):
                 return
             ang32 = ang[order].astype(np.float32)
+            rng32 = rng[order].astype(np.float32)
             self._information(ang32, self.mbes_range_max)
-            self.particles.update_mbes(self._gate(rng[order].astype(np.float32), ang32, self.mbes_range_max), ang32,
+            self.particles.update_mbes(self._gate(rng32, ang32, self.mbes_range_max), ang32,
                                        self.mbes_std, self.mbes_range_max, self.mbes_sensor_offset)
             self._accumulate_pending_detections(self._stamp_of(cloud))
             self.resample(self.particles)
+            self._match(rng32, ang32, self.mbes_range_max)
 
     def mbes_cb(self, scan):
         with self.lock:
@@ -638,11 +689,13 @@ class auv_pf(object):
             n = len(scan.ranges)
             angles = scan.angle_min + scan.angle_increment * np.arange(n)
             ang32 = angles.astype(np.float32)
+            rng32 = np.asarray(scan.ranges, dtype=np.float32)
             self._information(ang32, float(scan.range_max))
-            self.particles.update_mbes(self._gate(np.asarray(scan.ranges, dtype=np.float32), ang32, float(scan.range_max)),
+            self.particles.update_mbes(self._gate(rng32, ang32, float(scan.range_max)),
                                        ang32, self.mbes_std, float(scan.range_max), self.mbes_sensor_offset)
             self._accumulate_pending_detections(self._stamp_of(scan))
             self.resample(self.particles)
+            self._match(rng32, ang32, float(scan.range_max))
 
     # ---- DVL bottom range
     def dvl_cb(self, msg):

@@ -17,6 +17,7 @@
 #include "mcl_host_quantile.h"
 #include "mcl_host_innovation.h"
 #include "mcl_host_information.h"
+#include "mcl_host_match.h"
 #include "mcl_host_recovery.h"
 #include "mcl_host_modes.h"
 
@@ -1402,6 +1403,32 @@ int mcl_pose_information(mcl_handle* h, const double* poses, int64_t M, const fl
   if (!poses_out) return fail(h, MCL_ERR_INVALID, "pose_information: null argument");
   const InfoPing p = {beam_angles, B, r_max, sensor_offset, steps};
   return pose_information_run(h, p, poses, M, poses_out);
+}
+
+// ---- ping matching (include/mcl_match.h; host: mcl_host_match.h, kernel: csrc/mcl_match.h)
+int mcl_match_config_check(const mcl_match_config* cfg, double r_max, const char** reason) {
+  return match_config_check_impl(cfg, r_max, reason);
+}
+
+int mcl_match_solve(const mcl_match_sums* rec, const mcl_match_config* cfg, int32_t j, double delta_out[4], int32_t* dead_out) {
+  return match_solve_impl(rec, cfg, j, delta_out, dead_out);
+}
+
+int mcl_match_better(const mcl_match_sums* q, const mcl_match_sums* p, int32_t min_beams, int32_t* better) {
+  return match_better_impl(q, p, min_beams, better);
+}
+
+int mcl_match_derived(const mcl_match_sums* rec, const mcl_match_config* cfg, double sigma, mcl_match_derived_t* out) {
+  return match_derived_impl(rec, cfg, sigma, out);
+}
+
+int mcl_match_ping(mcl_handle* h, const double* poses, int64_t M, const float* ranges, const float* beam_angles, int32_t B,
+                   double sigma, double r_max, const double sensor_offset[6], const mcl_match_config* cfg,
+                   mcl_match_result* results_out, mcl_match_trace* trace_out, float* ranges_out) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!results_out) return fail(h, MCL_ERR_INVALID, "match_ping: null argument");
+  const MatchPing p = {ranges, beam_angles, B, sigma, r_max, sensor_offset, cfg};
+  return match_run(h, p, poses, M, results_out, trace_out, ranges_out);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

@@ -8,7 +8,8 @@
 // mcl_regularise (the factor also run by its kernel), and the keys, threshold, predicate,
 // start and bin choice of mcl_cloud_quantiles (include/mcl_quantile.h; the kernels run the same functions), and the
 // quantised residual, sample, merge and gate of mcl_ping_innovation (include/mcl_innovation.h), and the quantised
-// difference, steps, merge and matrix of mcl_ping_information (include/mcl_information.h).  No HIP header: the
+// difference, steps, merge and matrix of mcl_ping_information (include/mcl_information.h), and the compare, solve, checks
+// and derived quantities of mcl_match_ping (include/mcl_match.h; its kernel runs the first two).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -31,6 +32,7 @@
 #include "../../include/mcl_quantile.h"
 #include "../../include/mcl_innovation.h"
 #include "../../include/mcl_information.h"
+#include "../../include/mcl_match.h"
 
 namespace {
 
@@ -914,6 +916,216 @@ int information_matrix_impl(const mcl_information_sums* recs, int32_t count, int
   for (int e = 0; e < 6; ++e) o.J[e] = o.J[e] / s2;
   o.hit_share = sum_n > 0 ? (double)sum_m / (double)sum_n : 0.0;
   info_eigen(o);
+  *out = o;
+  return MCL_OK;
+}
+
+// ---- ping matching (include/mcl_match.h): which record is better, the damped normal equations and their solution, the
+// legality of a config and of a record, the derived quantities.  The kernel (csrc/mcl_match.h) runs match_better and
+// match_solve_core itself, from one lane: one statement of each rule.  The functions index their arrays in loops, so
+// the kernel hands them a workspace in LDS (MATCH_WS doubles), not in registers.
+constexpr int MATCH_WS = 32;   // A[10], L[10], y[4], t[4], delta[4]
+MCL_HD inline long long match_m(const mcl_match_sums& r) { return r.n - r.n_miss - r.n_jump; }
+// m_q >= min_beams and s_rho2_q m_p < s_rho2_p m_q, in 128 bits (the products are below 2^70)
+MCL_HD inline bool match_better(const mcl_match_sums& q, const mcl_match_sums& p, int min_beams) {
+  typedef unsigned __int128 u128;
+  const long long mq = match_m(q), mp = match_m(p);
+  if (mq < (long long)min_beams) return false;
+  return (u128)(unsigned long long)q.s_rho2 * (u128)(unsigned long long)mp < (u128)(unsigned long long)p.s_rho2 * (u128)(unsigned long long)mq;
+}
+MCL_HD inline double match_pow2(int j) {   // 2^j, -1022 <= j <= 1023
+  const unsigned long long b = (unsigned long long)(1023 + j) << 52;
+  double v;
+  __builtin_memcpy(&v, &b, sizeof v);
+  return v;
+}
+// the dimensions without a gradient: S_kk <= m floor^2 (m <= 2^11, floor <= 2^12: the product is below 2^36), and those >= D
+MCL_HD inline int match_dead_gradient(const mcl_match_sums& r, int D, int grad_floor_q) {
+  const long long lim = match_m(r) * (long long)grad_floor_q * (long long)grad_floor_q;
+  int dead = 0;
+  for (int k = 0; k < 4; ++k)
+    if (k >= D || r.S[reg_packed(k, k)] <= lim) dead |= 1 << k;
+  return dead;
+}
+MCL_HD inline int match_count_live(int dead) {
+  int c = 0;
+  for (int k = 0; k < 4; ++k) c += ((dead >> k) & 1) ? 0 : 1;
+  return c;
+}
+MCL_HD inline int match_nth_live(int dead, int i) {   // the i-th dimension that is not dead
+  for (int k = 0; k < 4; ++k)
+    if (!((dead >> k) & 1)) {
+      if (i == 0) return k;
+      --i;
+    }
+  return 3;
+}
+// A (packed, compacted to the live dimensions) and b (into y) of the normal equations, without damping
+MCL_HD inline void match_normal(const mcl_match_sums& r, int dead, double delta_xy, double delta_yaw, double* A, double* y) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int nl = match_count_live(dead);
+  for (int i = 0; i < nl; ++i) {
+    const int ki = match_nth_live(dead, i);
+    const double di = ki == 2 ? delta_yaw : delta_xy;
+    for (int k = 0; k <= i; ++k) {
+      const int kk = match_nth_live(dead, k);
+      const double dk = kk == 2 ? delta_yaw : delta_xy;
+      const double q = ((4.0 * di) * dk) * 16777216.0;
+      A[reg_packed(i, k)] = (double)r.S[reg_packed(ki, kk)] / q;
+    }
+    y[i] = (double)r.C[ki] / ((2.0 * di) * 16777216.0);
+  }
+}
+// L t = y, then L^T t' = t, without the columns `kill` (reg_factor's mask): y holds b on entry
+MCL_HD inline void match_substitute(const double* L, int nl, int kill, double* y, double* t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  for (int i = 0; i < nl; ++i) {
+    if ((kill >> i) & 1) {
+      y[i] = 0.0;
+      continue;
+    }
+    double s = y[i];
+    for (int k = 0; k < i; ++k) {
+      const double q = L[reg_packed(i, k)] * y[k];
+      s = s - q;
+    }
+    y[i] = s / L[reg_packed(i, i)];
+  }
+  for (int i = nl - 1; i >= 0; --i) {
+    if ((kill >> i) & 1) {
+      t[i] = 0.0;
+      continue;
+    }
+    double s = y[i];
+    for (int k = i + 1; k < nl; ++k) {
+      const double q = L[reg_packed(k, i)] * t[k];
+      s = s - q;
+    }
+    t[i] = s / L[reg_packed(i, i)];
+  }
+}
+// the mask of reg_factor over the compacted dimensions, as a mask over x, y, yaw, z
+MCL_HD inline int match_expand_mask(int dead, int kill) {
+  int out = 0;
+  const int nl = match_count_live(dead);
+  for (int i = 0; i < nl; ++i)
+    if ((kill >> i) & 1) out |= 1 << match_nth_live(dead, i);
+  return out;
+}
+// SOLVE of include/mcl_match.h: the step into ws[28 ... 31], the dead mask returned.  The caller has checked the config.
+MCL_HD inline int match_solve_core(const mcl_match_sums& r, const mcl_match_config& c, int j, double* ws) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double *A = ws, *L = ws + 10, *y = ws + 20, *t = ws + 24, *delta = ws + 28;
+  const int dead0 = match_dead_gradient(r, c.dims, c.grad_floor_q);
+  const int nl = match_count_live(dead0);
+  for (int k = 0; k < 4; ++k) delta[k] = 0.0;
+  if (nl == 0) return dead0;
+  match_normal(r, dead0, c.steps.delta_xy, c.steps.delta_yaw, A, y);
+  const double lam = match_pow2(j);
+  for (int i = 0; i < nl; ++i) {
+    const double q = lam * A[reg_packed(i, i)];
+    A[reg_packed(i, i)] = A[reg_packed(i, i)] + q;
+  }
+  const int kill = reg_factor(A, nl, L);
+  match_substitute(L, nl, kill, y, t);
+  for (int i = 0; i < nl; ++i)
+    if (!((kill >> i) & 1)) delta[match_nth_live(dead0, i)] = t[i];
+  const double tx = delta[0], ty = delta[1];
+  const double xx = tx * tx, yy = ty * ty;
+  const double h = sqrt(xx + yy);
+  double s = 1.0;
+  if (h > c.step_max_xy) s = c.step_max_xy / h;
+  const double az = fabs(delta[3]), aw = fabs(delta[2]);
+  if (az * s > c.step_max_xy) s = c.step_max_xy / az;
+  if (aw * s > c.step_max_yaw) s = c.step_max_yaw / aw;
+  if (s < 1.0)
+    for (int k = 0; k < 4; ++k) delta[k] = delta[k] * s;
+  return dead0 | match_expand_mask(dead0, kill);
+}
+// nullptr, or the rule of the config that is broken (the steps against r_max: match_config_check_impl)
+inline const char* match_config_why(const mcl_match_config* c) {
+  if (!c) return "null config";
+  if (c->dims != 3 && c->dims != 4) return "dims must be 3 (x, y, yaw) or 4 (x, y, yaw, z)";
+  if (c->max_iter < 1 || c->max_iter > MCL_MATCH_MAX_ITER) return "max_iter outside 1 ... 32";
+  if (c->min_beams < 1) return "min_beams must be >= 1";
+  if (c->grad_floor_q < 0 || c->grad_floor_q > MCL_MATCH_MAX_GRAD_FLOOR) return "grad_floor_q outside 0 ... 4096";
+  if (!(c->step_max_xy > 0.0) || !std::isfinite(c->step_max_xy)) return "step_max_xy must be positive and finite";
+  if (!(c->step_max_yaw > 0.0) || !std::isfinite(c->step_max_yaw)) return "step_max_yaw must be positive and finite";
+  if (!(c->tol_xy >= 0.0) || !std::isfinite(c->tol_xy)) return "tol_xy must be >= 0 and finite";
+  if (!(c->tol_yaw >= 0.0) || !std::isfinite(c->tol_yaw)) return "tol_yaw must be >= 0 and finite";
+  if (!(c->steps.delta_xy > 0.0) || !std::isfinite(c->steps.delta_xy)) return "delta_xy must be positive and finite";
+  if (!(c->steps.delta_yaw > 0.0) || !std::isfinite(c->steps.delta_yaw)) return "delta_yaw must be positive and finite";
+  return nullptr;
+}
+int match_config_check_impl(const mcl_match_config* cfg, double r_max, const char** reason) {
+  const char* why = match_config_why(cfg);
+  if (!why) why = info_steps_why(&cfg->steps, r_max);
+  if (reason) *reason = why;
+  return why ? MCL_ERR_INVALID : MCL_OK;
+}
+// can the record be a sum of the definition?
+inline bool match_legal(const mcl_match_sums& r) {
+  if (r.n < 0 || r.n > MCL_MATCH_MAX_BEAMS || r.n_miss < 0 || r.n_jump < 0 || r.n_miss > r.n || r.n_jump > r.n - r.n_miss) return false;
+  const long long m = match_m(r), cap = m << 46;
+  for (int j = 0; j < 4; ++j)
+    for (int k = 0; k <= j; ++k) {
+      const long long v = r.S[reg_packed(j, k)];
+      if (v > cap || v < (j == k ? 0 : -cap)) return false;
+    }
+  for (int k = 0; k < 4; ++k)
+    if (r.C[k] > 2 * cap || r.C[k] < -2 * cap) return false;
+  if (r.s_rho2 < 0 || r.s_rho2 > 4 * cap) return false;
+  return r.s_rho <= (m << 24) && r.s_rho >= -(m << 24);
+}
+int match_solve_impl(const mcl_match_sums* rec, const mcl_match_config* cfg, int32_t j, double* delta_out, int32_t* dead_out) {
+  if (!rec || !delta_out || !dead_out || match_config_why(cfg) || j < MCL_MATCH_J_MIN || j > MCL_MATCH_J_MAX + 2 || !match_legal(*rec))
+    return MCL_ERR_INVALID;
+  double ws[MATCH_WS];
+  *dead_out = match_solve_core(*rec, *cfg, j, ws);
+  for (int k = 0; k < 4; ++k) delta_out[k] = ws[28 + k];
+  return MCL_OK;
+}
+int match_better_impl(const mcl_match_sums* q, const mcl_match_sums* p, int32_t min_beams, int32_t* better) {
+  if (!q || !p || !better || min_beams < 1 || !match_legal(*q) || !match_legal(*p)) return MCL_ERR_INVALID;
+  *better = match_better(*q, *p, min_beams) ? 1 : 0;
+  return MCL_OK;
+}
+int match_derived_impl(const mcl_match_sums* rec, const mcl_match_config* cfg, double sigma, mcl_match_derived_t* out) {
+  if (!rec || !out || match_config_why(cfg) || !(sigma > 0.0) || !std::isfinite(sigma) || !match_legal(*rec)) return MCL_ERR_INVALID;
+  mcl_match_derived_t o;
+  memset(&o, 0, sizeof o);
+  const long long m = match_m(*rec);
+  o.m = (int32_t)m;
+  if (m > 0) {
+    o.rms = std::sqrt((double)rec->s_rho2 / (double)m) / 4096.0;
+    o.mean = ((double)rec->s_rho / (double)m) / 4096.0;
+  }
+  const double z = o.rms / sigma, s2 = sigma * sigma;
+  o.chi2 = z * z;
+  double ws[MATCH_WS];
+  double *A = ws, *L = ws + 10, *y = ws + 20, *t = ws + 24;
+  const int dead0 = match_dead_gradient(*rec, cfg->dims, cfg->grad_floor_q);
+  const int nl = match_count_live(dead0);
+  match_normal(*rec, dead0, cfg->steps.delta_xy, cfg->steps.delta_yaw, A, y);
+  for (int i = 0; i < nl; ++i)
+    for (int k = 0; k <= i; ++k) o.J[reg_packed(match_nth_live(dead0, i), match_nth_live(dead0, k))] = A[reg_packed(i, k)] / s2;
+  const int kill = nl > 0 ? reg_factor(A, nl, L) : 0;
+  o.dead = dead0 | match_expand_mask(dead0, kill);
+  for (int c = 0; c < nl; ++c) {
+    if ((kill >> c) & 1) continue;
+    for (int i = 0; i < nl; ++i) y[i] = i == c ? 1.0 : 0.0;
+    match_substitute(L, nl, kill, y, t);
+    for (int i = c; i < nl; ++i)
+      if (!((kill >> i) & 1)) o.cov[reg_packed(match_nth_live(dead0, i), match_nth_live(dead0, c))] = t[i] * s2;
+  }
+  for (int k = 0; k < cfg->dims; ++k)
+    if ((o.dead >> k) & 1) o.cov[reg_packed(k, k)] = std::numeric_limits<double>::infinity();
   *out = o;
   return MCL_OK;
 }

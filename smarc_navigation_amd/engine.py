@@ -292,6 +292,79 @@ class PoseInformation(object):
             setattr(self, f, r[f].copy())
 
 
+MATCH_SUMS = np.dtype(_lib.MATCH_SUMS_FIELDS)
+MATCH_RESULT = np.dtype(_lib.MATCH_RESULT_FIELDS)
+MATCH_TRACE = np.dtype(_lib.MATCH_TRACE_FIELDS)
+MATCH_DERIVED = np.dtype(_lib.MATCH_DERIVED_FIELDS)
+MATCH_CONVERGED, MATCH_MAX_ITER, MATCH_STALLED, MATCH_NO_OVERLAP = 0, 1, 2, 3
+MATCH_STATUS_NAMES = ('CONVERGED', 'MAX_ITER', 'STALLED', 'NO_OVERLAP')
+MATCH_MAX_DUMP = 1 << 26
+
+
+def make_match_config(r_max, fit_z=False, max_iter=12, min_beams=8, grad_floor_q=2, step_max_xy=2.0, step_max_yaw=0.1,
+                      tol_xy=1e-3, tol_yaw=1e-4, delta_xy=0.5, delta_yaw=0.01, jump_max=None):
+    """mcl_match_config (include/mcl_match.h); the steps as make_information_steps.  The defaults are policy."""
+    c = _lib.MatchConfig()
+    c.dims, c.max_iter, c.min_beams, c.grad_floor_q = (4 if fit_z else 3), int(max_iter), int(min_beams), int(grad_floor_q)
+    c.step_max_xy, c.step_max_yaw, c.tol_xy, c.tol_yaw = float(step_max_xy), float(step_max_yaw), float(tol_xy), float(tol_yaw)
+    c.steps = make_information_steps(r_max, delta_xy, delta_yaw, jump_max)
+    return c
+
+
+class PingMatch(object):
+    """what Engine.match_ping returns: `results` (a record array of MATCH_RESULT, one per start pose: x, y, yaw, z, status,
+    evaluations, accepted, j, dead, start, final), per pose the contributing beams m and -- the arithmetic of
+    mcl_match_derived, operation by operation -- rms, mean (metres), chi2 (per contributing beam) of the final record and
+    start_rms of the start's, the config, and with trace=True `trace` (M x (max_iter + 1) records of MATCH_TRACE), with
+    dump=True `ranges` (M x (max_iter + 1) x (1 + 2 D) x B, NaN where nothing was cast)."""
+
+    def __init__(self, results, cfg, sigma, trace=None, ranges=None):
+        self.results, self.cfg, self.sigma, self.trace, self.ranges = results, cfg, float(sigma), trace, ranges
+        self.status = results['status'].copy()
+        self.m, self.rms, self.mean = self._residuals(results['final'])
+        self.start_rms = self._residuals(results['start'])[1]
+        z = self.rms / self.sigma
+        self.chi2 = z * z
+
+    @staticmethod
+    def _residuals(rec):
+        m = rec['n'] - rec['n_miss'] - rec['n_jump']
+        some = m > 0
+        mf = np.where(some, m, 1).astype(np.float64)
+        rms = np.where(some, np.sqrt(rec['s_rho2'].astype(np.float64) / mf) / 4096.0, 0.0)
+        return m, rms, np.where(some, (rec['s_rho'].astype(np.float64) / mf) / 4096.0, 0.0)
+
+    def __len__(self):
+        return self.results.size
+
+    def best(self):
+        """the index of the CONVERGED pose with the lowest rms residual, or None"""
+        ok = np.flatnonzero(self.status == MATCH_CONVERGED)
+        return int(ok[np.argmin(self.rms[ok])]) if ok.size else None
+
+    def pose(self, i):
+        r = self.results[i]
+        return dict(x=float(r['x']), y=float(r['y']), yaw=float(r['yaw']), z=float(r['z']),
+                    status=MATCH_STATUS_NAMES[int(r['status'])], rms=float(self.rms[i]), evaluations=int(r['evaluations']))
+
+    def derived(self, i):
+        """mcl_match_derived of fix i's final record"""
+        return match_derived(self.results['final'][i], self.cfg, self.sigma)
+
+    def cov(self, i):
+        """the covariance of fix i over (x, y, yaw[, z]): sigma^2 A^-1, D x D; inf on the diagonal of a dead dimension"""
+        return self._symmetric(self.derived(i)['cov'])
+
+    def information(self, i):
+        """J = A / sigma^2 of fix i, without damping, D x D"""
+        return self._symmetric(self.derived(i)['J'])
+
+    def _symmetric(self, packed):
+        """the packed lower triangle over (x, y, yaw, z) as the full symmetric D x D matrix"""
+        low = _unpack_lower(packed, 4)
+        return (low + np.tril(low, -1).T)[:self.cfg.dims, :self.cfg.dims]
+
+
 def make_gate_config(nis_gate=10.83, min_support=0.01, max_gated_fraction=0.25):
     c = _lib.InnovationGateConfig()
     c.nis_gate, c.min_support, c.max_gated_fraction = float(nis_gate), float(min_support), float(max_gated_fraction)
@@ -828,6 +901,43 @@ class Engine(object):
                                                C.byref(steps), _ptr(out)))
         return PoseInformation(out[:p.shape[1]], sigma, delta_xy, delta_yaw)
 
+    # ---- ping matching: where the ping says the vehicle is (include/mcl_match.h)
+    def match_ping(self, poses, ranges, beam_angles, sigma, r_max, sensor_offset=None, fit_z=False, max_iter=12, trace=False,
+                   dump=False, cfg=None, **config):
+        """the Levenberg-Marquardt pose fix of one ping from each of M start poses (6 x M: x, y, z, roll, pitch, yaw in the
+        coordinates the particle state is stored in; mcl_match_ping) -- a PingMatch.  Needs a map, no particles; nothing of
+        the filter is read or written.  cfg: a MatchConfig instead of fit_z / max_iter / the keywords of make_match_config."""
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(6, -1))
+        r, a, so = _f32(ranges).reshape(-1), _f32(beam_angles).reshape(-1), _f64(sensor_offset)
+        if r.size != a.size:
+            raise ValueError('match_ping: %d ranges for %d beam angles' % (r.size, a.size))
+        c = cfg if cfg is not None else make_match_config(r_max, fit_z, max_iter, **config)
+        M, T, nv = p.shape[1], max(int(c.max_iter), 0) + 1, 1 + 2 * int(c.dims)
+        res = np.zeros(max(M, 1), MATCH_RESULT)
+        tr = np.zeros((max(M, 1), T), MATCH_TRACE) if trace else None
+        floats = max(M, 1) * T * max(nv, 1) * max(a.size, 1)
+        # (a dump beyond the limit: the library refuses it before it writes; one float stands in for the buffer)
+        rng = np.full(floats if floats <= MATCH_MAX_DUMP else 1, np.nan, np.float32) if dump else None
+        self._ck(self.lib.mcl_match_ping(self.h, _ptr(p), M, _ptr(r), _ptr(a), a.size, float(sigma), float(r_max), _ptr(so),
+                                         C.byref(c), _ptr(res), _ptr(tr), _ptr(rng)))
+        if rng is not None:
+            rng = rng.reshape(M, T, nv, a.size)
+        return PingMatch(res[:M], c, sigma, tr, rng)
+
+    def match_estimate(self, ranges, beam_angles, sigma, r_max, sensor_offset=None, modes=0, mode_cell=2.0, mode_n_yaw=36,
+                       start=None, **kw):
+        """match_ping from the cloud's mean pose (start: a pose of 6 instead), plus up to `modes` peaks of pose_modes: returns
+        (PingMatch, index of its best fix or None)"""
+        if start is None:
+            mean, yaw, _ = self.mean_cov()
+            start = np.array(mean, np.float64)
+            start[5] = yaw
+        starts = [np.asarray(start, np.float64).reshape(6)]
+        if modes > 0:
+            starts += [m.mean for m in self.pose_modes(mode_cell, mode_n_yaw, int(modes))[0]]
+        match = self.match_ping(np.stack(starts, axis=1), ranges, beam_angles, sigma, r_max, sensor_offset, **kw)
+        return match, match.best()
+
     def set_landmarks(self, xyz):
         a = _f64(xyz)
         self._ck(self.lib.mcl_set_landmarks(self.h, _ptr(a), a.shape[0]))
@@ -1275,6 +1385,38 @@ def group_ping_information(engines, beam_angles, sigma, r_max, sensor_offset=Non
     _lib.check(lib.mcl_group_ping_information(hs, ns, _ptr(a), a.size, float(r_max), _ptr(so), int(max_samples),
                                               C.byref(steps), _ptr(beams), C.byref(n)), engines[0].h)
     return PingInformation(beams[:a.size], n.value, sigma, delta_xy, delta_yaw)
+
+
+def _match_record(rec):
+    return np.ascontiguousarray(rec, dtype=MATCH_SUMS).reshape(-1)[:1].copy()
+
+
+def match_config_check(cfg, r_max):
+    """None when mcl_match_ping would accept the config for this r_max, else the rule that is broken (host arithmetic)"""
+    why = C.c_char_p()
+    rc = _lib.load().mcl_match_config_check(C.byref(cfg) if cfg is not None else None, float(r_max), C.byref(why))
+    return None if rc == 0 else (why.value or b'').decode()
+
+
+def match_solve(rec, cfg, j):
+    """SOLVE of include/mcl_match.h (mcl_match_solve: host arithmetic): (delta over x, y, yaw, z; the dead mask)"""
+    r, d, dead = _match_record(rec), np.zeros(4), C.c_int32(0)
+    _lib.check(_lib.load().mcl_match_solve(_ptr(r), C.byref(cfg), int(j), _ptr(d), C.byref(dead)))
+    return d, int(dead.value)
+
+
+def match_better(q, p, min_beams):
+    """is the pose with the record q better than the one with the record p (mcl_match_better: 128-bit integers)"""
+    a, b, out = _match_record(q), _match_record(p), C.c_int32(0)
+    _lib.check(_lib.load().mcl_match_better(_ptr(a), _ptr(b), int(min_beams), C.byref(out)))
+    return bool(out.value)
+
+
+def match_derived(rec, cfg, sigma):
+    """the derived quantities of a record (mcl_match_derived: host arithmetic) as one record of MATCH_DERIVED"""
+    r, out = _match_record(rec), np.zeros(1, MATCH_DERIVED)
+    _lib.check(_lib.load().mcl_match_derived(_ptr(r), C.byref(cfg), float(sigma), _ptr(out)))
+    return out[0]
 
 
 def localisability_map(engine, cell, z, yaws, beam_angles, sigma, r_max, sensor_offset=None, roll=0.0, pitch=0.0,

@@ -12,7 +12,8 @@ resampling (include/mcl_temper.h); `~regularise_scale` > 0 jitters every resampl
 share of the posterior about every published pose (include/mcl_quantile.h); `~mbes_gate_nis` > 0 marks the beams of a
 ping that the cloud cannot explain invalid before the MBES update (include/mcl_innovation.h); `~mbes_information_every`
 K > 0 logs what every K-th ping can tell the cloud: the one-ping Cramer-Rao bounds and the direction the terrain cannot fix
-(include/mcl_information.h).
+(include/mcl_information.h); `~mbes_match_every` K > 0 fits every K-th ping alone to the map after its update, from the
+published pose, and logs where that ping says the vehicle is -- nothing is fed back into the filter (include/mcl_match.h).
 
 ROS is not installed in the build container: the module imports whatever `rospy` / `tf` / `tf2_ros` / `*_msgs` are on
 the path -- a ROS 1 installation, or the stand-ins of tests/ros_stubs that tests/test_ros_node_stub.py drives main()
