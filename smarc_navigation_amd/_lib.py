@@ -1,6 +1,6 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
 mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h, mcl_innovation.h,
-mcl_information.h and mcl_match.h).
+mcl_information.h, mcl_match.h and mcl_swath.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -152,6 +152,9 @@ MATCH_TRACE_FIELDS = [('x', '<f8'), ('y', '<f8'), ('yaw', '<f8'), ('z', '<f8'), 
                       ('accepted', '<i4')]
 MATCH_DERIVED_FIELDS = [('rms', '<f8'), ('mean', '<f8'), ('chi2', '<f8'), ('J', '<f8', (10,)), ('cov', '<f8', (10,)),
                         ('dead', '<i4'), ('m', '<i4')]
+
+# mcl_swath_offset (include/mcl_swath.h; 48 bytes) travels as a numpy record array (engine.SwathOffset is the dtype)
+SWATH_OFFSET_FIELDS = [('dx', '<f8'), ('dy', '<f8'), ('dz', '<f8'), ('roll', '<f8'), ('pitch', '<f8'), ('dyaw', '<f8')]
 
 # mcl_information_sums (72 bytes) and mcl_information_result (104 bytes) travel as numpy record arrays
 INFORMATION_SUMS_FIELDS = [('n', '<i8'), ('n_miss', '<i8'), ('n_jump', '<i8'), ('sxx', '<u8'), ('syy', '<u8'), ('sww', '<u8'),
@@ -357,6 +360,16 @@ MATCH_SYMBOLS = {
     'mcl_match_ping': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _d, _d, _vp, C.POINTER(MatchConfig), _vp, _vp, _vp]),
 }
 
+# include/mcl_swath.h: swath matching, the pose fix of the last K pings on the map as one rigid set
+SWATH_SYMBOLS = {
+    'mcl_swath_offsets': (C.c_int, [_vp, _i32, _i32, _vp]),
+    'mcl_swath_check': (C.c_int, [_i32, _i32, _vp, C.POINTER(C.c_char_p)]),
+    'mcl_swath_solve': (C.c_int, [_vp, C.POINTER(MatchConfig), _i32, _vp, C.POINTER(C.c_int32)]),
+    'mcl_swath_better': (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_int32)]),
+    'mcl_swath_derived': (C.c_int, [_vp, C.POINTER(MatchConfig), _d, _vp]),
+    'mcl_match_swath': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _d, _d, _vp, C.POINTER(MatchConfig), _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -374,7 +387,7 @@ def load():
                               list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
                               list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items()) +
                               list(INNOVATION_SYMBOLS.items()) + list(INFORMATION_SYMBOLS.items()) +
-                              list(MATCH_SYMBOLS.items())):
+                              list(MATCH_SYMBOLS.items()) + list(SWATH_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

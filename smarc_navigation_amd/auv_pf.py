@@ -132,6 +132,17 @@ DEFAULT_PARAMS = {
     # the parameter.  A call the library refuses (a ping of more than 2048 beams, say) is logged and counted in
     # `match_errors`; the callback goes on.
     'mbes_match_every': 0,
+    # Swath matching (include/mcl_swath.h): `mbes_swath_pings` K > 0: the node keeps a ring of the last K MBES pings' ranges
+    # with the vehicle's odometry pose at each of them, and after the update (and resampling) of every
+    # `mbes_swath_every`-th ping, once the ring is full, fits those K pings to the map as one rigid set -- tied to each other
+    # by the odometry, anchored at the newest, started from the pose the node would publish -- keeps the answer in
+    # `last_swath`, appends a row to `swath_log` and logs it (logger 'auv_pf', at most once per `swath_log_period` seconds
+    # of filter time).  One ping cannot tell the along-track position from depth; K pings can.  Nothing is fed back into
+    # the filter.  K = 0 = off: no call is made and no ring is kept.  A ping whose beam count differs from the ring's
+    # restarts the ring; the newest ping's beam angles stand for all K.  A call the library refuses is logged and counted
+    # in `swath_errors`; the callback goes on.
+    'mbes_swath_pings': 0,
+    'mbes_swath_every': 1,
 }
 
 
@@ -428,6 +439,21 @@ class auv_pf(object):
         self.match_log = []             # (stamp, status, x, y, yaw, rms, evaluations, start x, start y, start yaw) of every call
         self._match_pings = 0
         self._match_logged = None
+        # swath matching: the last K pings as one rigid set, behind every E-th MBES ping
+        # (the range first: a NaN fails every comparison, an infinity has no int())
+        if not 0 <= p['mbes_swath_pings'] <= _engine.SWATH_MAX_PINGS or int(p['mbes_swath_pings']) != p['mbes_swath_pings']:
+            raise ValueError('mbes_swath_pings must be an integer in 0 ... %d, not %r' % (_engine.SWATH_MAX_PINGS, p['mbes_swath_pings']))
+        if not 1 <= p['mbes_swath_every'] < float('inf') or int(p['mbes_swath_every']) != p['mbes_swath_every']:
+            raise ValueError('mbes_swath_every must be an integer >= 1, not %r' % (p['mbes_swath_every'],))
+        self.mbes_swath_pings, self.mbes_swath_every = int(p['mbes_swath_pings']), int(p['mbes_swath_every'])
+        self.swath_log_period = 5.0
+        self.last_swath = None          # dict: the start, the fix (or None), its status and rms residual, the offsets
+        self.swath_calls = 0
+        self.swath_errors = 0           # calls the library refused (logged; the filter is not affected)
+        self.swath_log = []             # rows as match_log's
+        self._swath_ring = collections.deque(maxlen=self.mbes_swath_pings) if self.mbes_swath_pings > 0 else None
+        self._swath_pings = 0
+        self._swath_logged = None
 
     # ---- REPLAY-mode RNG source (parity runs): rs must offer randn(n, 6) and random_sample(k)
     def set_replay_source(self, rs):
@@ -644,6 +670,49 @@ class auv_pf(object):
                 'ping match: %s after %d evaluations, %.3f m from the published pose, rms residual %.3g m', fix['status'],
                 fix['evaluations'], math.hypot(fix['x'] - start[0], fix['y'] - start[1]), fix['rms'])
 
+    def _swath(self, ranges, angles, r_max):
+        """with mbes_swath_pings = K > 0: the ping joins the ring with the odometry pose it was taken at; behind pings 0, E,
+        2 E, ... (E = mbes_swath_every), once the ring holds K pings, where those K pings together say the vehicle is at the
+        newest of them.  The filter is not told."""
+        ring = self._swath_ring
+        if ring is None:
+            return
+        k = self._swath_pings
+        self._swath_pings += 1
+        if self.odom_latest is None:
+            ring.clear()                # no pose to tie the ping to the others with
+            return
+        if ring and ring[-1][0].size != ranges.size:
+            ring.clear()                # another sonar geometry: the pings of a swath share one beam table (the newest ping's)
+        po = self.odom_latest.pose.pose
+        roll, pitch, yaw = euler_from_quaternion([po.orientation.x, po.orientation.y, po.orientation.z, po.orientation.w])
+        ring.append((np.array(ranges, np.float32),
+                     (float(po.position.x), float(po.position.y), float(po.position.z), float(roll), float(pitch), float(yaw))))
+        if k % self.mbes_swath_every or len(ring) < self.mbes_swath_pings:
+            return
+        mean, myaw, _ = self.particles.mean_cov()
+        start = [float(mean[0]), float(mean[1]), float(mean[2]), float(mean[3]), float(mean[4]), float(myaw)]
+        try:
+            offsets = _engine.swath_offsets(np.array([r[1] for r in ring], np.float64).T, -1)
+            match, best = self.particles.match_swath_estimate(np.stack([r[0] for r in ring]), angles, offsets, self.mbes_std, r_max,
+                                                              self.mbes_sensor_offset, start=start)
+        except _engine.MclError as err:
+            # a diagnostic that feeds nothing back must not take the callback down after the filter has been updated
+            self.swath_errors += 1
+            logging.getLogger('auv_pf').warning('swath match refused (%s): the filter goes on without it', err)
+            return
+        i = 0 if best is None else best
+        fix = match.pose(i)
+        self.last_swath = dict(start=start, converged=best is not None, match=match, offsets=offsets, **fix)
+        self.swath_calls += 1
+        self.swath_log.append((self.time, fix['status'], fix['x'], fix['y'], fix['yaw'], fix['rms'], fix['evaluations'],
+                               start[0], start[1], start[5]))
+        if self._swath_logged is None or self.time - self._swath_logged >= self.swath_log_period:
+            self._swath_logged = self.time
+            logging.getLogger('auv_pf').info(
+                'swath match of %d pings: %s after %d evaluations, %.3f m from the published pose, rms residual %.3g m',
+                len(ring), fix['status'], fix['evaluations'], math.hypot(fix['x'] - start[0], fix['y'] - start[1]), fix['rms'])
+
     def _gate(self, ranges, angles, r_max):
         """the ping's ranges as the update takes them: with mbes_gate_nis > 0 the beams the cloud cannot explain set to 0"""
         if not self.mbes_gate_nis > 0.0:
@@ -681,6 +750,7 @@ class auv_pf(object):
             self._accumulate_pending_detections(self._stamp_of(cloud))
             self.resample(self.particles)
             self._match(rng32, ang32, self.mbes_range_max)
+            self._swath(rng32, ang32, self.mbes_range_max)
 
     def mbes_cb(self, scan):
         with self.lock:
@@ -696,6 +766,7 @@ class auv_pf(object):
             self._accumulate_pending_detections(self._stamp_of(scan))
             self.resample(self.particles)
             self._match(rng32, ang32, float(scan.range_max))
+            self._swath(rng32, ang32, float(scan.range_max))
 
     # ---- DVL bottom range
     def dvl_cb(self, msg):

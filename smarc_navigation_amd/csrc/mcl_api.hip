@@ -18,6 +18,7 @@
 #include "mcl_host_innovation.h"
 #include "mcl_host_information.h"
 #include "mcl_host_match.h"
+#include "mcl_host_swath.h"
 #include "mcl_host_recovery.h"
 #include "mcl_host_modes.h"
 
@@ -1429,6 +1430,36 @@ int mcl_match_ping(mcl_handle* h, const double* poses, int64_t M, const float* r
   if (!results_out) return fail(h, MCL_ERR_INVALID, "match_ping: null argument");
   const MatchPing p = {ranges, beam_angles, B, sigma, r_max, sensor_offset, cfg};
   return match_run(h, p, poses, M, results_out, trace_out, ranges_out);
+}
+
+// ---- swath matching (include/mcl_swath.h; host: mcl_host_swath.h, kernel: csrc/mcl_swath.h)
+int mcl_swath_offsets(const double* poses6, int32_t K, int32_t anchor, mcl_swath_offset* out) {
+  return swath_offsets_impl(poses6, K, anchor, out);
+}
+
+int mcl_swath_check(int32_t K, int32_t B, const mcl_swath_offset* offsets, const char** reason) {
+  return swath_check_impl(K, B, offsets, reason);
+}
+
+int mcl_swath_solve(const mcl_match_sums* rec, const mcl_match_config* cfg, int32_t j, double delta_out[4], int32_t* dead_out) {
+  return match_solve_impl(rec, cfg, j, delta_out, dead_out, MCL_SWATH_MAX_BEAMS);
+}
+
+int mcl_swath_better(const mcl_match_sums* q, const mcl_match_sums* p, int32_t min_beams, int32_t* better) {
+  return match_better_impl(q, p, min_beams, better, MCL_SWATH_MAX_BEAMS);
+}
+
+int mcl_swath_derived(const mcl_match_sums* rec, const mcl_match_config* cfg, double sigma, mcl_match_derived_t* out) {
+  return match_derived_impl(rec, cfg, sigma, out, MCL_SWATH_MAX_BEAMS);
+}
+
+int mcl_match_swath(mcl_handle* h, const double* poses, int64_t M, const float* ranges, const float* beam_angles, int32_t B,
+                    const mcl_swath_offset* offsets, int32_t K, double sigma, double r_max, const double sensor_offset[6],
+                    const mcl_match_config* cfg, mcl_match_result* results_out, mcl_match_trace* trace_out, float* ranges_out) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!results_out) return fail(h, MCL_ERR_INVALID, "match_swath: null argument");
+  const Swath s = {{ranges, beam_angles, B, sigma, r_max, sensor_offset, cfg}, offsets, K};
+  return swath_run(h, s, poses, M, results_out, trace_out, ranges_out);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

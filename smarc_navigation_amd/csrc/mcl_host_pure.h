@@ -33,6 +33,7 @@
 #include "../../include/mcl_innovation.h"
 #include "../../include/mcl_information.h"
 #include "../../include/mcl_match.h"
+#include "../../include/mcl_swath.h"
 
 namespace {
 
@@ -926,7 +927,7 @@ int information_matrix_impl(const mcl_information_sums* recs, int32_t count, int
 // the kernel hands them a workspace in LDS (MATCH_WS doubles), not in registers.
 constexpr int MATCH_WS = 32;   // A[10], L[10], y[4], t[4], delta[4]
 MCL_HD inline long long match_m(const mcl_match_sums& r) { return r.n - r.n_miss - r.n_jump; }
-// m_q >= min_beams and s_rho2_q m_p < s_rho2_p m_q, in 128 bits (the products are below 2^70)
+// m_q >= min_beams and s_rho2_q m_p < s_rho2_p m_q, in 128 bits (the products are below 2^70; a swath's, mcl_swath.h, 2^76)
 MCL_HD inline bool match_better(const mcl_match_sums& q, const mcl_match_sums& p, int min_beams) {
   typedef unsigned __int128 u128;
   const long long mq = match_m(q), mp = match_m(p);
@@ -939,7 +940,7 @@ MCL_HD inline double match_pow2(int j) {   // 2^j, -1022 <= j <= 1023
   __builtin_memcpy(&v, &b, sizeof v);
   return v;
 }
-// the dimensions without a gradient: S_kk <= m floor^2 (m <= 2^11, floor <= 2^12: the product is below 2^36), and those >= D
+// the dimensions without a gradient: S_kk <= m floor^2 (m <= 2^11, a swath's 2^14, floor <= 2^12: the product is below 2^38), and those >= D
 MCL_HD inline int match_dead_gradient(const mcl_match_sums& r, int D, int grad_floor_q) {
   const long long lim = match_m(r) * (long long)grad_floor_q * (long long)grad_floor_q;
   int dead = 0;
@@ -1069,9 +1070,9 @@ int match_config_check_impl(const mcl_match_config* cfg, double r_max, const cha
   if (reason) *reason = why;
   return why ? MCL_ERR_INVALID : MCL_OK;
 }
-// can the record be a sum of the definition?
-inline bool match_legal(const mcl_match_sums& r) {
-  if (r.n < 0 || r.n > MCL_MATCH_MAX_BEAMS || r.n_miss < 0 || r.n_jump < 0 || r.n_miss > r.n || r.n_jump > r.n - r.n_miss) return false;
+// can the record be a sum of the definition?  n_max: MCL_MATCH_MAX_BEAMS, or a swath's MCL_SWATH_MAX_BEAMS (m <= 2^14: 4 cap <= 2^62)
+inline bool match_legal(const mcl_match_sums& r, long long n_max = MCL_MATCH_MAX_BEAMS) {
+  if (r.n < 0 || r.n > n_max || r.n_miss < 0 || r.n_jump < 0 || r.n_miss > r.n || r.n_jump > r.n - r.n_miss) return false;
   const long long m = match_m(r), cap = m << 46;
   for (int j = 0; j < 4; ++j)
     for (int k = 0; k <= j; ++k) {
@@ -1083,21 +1084,24 @@ inline bool match_legal(const mcl_match_sums& r) {
   if (r.s_rho2 < 0 || r.s_rho2 > 4 * cap) return false;
   return r.s_rho <= (m << 24) && r.s_rho >= -(m << 24);
 }
-int match_solve_impl(const mcl_match_sums* rec, const mcl_match_config* cfg, int32_t j, double* delta_out, int32_t* dead_out) {
-  if (!rec || !delta_out || !dead_out || match_config_why(cfg) || j < MCL_MATCH_J_MIN || j > MCL_MATCH_J_MAX + 2 || !match_legal(*rec))
+int match_solve_impl(const mcl_match_sums* rec, const mcl_match_config* cfg, int32_t j, double* delta_out, int32_t* dead_out,
+                     long long n_max = MCL_MATCH_MAX_BEAMS) {
+  if (!rec || !delta_out || !dead_out || match_config_why(cfg) || j < MCL_MATCH_J_MIN || j > MCL_MATCH_J_MAX + 2 || !match_legal(*rec, n_max))
     return MCL_ERR_INVALID;
   double ws[MATCH_WS];
   *dead_out = match_solve_core(*rec, *cfg, j, ws);
   for (int k = 0; k < 4; ++k) delta_out[k] = ws[28 + k];
   return MCL_OK;
 }
-int match_better_impl(const mcl_match_sums* q, const mcl_match_sums* p, int32_t min_beams, int32_t* better) {
-  if (!q || !p || !better || min_beams < 1 || !match_legal(*q) || !match_legal(*p)) return MCL_ERR_INVALID;
+int match_better_impl(const mcl_match_sums* q, const mcl_match_sums* p, int32_t min_beams, int32_t* better,
+                      long long n_max = MCL_MATCH_MAX_BEAMS) {
+  if (!q || !p || !better || min_beams < 1 || !match_legal(*q, n_max) || !match_legal(*p, n_max)) return MCL_ERR_INVALID;
   *better = match_better(*q, *p, min_beams) ? 1 : 0;
   return MCL_OK;
 }
-int match_derived_impl(const mcl_match_sums* rec, const mcl_match_config* cfg, double sigma, mcl_match_derived_t* out) {
-  if (!rec || !out || match_config_why(cfg) || !(sigma > 0.0) || !std::isfinite(sigma) || !match_legal(*rec)) return MCL_ERR_INVALID;
+int match_derived_impl(const mcl_match_sums* rec, const mcl_match_config* cfg, double sigma, mcl_match_derived_t* out,
+                       long long n_max = MCL_MATCH_MAX_BEAMS) {
+  if (!rec || !out || match_config_why(cfg) || !(sigma > 0.0) || !std::isfinite(sigma) || !match_legal(*rec, n_max)) return MCL_ERR_INVALID;
   mcl_match_derived_t o;
   memset(&o, 0, sizeof o);
   const long long m = match_m(*rec);
@@ -1127,6 +1131,61 @@ int match_derived_impl(const mcl_match_sums* rec, const mcl_match_config* cfg, d
   for (int k = 0; k < cfg->dims; ++k)
     if ((o.dead >> k) & 1) o.cov[reg_packed(k, k)] = std::numeric_limits<double>::infinity();
   *out = o;
+  return MCL_OK;
+}
+
+// ---- swath matching (include/mcl_swath.h): the offsets of K dead-reckoned poses relative to one of them and the check of
+// a swath.  Solve, compare and derived quantities are the ping matching's above with n_max = MCL_SWATH_MAX_BEAMS.
+inline const char* swath_why(int K, int B, const mcl_swath_offset* off) {
+  if (K < 1 || K > MCL_SWATH_MAX_PINGS) return "K outside 1 ... 64";
+  if (B < 1 || B > MCL_MATCH_MAX_BEAMS) return "B outside 1 ... 2048";
+  if ((long long)K * B > MCL_SWATH_MAX_BEAMS) return "K B above 16384";
+  if (!off) return "null offsets";
+  for (int k = 0; k < K; ++k) {
+    const mcl_swath_offset& o = off[k];
+    if (!std::isfinite(o.dx) || !std::isfinite(o.dy) || !std::isfinite(o.dz) || !std::isfinite(o.roll) || !std::isfinite(o.pitch) ||
+        !std::isfinite(o.dyaw))
+      return "an offset is not finite";
+  }
+  return nullptr;
+}
+int swath_check_impl(int K, int B, const mcl_swath_offset* off, const char** reason) {
+  const char* why = swath_why(K, B, off);
+  if (reason) *reason = why;
+  return why ? MCL_ERR_INVALID : MCL_OK;
+}
+// the library's rule for a yaw that moved: kept when -pi <= t < pi, else ((t + pi) mod 2 pi) - pi with the floored modulo
+inline double swath_wrap(double t) {
+  const double pi = 3.14159265358979323846, b = 2.0 * pi;
+  if (t >= -pi && t < pi) return t;
+  double m = std::fmod(t + pi, b);
+  if (m < 0.0) m = m + b;
+  return m - pi;
+}
+int swath_offsets_impl(const double* p, int K, int anchor, mcl_swath_offset* out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (!p || !out || K < 1 || K > MCL_SWATH_MAX_PINGS || anchor < -1 || anchor >= K) return MCL_ERR_INVALID;
+  for (int k = 0; k < 6 * K; ++k)
+    if (!std::isfinite(p[k])) return MCL_ERR_INVALID;
+  const int a = anchor < 0 ? K - 1 : anchor;
+  const double *x = p, *y = p + K, *z = p + 2 * K, *roll = p + 3 * K, *pitch = p + 4 * K, *yaw = p + 5 * K;
+  const double s = std::sin(yaw[a]), c = std::cos(yaw[a]);
+  for (int k = 0; k < K; ++k) {
+    mcl_swath_offset o;
+    const double u = x[k] - x[a], w = y[k] - y[a];
+    const double cu = c * u, sw = s * w, cw = c * w, su = s * u;
+    o.dx = cu + sw;
+    o.dy = cw - su;
+    o.dz = z[k] - z[a];
+    o.roll = roll[k];
+    o.pitch = pitch[k];
+    const double t = yaw[k] - yaw[a];
+    o.dyaw = swath_wrap(t);
+    if (k == a) o.dx = o.dy = o.dz = o.dyaw = 0.0;   // (the differences are +0.0 already; c * 0 + s * 0 may be -0.0)
+    out[k] = o;
+  }
   return MCL_OK;
 }
 

@@ -7,7 +7,8 @@
 //     evaluation      : every lane reads the pose to evaluate out of LDS; in every wave the lanes 0 ... 2 D build its
 //                       1 + 2 D sensor frames (variant v = lane: one fp64 addition on the stored number, then lane_frame --
 //                       one round of sincos) and the other lanes read them with lane_frame_of.  A lane casts its beam from
-//                       each frame with cast_from_frame<MAP> -- one loop, one copy of the cast -- and keeps the nineteen
+//                       each frame with cast_from_frame<MAP> -- one loop, one copy of the cast: match_beam, the per-beam
+//                       body k_swath_match (csrc/mcl_swath.h) runs too -- and keeps the nineteen
 //                       integers of a record in registers over its rounds; then they go through wave_sum into one LDS row
 //                       per wave.
 //     decision        : after a barrier thread 0 (match_decide, fp contract off, the functions the host exports:
@@ -145,6 +146,72 @@ __device__ __forceinline__ void match_decide(const MatchArgs& a, MatchBlock& blk
   blk.go = status < 0 ? 1 : 0;
 }
 
+// One beam of one evaluation, shared by k_ping_match and k_swath_match (csrc/mcl_swath.h): the beam record bt cast from the
+// 1 + 2 D frames the wave's lanes 0 ... 2 D hold in F, and what it adds to the lane's nineteen words.  Every lane of the wave
+// calls it (lane_frame_of reads across the wave); cast: this lane has a counting beam.  dump: nullptr, or where the
+// lane's range of variant 0 goes, variant v at dump[v B].
+template <int MAP, int D>
+__device__ __forceinline__ void match_beam(const MbesArgs& m, const LaneFrame& F, const float4& bt, bool cast, long long jump_q,
+                                           float* dump, size_t B, long long (&acc)[MATCH_WORDS]) {
+  constexpr int NV = 1 + 2 * D;
+  double v[3];
+  beam_in_vehicle(m, bt, v);
+  float e0 = 0.f, ep = 0.f;
+  long long d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+  bool miss = false;
+#pragma unroll 1
+  for (int var = 0; var < NV; ++var) {
+    const LaneFrame U = lane_frame_of(F, var);
+    float e = 0.f;
+    if (cast) {
+      e = cast_from_frame<MAP>(m, U, v);
+      miss = miss || e == m.r_max;
+      if (dump) dump[(size_t)var * B] = e;
+    }
+    if (var == 0) {
+      e0 = e;
+    } else if (var & 1) {
+      ep = e;
+    } else {
+      const long long d = info_difference(ep, e);
+      if (var == 2)
+        d0 = d;
+      else if (var == 4)
+        d1 = d;
+      else if (var == 6)
+        d2 = d;
+      else
+        d3 = d;
+    }
+  }
+  const long long a0 = d0 < 0 ? -d0 : d0, a1 = d1 < 0 ? -d1 : d1, a2 = d2 < 0 ? -d2 : d2, a3 = d3 < 0 ? -d3 : d3;
+  const bool jump = cast && !miss && (a0 > jump_q || a1 > jump_q || a2 > jump_q || a3 > jump_q);
+  acc[0] += cast ? 1 : 0;
+  acc[1] += cast && miss ? 1 : 0;
+  acc[2] += jump ? 1 : 0;
+  if (cast && !miss && !jump) {
+    const long long rho = innov_quantise(bt.w, e0);
+    acc[3] += d0 * d0;
+    acc[4] += d1 * d0;
+    acc[5] += d1 * d1;
+    acc[6] += d2 * d0;
+    acc[7] += d2 * d1;
+    acc[8] += d2 * d2;
+    if constexpr (D == 4) {
+      acc[9] += d3 * d0;
+      acc[10] += d3 * d1;
+      acc[11] += d3 * d2;
+      acc[12] += d3 * d3;
+      acc[16] += d3 * rho;
+    }
+    acc[13] += d0 * rho;
+    acc[14] += d1 * rho;
+    acc[15] += d2 * rho;
+    acc[17] += rho;
+    acc[18] += rho * rho;
+  }
+}
+
 template <int MAP, int D>
 __global__ void __launch_bounds__(BEAM_CHUNK) k_ping_match(MatchArgs a) {
   static_assert(D == 3 || D == 4, "x, y, yaw and perhaps z");
@@ -156,7 +223,6 @@ __global__ void __launch_bounds__(BEAM_CHUNK) k_ping_match(MatchArgs a) {
   const long long i = blockIdx.x;
   const int T = a.cfg.max_iter + 1;
   const size_t B = (size_t)a.n_beams;
-  const float r_max = m.r_max;
   const double roll = m.st[3][i], pitch = m.st[4][i];
   const double dxy = a.cfg.steps.delta_xy, dyaw = a.cfg.steps.delta_yaw;
   MatchLane0 st = {0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
@@ -182,68 +248,14 @@ __global__ void __launch_bounds__(BEAM_CHUNK) k_ping_match(MatchArgs a) {
     long long acc[MATCH_WORDS];
 #pragma unroll
     for (int f = 0; f < MATCH_WORDS; ++f) acc[f] = 0;
+    float* dump = a.ranges_out ? a.ranges_out + ((size_t)i * (size_t)T + (size_t)t) * NV * B : nullptr;
     for (int b0 = 0; b0 < a.n_beams; b0 += (int)blockDim.x) {
       const int b = b0 + tid;
       const bool have = b < a.n_beams;
       const float4 bt = have ? a.beam[b] : make_float4(0.f, 0.f, -1.f, 0.f);
       const bool cast = have && beam_valid(bt.w);
       if (__ballot(cast) == 0ull) continue;   // (a wave without a counting beam this round; no barrier inside the rounds)
-      double v[3];
-      beam_in_vehicle(m, bt, v);
-      float e0 = 0.f, ep = 0.f;
-      long long d0 = 0, d1 = 0, d2 = 0, d3 = 0;
-      bool miss = false;
-#pragma unroll 1
-      for (int var = 0; var < NV; ++var) {
-        const LaneFrame U = lane_frame_of(F, var);
-        float e = 0.f;
-        if (cast) {
-          e = cast_from_frame<MAP>(m, U, v);
-          miss = miss || e == r_max;
-          if (a.ranges_out) a.ranges_out[(((size_t)i * (size_t)T + (size_t)t) * NV + (size_t)var) * B + (size_t)b] = e;
-        }
-        if (var == 0) {
-          e0 = e;
-        } else if (var & 1) {
-          ep = e;
-        } else {
-          const long long d = info_difference(ep, e);
-          if (var == 2)
-            d0 = d;
-          else if (var == 4)
-            d1 = d;
-          else if (var == 6)
-            d2 = d;
-          else
-            d3 = d;
-        }
-      }
-      const long long a0 = d0 < 0 ? -d0 : d0, a1 = d1 < 0 ? -d1 : d1, a2 = d2 < 0 ? -d2 : d2, a3 = d3 < 0 ? -d3 : d3;
-      const bool jump = cast && !miss && (a0 > a.jump_q || a1 > a.jump_q || a2 > a.jump_q || a3 > a.jump_q);
-      acc[0] += cast ? 1 : 0;
-      acc[1] += cast && miss ? 1 : 0;
-      acc[2] += jump ? 1 : 0;
-      if (cast && !miss && !jump) {
-        const long long rho = innov_quantise(bt.w, e0);
-        acc[3] += d0 * d0;
-        acc[4] += d1 * d0;
-        acc[5] += d1 * d1;
-        acc[6] += d2 * d0;
-        acc[7] += d2 * d1;
-        acc[8] += d2 * d2;
-        if constexpr (D == 4) {
-          acc[9] += d3 * d0;
-          acc[10] += d3 * d1;
-          acc[11] += d3 * d2;
-          acc[12] += d3 * d3;
-          acc[16] += d3 * rho;
-        }
-        acc[13] += d0 * rho;
-        acc[14] += d1 * rho;
-        acc[15] += d2 * rho;
-        acc[17] += rho;
-        acc[18] += rho * rho;
-      }
+      match_beam<MAP, D>(m, F, bt, cast, a.jump_q, dump ? dump + b : nullptr, B, acc);
     }
     // ---- the wave's record into its LDS row (all 64 lanes are here: the workgroup is whole waves)
 #pragma unroll

@@ -299,6 +299,8 @@ MATCH_DERIVED = np.dtype(_lib.MATCH_DERIVED_FIELDS)
 MATCH_CONVERGED, MATCH_MAX_ITER, MATCH_STALLED, MATCH_NO_OVERLAP = 0, 1, 2, 3
 MATCH_STATUS_NAMES = ('CONVERGED', 'MAX_ITER', 'STALLED', 'NO_OVERLAP')
 MATCH_MAX_DUMP = 1 << 26
+SwathOffset = np.dtype(_lib.SWATH_OFFSET_FIELDS)
+SWATH_MAX_PINGS, SWATH_MAX_BEAMS = 64, 16384
 
 
 def make_match_config(r_max, fit_z=False, max_iter=12, min_beams=8, grad_floor_q=2, step_max_xy=2.0, step_max_yaw=0.1,
@@ -318,8 +320,9 @@ class PingMatch(object):
     start_rms of the start's, the config, and with trace=True `trace` (M x (max_iter + 1) records of MATCH_TRACE), with
     dump=True `ranges` (M x (max_iter + 1) x (1 + 2 D) x B, NaN where nothing was cast)."""
 
-    def __init__(self, results, cfg, sigma, trace=None, ranges=None):
+    def __init__(self, results, cfg, sigma, trace=None, ranges=None, derive=None):
         self.results, self.cfg, self.sigma, self.trace, self.ranges = results, cfg, float(sigma), trace, ranges
+        self._derive = derive if derive is not None else match_derived   # (Engine.match_swath: swath_derived)
         self.status = results['status'].copy()
         self.m, self.rms, self.mean = self._residuals(results['final'])
         self.start_rms = self._residuals(results['start'])[1]
@@ -348,8 +351,8 @@ class PingMatch(object):
                     status=MATCH_STATUS_NAMES[int(r['status'])], rms=float(self.rms[i]), evaluations=int(r['evaluations']))
 
     def derived(self, i):
-        """mcl_match_derived of fix i's final record"""
-        return match_derived(self.results['final'][i], self.cfg, self.sigma)
+        """mcl_match_derived (a swath's fix: mcl_swath_derived) of fix i's final record"""
+        return self._derive(self.results['final'][i], self.cfg, self.sigma)
 
     def cov(self, i):
         """the covariance of fix i over (x, y, yaw[, z]): sigma^2 A^-1, D x D; inf on the diagonal of a dead dimension"""
@@ -938,6 +941,47 @@ class Engine(object):
         match = self.match_ping(np.stack(starts, axis=1), ranges, beam_angles, sigma, r_max, sensor_offset, **kw)
         return match, match.best()
 
+    # ---- swath matching: where the last K pings, rigidly tied by dead reckoning, say the vehicle is (include/mcl_swath.h)
+    def match_swath(self, poses, ranges, beam_angles, offsets, sigma, r_max, sensor_offset=None, fit_z=False, max_iter=12,
+                    trace=False, dump=False, cfg=None, **config):
+        """the Levenberg-Marquardt fix of the ANCHOR of a swath from each of M start poses (6 x M as for match_ping; their
+        roll and pitch are not read): ranges K x B, offsets K records of SwathOffset (swath_offsets makes them) -- a
+        PingMatch whose derived quantities go through mcl_swath_derived and whose dump is M x (max_iter + 1) x K x
+        (1 + 2 D) x B.  Needs a map, no particles; nothing of the filter is read or written."""
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(6, -1))
+        a, so = _f32(beam_angles).reshape(-1), _f64(sensor_offset)
+        off = np.ascontiguousarray(offsets, dtype=SwathOffset).reshape(-1)
+        K = off.size
+        r = _f32(ranges).reshape(-1)
+        if r.size != K * a.size:
+            raise ValueError('match_swath: %d ranges for %d pings of %d beam angles' % (r.size, K, a.size))
+        c = cfg if cfg is not None else make_match_config(r_max, fit_z, max_iter, **config)
+        M, T, nv = p.shape[1], max(int(c.max_iter), 0) + 1, 1 + 2 * int(c.dims)
+        res = np.zeros(max(M, 1), MATCH_RESULT)
+        tr = np.zeros((max(M, 1), T), MATCH_TRACE) if trace else None
+        floats = max(M, 1) * T * max(K, 1) * max(nv, 1) * max(a.size, 1)
+        # (a dump beyond the limit: the library refuses it before it writes; one float stands in for the buffer)
+        rng = np.full(floats if floats <= MATCH_MAX_DUMP else 1, np.nan, np.float32) if dump else None
+        self._ck(self.lib.mcl_match_swath(self.h, _ptr(p), M, _ptr(r), _ptr(a), a.size, _ptr(off), K, float(sigma), float(r_max),
+                                          _ptr(so), C.byref(c), _ptr(res), _ptr(tr), _ptr(rng)))
+        if rng is not None:
+            rng = rng.reshape(M, T, K, nv, a.size)
+        return PingMatch(res[:M], c, sigma, tr, rng, derive=swath_derived)
+
+    def match_swath_estimate(self, ranges, beam_angles, offsets, sigma, r_max, sensor_offset=None, modes=0, mode_cell=2.0,
+                             mode_n_yaw=36, start=None, **kw):
+        """match_swath from the cloud's mean pose (start: a pose of 6 instead), plus up to `modes` peaks of pose_modes:
+        returns (PingMatch, index of its best fix or None)"""
+        if start is None:
+            mean, yaw, _ = self.mean_cov()
+            start = np.array(mean, np.float64)
+            start[5] = yaw
+        starts = [np.asarray(start, np.float64).reshape(6)]
+        if modes > 0:
+            starts += [m.mean for m in self.pose_modes(mode_cell, mode_n_yaw, int(modes))[0]]
+        match = self.match_swath(np.stack(starts, axis=1), ranges, beam_angles, offsets, sigma, r_max, sensor_offset, **kw)
+        return match, match.best()
+
     def set_landmarks(self, xyz):
         a = _f64(xyz)
         self._ck(self.lib.mcl_set_landmarks(self.h, _ptr(a), a.shape[0]))
@@ -1416,6 +1460,44 @@ def match_derived(rec, cfg, sigma):
     """the derived quantities of a record (mcl_match_derived: host arithmetic) as one record of MATCH_DERIVED"""
     r, out = _match_record(rec), np.zeros(1, MATCH_DERIVED)
     _lib.check(_lib.load().mcl_match_derived(_ptr(r), C.byref(cfg), float(sigma), _ptr(out)))
+    return out[0]
+
+
+def swath_offsets(poses6, anchor=-1):
+    """mcl_swath_offsets (host arithmetic): the K records of SwathOffset of the vehicle's poses at the K pings (6 x K: x, y,
+    z, roll, pitch, yaw; dead reckoning will do) relative to column `anchor` (-1: the last)"""
+    p = np.ascontiguousarray(np.asarray(poses6, np.float64).reshape(6, -1))
+    out = np.zeros(max(p.shape[1], 1), SwathOffset)
+    _lib.check(_lib.load().mcl_swath_offsets(_ptr(p), p.shape[1], int(anchor), _ptr(out)))
+    return out[:p.shape[1]]
+
+
+def swath_check(K, B, offsets):
+    """None when mcl_match_swath would accept the swath's shape and offsets, else the rule that is broken"""
+    off = None if offsets is None else np.ascontiguousarray(offsets, dtype=SwathOffset).reshape(-1)
+    why = C.c_char_p()
+    rc = _lib.load().mcl_swath_check(int(K), int(B), _ptr(off), C.byref(why))
+    return None if rc == 0 else (why.value or b'').decode()
+
+
+def swath_solve(rec, cfg, j):
+    """match_solve for the record of a swath (mcl_swath_solve: n up to 16384)"""
+    r, d, dead = _match_record(rec), np.zeros(4), C.c_int32(0)
+    _lib.check(_lib.load().mcl_swath_solve(_ptr(r), C.byref(cfg), int(j), _ptr(d), C.byref(dead)))
+    return d, int(dead.value)
+
+
+def swath_better(q, p, min_beams):
+    """match_better for the records of a swath (mcl_swath_better)"""
+    a, b, out = _match_record(q), _match_record(p), C.c_int32(0)
+    _lib.check(_lib.load().mcl_swath_better(_ptr(a), _ptr(b), int(min_beams), C.byref(out)))
+    return bool(out.value)
+
+
+def swath_derived(rec, cfg, sigma):
+    """match_derived for the record of a swath (mcl_swath_derived) as one record of MATCH_DERIVED"""
+    r, out = _match_record(rec), np.zeros(1, MATCH_DERIVED)
+    _lib.check(_lib.load().mcl_swath_derived(_ptr(r), C.byref(cfg), float(sigma), _ptr(out)))
     return out[0]
 
 

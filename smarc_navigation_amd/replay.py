@@ -330,23 +330,34 @@ def information_summary(log):
     return out
 
 
+def _fix_log_summary(prefix, log, truth_xy):
+    """the summary keys of a log of pose fixes (match_log, swath_log: one row per call: stamp, status, x, y, yaw, rms,
+    evaluations, and the published pose x, y, yaw the fix started from), named prefix_*"""
+    ok = np.array([r[1] == 'CONVERGED' for r in log], dtype=bool)
+    rms = np.array([r[5] for r in log], dtype=np.float64)
+    out = {prefix + '_calls': len(log), prefix + '_converged_share': float(ok.mean()) if len(log) else 0.0,
+           prefix + '_rms_residual_median': float(np.median(rms[ok])) if ok.any() else None,
+           prefix + '_rmse_xy': None, prefix + '_filter_rmse_xy': None}
+    if truth_xy is not None and ok.any():
+        t = np.asarray(truth_xy, dtype=np.float64)[ok]
+        fix = np.array([[r[2], r[3]] for r in log], dtype=np.float64)[ok]
+        own = np.array([[r[7], r[8]] for r in log], dtype=np.float64)[ok]
+        out[prefix + '_rmse_xy'], out[prefix + '_filter_rmse_xy'] = pose_rmse(fix, t), pose_rmse(own, t)
+    return out
+
+
 def match_summary(log, truth_xy=None):
     """what a node with mbes_match_every > 0 adds to a summary, from its match_log (one row per call: stamp, status, x, y,
     yaw, rms, evaluations, and the published pose x, y, yaw the fix started from): the calls, the share of them that
     converged, the median rms residual of the converged fixes (metres) and -- with truth_xy, the stream's truth at the
     pings of the calls -- the RMSE of the converged fixes against it, beside the filter's own at the same pings"""
-    out = dict(match_calls=len(log))
-    ok = np.array([r[1] == 'CONVERGED' for r in log], dtype=bool)
-    out['match_converged_share'] = float(ok.mean()) if len(log) else 0.0
-    rms = np.array([r[5] for r in log], dtype=np.float64)
-    out['match_rms_residual_median'] = float(np.median(rms[ok])) if ok.any() else None
-    out['match_rmse_xy'] = out['match_filter_rmse_xy'] = None
-    if truth_xy is not None and ok.any():
-        t = np.asarray(truth_xy, dtype=np.float64)[ok]
-        fix = np.array([[r[2], r[3]] for r in log], dtype=np.float64)[ok]
-        own = np.array([[r[7], r[8]] for r in log], dtype=np.float64)[ok]
-        out['match_rmse_xy'], out['match_filter_rmse_xy'] = pose_rmse(fix, t), pose_rmse(own, t)
-    return out
+    return _fix_log_summary('match', log, truth_xy)
+
+
+def swath_summary(log, truth_xy=None):
+    """what a node with mbes_swath_pings > 0 adds to a summary, from its swath_log (rows as match_log's): match_summary's
+    figures as swath_calls, swath_converged_share, swath_rms_residual_median, swath_rmse_xy beside swath_filter_rmse_xy"""
+    return _fix_log_summary('swath', log, truth_xy)
 
 
 def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, publish_every=5, smooth_lag=0,
@@ -360,7 +371,8 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
     ping is first held against the cloud (Engine.ping_innovation, include/mcl_innovation.h; nothing of the filter changes)
     and the summary gains innovation_summary's keys: what to tune the node's mbes_std with.  A node with mbes_gate_nis > 0
     adds gate_pings, gate_n_gated, gate_inconsistent; one with mbes_information_every > 0 adds information_summary's keys.
-    One with mbes_match_every > 0 adds match_summary's keys (the fixes of include/mcl_match.h against the stream's truth).
+    One with mbes_match_every > 0 adds match_summary's keys (the fixes of include/mcl_match.h against the stream's truth),
+    one with mbes_swath_pings > 0 swath_summary's (include/mcl_swath.h).
     A stream that carries its map (map_z, map_origin, map_res) is replayed over it when neither grid nor mesh is given."""
     from . import auv_pf as node
     from . import msgs
@@ -375,7 +387,7 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
     if mesh is not None:
         pf.set_map_mesh(mesh['verts'], mesh['tris'])
     n = len(stream['stamp'])
-    inn_nis, inn_nu, n_inconsistent, match_at = [], [], 0, []
+    inn_nis, inn_nu, n_inconsistent, match_at, swath_at = [], [], 0, [], []
     pf.start_timing(float(stream['t0']) if 't0' in stream else float(stream['stamp'][0]) - 0.02)
     gps_at = {int(k): j for j, k in enumerate(stream['gps_idx'])} if 'gps_idx' in stream else {}
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])} if 'mbes_idx' in stream else {}
@@ -420,10 +432,12 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
                                                    pf.mbes_std, float(scan.range_max), pf.mbes_sensor_offset)
                 inn_nis.append(np.where(inn.valid, inn.nis, np.nan))
                 inn_nu.append(np.where(inn.valid, inn.nu, np.nan))
-            calls, matched = pf.gate_calls, pf.match_calls
+            calls, matched, swathed = pf.gate_calls, pf.match_calls, pf.swath_calls
             pf.mbes_cb(scan)
             if pf.match_calls > matched:
                 match_at.append(k)
+            if pf.swath_calls > swathed:
+                swath_at.append(k)
             if pf.gate_calls > calls and pf.last_innovation.inconsistent:
                 n_inconsistent += 1
         while next_fix < len(fixes) and fixes[next_fix][0] <= stream['stamp'][k]:
@@ -485,6 +499,10 @@ def replay(stream, params=None, m2o=None, utm2map=None, grid=None, mesh=None, pu
         # ping matching (include/mcl_match.h): where every K-th ping alone says the vehicle is, against the stream's truth
         summary['mbes_match_every'] = int(pf.mbes_match_every)
         summary.update(match_summary(pf.match_log, np.asarray(stream['truth_xyz'])[match_at][:, :2] if 'truth_xyz' in stream else None))
+    if pf.mbes_swath_pings > 0:
+        # swath matching (include/mcl_swath.h): where the last K pings together say the vehicle is, against the stream's truth
+        summary['mbes_swath_pings'], summary['mbes_swath_every'] = int(pf.mbes_swath_pings), int(pf.mbes_swath_every)
+        summary.update(swath_summary(pf.swath_log, np.asarray(stream['truth_xyz'])[swath_at][:, :2] if 'truth_xyz' in stream else None))
     summary['pf_distance'], summary['pf_final'] = track_metrics(pf_xyz.T)
     for name in ('dr_xyz', 'truth_xyz'):
         if name in stream:
@@ -725,6 +743,12 @@ def main(argv=None):
                          'ping alone to the map from the published pose (include/mcl_match.h); nothing is fed back; the summary '
                          'gains match_calls, match_converged_share, match_rmse_xy (against the stream\'s truth, beside the '
                          'filter\'s own match_filter_rmse_xy) and match_rms_residual_median; plain stream replay only; 0: off')
+    ap.add_argument('--swath', type=int, nargs='+', default=None, metavar='K',
+                    help='--swath K [EVERY]: the node\'s mbes_swath_pings and mbes_swath_every: after the update of every EVERY-th '
+                         'ping (default: every ping) fit the last K pings, tied by the odometry, to the map as one rigid set from the '
+                         'published pose (include/mcl_swath.h); nothing is fed back; the summary gains swath_calls, '
+                         'swath_converged_share, swath_rmse_xy (beside the filter\'s own swath_filter_rmse_xy) and '
+                         'swath_rms_residual_median -- with --match, match_rmse_xy stands beside them; plain stream replay only')
     ap.add_argument('--mbes-every', type=int, default=0, metavar='K',
                     help='synthetic streams: a multibeam ping every K samples over a synthetic map the stream carries')
     ap.add_argument('--outliers', type=float, nargs=2, default=None, metavar=('FRACTION', 'SHORTEN_M'),
@@ -794,6 +818,9 @@ def main(argv=None):
         ap.error('--information: EVERY >= 0, and only with the plain stream replay')
     if a.match < 0 or (a.match > 0 and (a.bag or a.recover)):
         ap.error('--match: EVERY >= 0, and only with the plain stream replay')
+    if a.swath is not None and (len(a.swath) > 2 or a.swath[0] < 1 or a.swath[0] > 64 or (len(a.swath) == 2 and a.swath[1] < 1)
+                                or a.bag or a.recover):
+        ap.error('--swath K [EVERY]: 1 <= K <= 64, EVERY >= 1, and only with the plain stream replay')
     if a.sigma is not None and not (a.sigma > 0.0 and np.isfinite(a.sigma)):
         ap.error('--sigma must be finite and > 0')
     if (a.mbes_every != 0 or a.outliers is not None) and not synthetic:
@@ -863,6 +890,8 @@ def main(argv=None):
         params.update(mbes_information_every=a.information)
     if a.match > 0:
         params.update(mbes_match_every=a.match)
+    if a.swath is not None:
+        params.update(mbes_swath_pings=a.swath[0], mbes_swath_every=a.swath[1] if len(a.swath) == 2 else 1)
     if a.sigma is not None:
         params.update(mbes_std=a.sigma)
     if a.regularise > 0:

@@ -13,7 +13,10 @@ share of the posterior about every published pose (include/mcl_quantile.h); `~mb
 ping that the cloud cannot explain invalid before the MBES update (include/mcl_innovation.h); `~mbes_information_every`
 K > 0 logs what every K-th ping can tell the cloud: the one-ping Cramer-Rao bounds and the direction the terrain cannot fix
 (include/mcl_information.h); `~mbes_match_every` K > 0 fits every K-th ping alone to the map after its update, from the
-published pose, and logs where that ping says the vehicle is -- nothing is fed back into the filter (include/mcl_match.h).
+published pose, and logs where that ping says the vehicle is -- nothing is fed back into the filter (include/mcl_match.h);
+`~mbes_swath_pings` K > 0 keeps the last K pings with the odometry pose of each and, after the update of every
+`~mbes_swath_every`-th ping (default 1), fits them to the map as one rigid set anchored at the newest -- what one ping cannot
+tell apart, the along-track position and depth, K pings can; nothing is fed back either (include/mcl_swath.h).
 
 ROS is not installed in the build container: the module imports whatever `rospy` / `tf` / `tf2_ros` / `*_msgs` are on
 the path -- a ROS 1 installation, or the stand-ins of tests/ros_stubs that tests/test_ros_node_stub.py drives main()
