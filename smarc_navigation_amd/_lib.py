@@ -1,6 +1,6 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
 mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h, mcl_innovation.h,
-mcl_information.h, mcl_match.h and mcl_swath.h).
+mcl_information.h, mcl_match.h, mcl_swath.h and mcl_reseed.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -155,6 +155,17 @@ MATCH_DERIVED_FIELDS = [('rms', '<f8'), ('mean', '<f8'), ('chi2', '<f8'), ('J', 
 
 # mcl_swath_offset (include/mcl_swath.h; 48 bytes) travels as a numpy record array (engine.SwathOffset is the dtype)
 SWATH_OFFSET_FIELDS = [('dx', '<f8'), ('dy', '<f8'), ('dz', '<f8'), ('roll', '<f8'), ('pitch', '<f8'), ('dyaw', '<f8')]
+
+# mcl_reseed_component (include/mcl_reseed.h; 80 bytes) travels as a numpy record array (engine.ReseedComponent is the dtype)
+RESEED_COMPONENT_FIELDS = [('mean', '<f8', (3,)), ('chol', '<f8', (6,)), ('mass', '<u4'), ('reserved', '<u4')]
+
+
+class ReseedSelectConfig(C.Structure):
+    """mcl_reseed_select_config (include/mcl_reseed.h)"""
+    _fields_ = [('max_components', C.c_int32), ('min_beams', C.c_int32), ('max_rms', C.c_double), ('sep_xy', C.c_double),
+                ('sep_yaw', C.c_double), ('cov_scale', C.c_double), ('add_std_xy', C.c_double), ('add_std_yaw', C.c_double),
+                ('dead_std_xy', C.c_double), ('dead_std_yaw', C.c_double)]
+
 
 # mcl_information_sums (72 bytes) and mcl_information_result (104 bytes) travel as numpy record arrays
 INFORMATION_SUMS_FIELDS = [('n', '<i8'), ('n_miss', '<i8'), ('n_jump', '<i8'), ('sxx', '<u8'), ('syy', '<u8'), ('sww', '<u8'),
@@ -370,6 +381,15 @@ SWATH_SYMBOLS = {
     'mcl_match_swath': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _d, _d, _vp, C.POINTER(MatchConfig), _vp, _vp, _vp]),
 }
 
+# include/mcl_reseed.h: sensor resetting, particles injected from a mixture of Gaussians at the fixes of a match
+RESEED_SYMBOLS = {
+    'mcl_reseed_select_check': (C.c_int, [C.POINTER(ReseedSelectConfig), C.POINTER(C.c_char_p)]),
+    'mcl_reseed_components_check': (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p)]),
+    'mcl_reseed_select': (C.c_int, [_vp, _i64, C.POINTER(MatchConfig), _d, C.POINTER(ReseedSelectConfig), _vp, _vp,
+                                    C.POINTER(C.c_int32)]),
+    'mcl_inject_gaussian': (C.c_int, [_vp, _d, _vp, _i32, _vp, C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -387,7 +407,7 @@ def load():
                               list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
                               list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items()) +
                               list(INNOVATION_SYMBOLS.items()) + list(INFORMATION_SYMBOLS.items()) +
-                              list(MATCH_SYMBOLS.items()) + list(SWATH_SYMBOLS.items())):
+                              list(MATCH_SYMBOLS.items()) + list(SWATH_SYMBOLS.items()) + list(RESEED_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

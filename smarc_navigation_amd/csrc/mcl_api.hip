@@ -20,6 +20,7 @@
 #include "mcl_host_match.h"
 #include "mcl_host_swath.h"
 #include "mcl_host_recovery.h"
+#include "mcl_host_reseed.h"
 #include "mcl_host_modes.h"
 
 // dead-reckoning integrator (host only; uses euler_from_quat above)
@@ -1460,6 +1461,31 @@ int mcl_match_swath(mcl_handle* h, const double* poses, int64_t M, const float* 
   if (!results_out) return fail(h, MCL_ERR_INVALID, "match_swath: null argument");
   const Swath s = {{ranges, beam_angles, B, sigma, r_max, sensor_offset, cfg}, offsets, K};
   return swath_run(h, s, poses, M, results_out, trace_out, ranges_out);
+}
+
+// ---- sensor resetting (include/mcl_reseed.h; host: mcl_host_reseed.h, kernel: csrc/mcl_reseed.h)
+int mcl_reseed_select_check(const mcl_reseed_select_config* cfg, const char** reason) {
+  return reseed_select_check_impl(cfg, reason);
+}
+
+int mcl_reseed_components_check(const mcl_reseed_component* comps, int32_t n_comp, const char** reason) {
+  return reseed_components_check_impl(comps, n_comp, reason);
+}
+
+int mcl_reseed_select(const mcl_match_result* results, int64_t M, const mcl_match_config* mcfg, double sigma,
+                      const mcl_reseed_select_config* cfg, mcl_reseed_component* comps_out, int64_t* index_out,
+                      int32_t* n_out) {
+  return reseed_select_impl(results, M, mcfg, sigma, cfg, comps_out, index_out, n_out);
+}
+
+int mcl_inject_gaussian(mcl_handle* h, double fraction, const mcl_reseed_component* comps, int32_t n_comp,
+                        const double* replay, int64_t* n_injected) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!comps) return fail(h, MCL_ERR_INVALID, "inject_gaussian: null components");
+  if (!(fraction >= 0.0 && fraction <= 1.0)) return fail(h, MCL_ERR_INVALID, "inject_gaussian: fraction outside [0, 1]");
+  if (h->have_lw) return fail(h, MCL_ERR_STATE, "inject_gaussian: log-weights pending (resample first: they describe the particles as they are)");
+  RET_IF(set_device(h));
+  return reseed_inject(h, fraction, comps, n_comp, replay, n_injected);
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

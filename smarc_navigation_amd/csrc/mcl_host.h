@@ -210,10 +210,11 @@ struct mcl_handle {
   bool have_lw = false, have_cdf = false, have_meancov = false;
   uint32_t step_predict = 0, step_resample = 0;
   // global localisation / recovery (include/mcl_recovery.h)
-  uint32_t step_inject = 0;       // Philox step of the next mcl_inject_uniform; reset by both init calls
+  uint32_t step_inject = 0;       // Philox step of the next mcl_inject_uniform / mcl_inject_gaussian; reset by both init calls
   double map_xy[4] = {0, 0, 0, 0};  // footprint of the map (x_min, x_max, y_min, y_max; MAP frame), valid while map_kind >= 0
   DevBuf<double> wstats_dev;   // weight statistics: WS_OUT_WORDS result words, then one 32-byte record per tile (lazily)
   DevBuf<u64> inject_cnt;      // injection: the replaced-particle total, then one count per workgroup (lazily)
+  DevBuf<double> reseed_tab;   // sensor resetting (include/mcl_reseed.h): the component table of csrc/mcl_reseed.h, RESEED_TAB_WORDS (lazily)
   DevBuf<u64> temper_dev;      // tempering (include/mcl_temper.h): the state block of csrc/mcl_temper.h, TP_WORDS (lazily)
   // dominant modes (include/mcl_modes.h; all lazily)
   bool have_state = false;     // the particles were initialised (either init call, mcl_set_particles)

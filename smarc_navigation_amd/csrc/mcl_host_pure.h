@@ -9,7 +9,8 @@
 // start and bin choice of mcl_cloud_quantiles (include/mcl_quantile.h; the kernels run the same functions), and the
 // quantised residual, sample, merge and gate of mcl_ping_innovation (include/mcl_innovation.h), and the quantised
 // difference, steps, merge and matrix of mcl_ping_information (include/mcl_information.h), and the compare, solve, checks
-// and derived quantities of mcl_match_ping (include/mcl_match.h; its kernel runs the first two).  No HIP header: the
+// and derived quantities of mcl_match_ping (include/mcl_match.h; its kernel runs the first two), and the checks, the rank
+// and the selection of mcl_reseed.h (its kernel runs the rank).  No HIP header: the
 // translation unit mcl_api.hip includes it through mcl_host.h, and `make host-asan` compiles it -- with mcl_dr_impl.h and
 // the node's core -- under AddressSanitizer / UBSan / ThreadSanitizer with plain g++ (the reference is racy
 // by construction, auv_pf.py:126,202-211,264-285; GPU sanitizers are not available on this pool).
@@ -34,6 +35,7 @@
 #include "../../include/mcl_information.h"
 #include "../../include/mcl_match.h"
 #include "../../include/mcl_swath.h"
+#include "../../include/mcl_reseed.h"
 
 namespace {
 
@@ -1186,6 +1188,123 @@ int swath_offsets_impl(const double* p, int K, int anchor, mcl_swath_offset* out
     if (k == a) o.dx = o.dy = o.dz = o.dyaw = 0.0;   // (the differences are +0.0 already; c * 0 + s * 0 may be -0.0)
     out[k] = o;
   }
+  return MCL_OK;
+}
+
+// ---- sensor resetting (include/mcl_reseed.h): the rules of a component table and of the selection config, the component
+// a 53-bit draw picks, and the selection of a mixture from match results.
+inline const char* reseed_select_why(const mcl_reseed_select_config* c) {
+  if (!c) return "null config";
+  if (c->max_components < 1 || c->max_components > MCL_RESEED_MAX_COMPONENTS) return "max_components outside 1 ... 256";
+  if (c->min_beams < 1) return "min_beams must be >= 1";
+  if (!std::isfinite(c->max_rms) || c->max_rms < 0.0) return "max_rms must be finite and >= 0";
+  if (!std::isfinite(c->sep_xy) || c->sep_xy < 0.0 || !std::isfinite(c->sep_yaw) || c->sep_yaw < 0.0) return "sep_xy and sep_yaw must be finite and >= 0";
+  if (!std::isfinite(c->cov_scale) || !(c->cov_scale > 0.0)) return "cov_scale must be finite and > 0";
+  if (!std::isfinite(c->add_std_xy) || c->add_std_xy < 0.0 || !std::isfinite(c->add_std_yaw) || c->add_std_yaw < 0.0)
+    return "add_std_xy and add_std_yaw must be finite and >= 0";
+  if (!std::isfinite(c->dead_std_xy) || !(c->dead_std_xy > 0.0) || !std::isfinite(c->dead_std_yaw) || !(c->dead_std_yaw > 0.0))
+    return "dead_std_xy and dead_std_yaw must be finite and > 0";
+  return nullptr;
+}
+int reseed_select_check_impl(const mcl_reseed_select_config* cfg, const char** reason) {
+  const char* why = reseed_select_why(cfg);
+  if (reason) *reason = why;
+  return why ? MCL_ERR_INVALID : MCL_OK;
+}
+// the table of mcl_inject_gaussian; total (or nullptr): W, the sum of the masses
+inline const char* reseed_components_why(const mcl_reseed_component* comps, int n_comp, uint64_t* total) {
+  if (!comps) return "null components";
+  if (n_comp < 1 || n_comp > MCL_RESEED_MAX_COMPONENTS) return "n_comp outside 1 ... 256";
+  uint64_t W = 0;
+  for (int c = 0; c < n_comp; ++c) {
+    const mcl_reseed_component& k = comps[c];
+    for (int r = 0; r < 3; ++r)
+      if (!std::isfinite(k.mean[r])) return "a mean is not finite";
+    for (int r = 0; r < 6; ++r)
+      if (!std::isfinite(k.chol[r])) return "a factor entry is not finite";
+    if (k.chol[0] < 0.0 || k.chol[2] < 0.0 || k.chol[5] < 0.0) return "a diagonal of the factor is negative";
+    W += k.mass;
+  }
+  if (W == 0) return "the masses add up to 0";
+  if (W > (1ull << 31)) return "the masses add up to more than 2^31";
+  if (total) *total = W;
+  return nullptr;
+}
+int reseed_components_check_impl(const mcl_reseed_component* comps, int n_comp, const char** reason) {
+  const char* why = reseed_components_why(comps, n_comp, nullptr);
+  if (reason) *reason = why;
+  return why ? MCL_ERR_INVALID : MCL_OK;
+}
+// r = (t W) >> 53 of the 128-bit product (t < 2^53, W <= 2^31: r < W); the kernel runs the same function
+MCL_HD inline uint32_t reseed_rank(uint64_t t, uint64_t W) {
+  const uint64_t t_hi = t >> 32, t_lo = t & 0xffffffffull;   // W < 2^32: two 64-bit products, no carry lost
+  const uint64_t lo = t_lo * W, hi = t_hi * W + (lo >> 32);  // t W = hi 2^32 + (lo mod 2^32)
+  return (uint32_t)(hi >> 21);
+}
+int reseed_select_impl(const mcl_match_result* res, int64_t M, const mcl_match_config* mcfg, double sigma,
+                       const mcl_reseed_select_config* cfg, mcl_reseed_component* comps_out, int64_t* index_out, int32_t* n_out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (!res || !comps_out || !index_out || !n_out || M < 1 || M > MCL_MATCH_MAX_POSES || reseed_select_why(cfg) || match_config_why(mcfg) ||
+      !(sigma > 0.0) || !std::isfinite(sigma))
+    return MCL_ERR_INVALID;
+  struct Cand {
+    double rms;
+    int64_t i;
+    mcl_match_derived_t d;
+  };
+  std::vector<Cand> cand;
+  for (int64_t i = 0; i < M; ++i) {
+    if (res[i].status != MCL_MATCH_CONVERGED) continue;
+    Cand c;
+    if (match_derived_impl(&res[i].final, mcfg, sigma, &c.d, MCL_SWATH_MAX_BEAMS) != MCL_OK) return MCL_ERR_INVALID;
+    if (!std::isfinite(res[i].x) || !std::isfinite(res[i].y) || !std::isfinite(res[i].yaw)) return MCL_ERR_INVALID;
+    if (c.d.m < cfg->min_beams || !(c.d.rms <= cfg->max_rms)) continue;
+    c.rms = c.d.rms;
+    c.i = i;
+    cand.push_back(c);
+  }
+  std::stable_sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.rms < b.rms; });   // (by index within equal rms)
+  int n = 0;
+  for (const Cand& c : cand) {
+    if (n == cfg->max_components) break;
+    const mcl_match_result& r = res[c.i];
+    bool near = false;
+    for (int k = 0; k < n && !near; ++k) {
+      const double dx = r.x - comps_out[k].mean[0], dy = r.y - comps_out[k].mean[1];
+      const double xx = dx * dx, yy = dy * dy;
+      const double dist = std::sqrt(xx + yy);
+      const double t = r.yaw - comps_out[k].mean[2];
+      near = dist <= cfg->sep_xy && std::fabs(swath_wrap(t)) <= cfg->sep_yaw;
+    }
+    if (near) continue;
+    double cov[6];
+    for (int k = 0; k < 6; ++k) cov[k] = cfg->cov_scale * c.d.cov[k];
+    for (int k = 0; k < 3; ++k) {
+      if (!((c.d.dead >> k) & 1)) continue;
+      for (int j = 0; j < 3; ++j) cov[j >= k ? reg_packed(j, k) : reg_packed(k, j)] = 0.0;
+      const double s = k == 2 ? cfg->dead_std_yaw : cfg->dead_std_xy;
+      cov[reg_packed(k, k)] = s * s;
+    }
+    for (int k = 0; k < 3; ++k) {
+      const double s = k == 2 ? cfg->add_std_yaw : cfg->add_std_xy;
+      const double q = s * s;
+      cov[reg_packed(k, k)] = cov[reg_packed(k, k)] + q;
+    }
+    mcl_reseed_component o;
+    memset(&o, 0, sizeof o);
+    o.mean[0] = r.x;
+    o.mean[1] = r.y;
+    o.mean[2] = r.yaw;
+    int32_t dead;
+    if (regularise_factor_impl(cov, 3, o.chol, &dead) != MCL_OK) return MCL_ERR_INVALID;
+    o.mass = 1;
+    comps_out[n] = o;
+    index_out[n] = c.i;
+    ++n;
+  }
+  *n_out = n;
   return MCL_OK;
 }
 

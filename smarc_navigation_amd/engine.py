@@ -301,6 +301,9 @@ MATCH_STATUS_NAMES = ('CONVERGED', 'MAX_ITER', 'STALLED', 'NO_OVERLAP')
 MATCH_MAX_DUMP = 1 << 26
 SwathOffset = np.dtype(_lib.SWATH_OFFSET_FIELDS)
 SWATH_MAX_PINGS, SWATH_MAX_BEAMS = 64, 16384
+ReseedComponent = np.dtype(_lib.RESEED_COMPONENT_FIELDS)
+RESEED_MAX_COMPONENTS = 256
+RESEED_MAX_STARTS = 65536          # MCL_MATCH_MAX_POSES: what one match call takes
 
 
 def make_match_config(r_max, fit_z=False, max_iter=12, min_beams=8, grad_floor_q=2, step_max_xy=2.0, step_max_yaw=0.1,
@@ -492,6 +495,25 @@ class Engine(object):
         k = C.c_int64(0)
         self._ck(self.lib.mcl_inject_uniform(self.h, float(fraction), C.byref(b), _ptr(u), C.byref(k) if count else None))
         return int(k.value) if count else None
+
+    # ---- sensor resetting (include/mcl_reseed.h)
+    def inject_gaussian(self, fraction, components, normals=None, count=True):
+        """replace the particles whose selection draw is < fraction by draws from the mixture `components` (records of
+        ReseedComponent: mean (x, y, yaw), the packed factor of the covariance, an integer mass; reseed_select makes
+        them from a match); returns the number replaced, or None with count=False (the call then does not wait for the
+        GPU).  normals: n x 5 (u_select, u_comp, xi_0, xi_1, xi_2; REPLAY mode)."""
+        comps = np.ascontiguousarray(components, dtype=ReseedComponent).reshape(-1)
+        u = _f64(normals)
+        k = C.c_int64(0)
+        self._ck(self.lib.mcl_inject_gaussian(self.h, float(fraction), _ptr(comps), comps.size, _ptr(u),
+                                              C.byref(k) if count else None))
+        return int(k.value) if count else None
+
+    def reseed_starts(self, box=None, pitch=4.0, yaw=(-math.pi, math.pi), n_yaw=8, z=0.0, roll=0.0, pitch_angle=0.0):
+        """reseed_starts over `box` (ODOM frame), or with box=None over the map's footprint carried into the odom frame"""
+        if box is None:
+            return reseed_starts(None, pitch, yaw, n_yaw, z, roll, pitch_angle, bounds=self.map_bounds(), m2o=self.m2o)
+        return reseed_starts(box, pitch, yaw, n_yaw, z, roll, pitch_angle)
 
     # ---- dominant modes of the cloud (include/mcl_modes.h)
     def mode_grid(self, cell, n_yaw=36, box=None):
@@ -1499,6 +1521,97 @@ def swath_derived(rec, cfg, sigma):
     r, out = _match_record(rec), np.zeros(1, MATCH_DERIVED)
     _lib.check(_lib.load().mcl_swath_derived(_ptr(r), C.byref(cfg), float(sigma), _ptr(out)))
     return out[0]
+
+
+def make_reseed_select_config(max_components=16, min_beams=32, max_rms=0.5, sep_xy=1.0, sep_yaw=0.1, cov_scale=1.0,
+                              add_std_xy=0.25, add_std_yaw=0.02, dead_std_xy=4.0, dead_std_yaw=0.2):
+    """mcl_reseed_select_config (include/mcl_reseed.h).  The defaults are policy."""
+    c = _lib.ReseedSelectConfig()
+    c.max_components, c.min_beams = int(max_components), int(min_beams)
+    c.max_rms, c.sep_xy, c.sep_yaw, c.cov_scale = float(max_rms), float(sep_xy), float(sep_yaw), float(cov_scale)
+    c.add_std_xy, c.add_std_yaw, c.dead_std_xy, c.dead_std_yaw = (float(add_std_xy), float(add_std_yaw), float(dead_std_xy),
+                                                                  float(dead_std_yaw))
+    return c
+
+
+def reseed_select_check(cfg=None, **config):
+    """None when mcl_reseed_select would accept the config (a ReseedSelectConfig, or the keywords of
+    make_reseed_select_config), else the rule that is broken (host arithmetic)"""
+    c = cfg if cfg is not None else make_reseed_select_config(**config)
+    why = C.c_char_p()
+    rc = _lib.load().mcl_reseed_select_check(C.byref(c), C.byref(why))
+    return None if rc == 0 else (why.value or b'').decode()
+
+
+def reseed_components_check(components):
+    """None when mcl_inject_gaussian would accept the table of components, else the rule that is broken"""
+    comps = None if components is None else np.ascontiguousarray(components, dtype=ReseedComponent).reshape(-1)
+    why = C.c_char_p()
+    rc = _lib.load().mcl_reseed_components_check(_ptr(comps), 0 if comps is None else comps.size, C.byref(why))
+    return None if rc == 0 else (why.value or b'').decode()
+
+
+def reseed_select(match, sigma=None, cfg=None, **config):
+    """mcl_reseed_select (host arithmetic): the mixture of a PingMatch's converged fixes -- (components, a record array of
+    ReseedComponent, lowest rms first; indices, the result each came from).  sigma: the match's own when None.  cfg: a
+    ReseedSelectConfig instead of the keywords of make_reseed_select_config.  No candidate gives two empty arrays."""
+    c = cfg if cfg is not None else make_reseed_select_config(**config)
+    res = np.ascontiguousarray(match.results, dtype=MATCH_RESULT).reshape(-1)
+    room = max(int(c.max_components), 1) if 1 <= int(c.max_components) <= RESEED_MAX_COMPONENTS else 1
+    comps, idx, n = np.zeros(room, ReseedComponent), np.zeros(room, np.int64), C.c_int32(0)
+    _lib.check(_lib.load().mcl_reseed_select(_ptr(res), res.size, C.byref(match.cfg), float(match.sigma if sigma is None else sigma),
+                                             C.byref(c), _ptr(comps), _ptr(idx), C.byref(n)))
+    return comps[:n.value].copy(), idx[:n.value].copy()
+
+
+def footprint_odom(bounds, m2o):
+    """the bounding box, in the odom frame, of the map footprint's four corners carried through the inverse of m2o (the rule
+    of Engine.mode_grid and of mcl_recovery.h; m2o must turn about z alone): (x_min, x_max, y_min, y_max)"""
+    m = np.identity(4) if m2o is None else np.asarray(m2o, np.float64).reshape(4, 4)
+    if (abs(m[0, 2]) > 1e-12 or abs(m[1, 2]) > 1e-12 or abs(m[2, 0]) > 1e-12 or abs(m[2, 1]) > 1e-12 or
+            abs(m[2, 2] - 1.0) > 1e-12):
+        raise MclError(-4, 'the map footprint needs an m2o that turns about z alone')
+    x_min, x_max, y_min, y_max = [float(v) for v in bounds]
+    xs, ys = [], []
+    for x, y in ((x_min, y_min), (x_min, y_max), (x_max, y_min), (x_max, y_max)):
+        dx, dy = x - m[0, 3], y - m[1, 3]
+        xs.append(m[0, 0] * dx + m[1, 0] * dy)
+        ys.append(m[0, 1] * dx + m[1, 1] * dy)
+    return (min(xs), max(xs), min(ys), max(ys))
+
+
+def reseed_starts(box, pitch, yaw=(-math.pi, math.pi), n_yaw=8, z=0.0, roll=0.0, pitch_angle=0.0, bounds=None, m2o=None):
+    """a lattice of start poses for match_ping / match_swath, 6 x M (x, y, z, roll, pitch, yaw): the box (x_min, x_max,
+    y_min, y_max; ODOM frame) cut into nx x ny equal cells no wider than `pitch` (nx = ceil(extent / pitch), at least 1),
+    the yaw interval into n_yaw equal cells, one start at every cell's CENTRE, column (iy nx + ix) n_yaw + k; yaw wrapped
+    into [-pi, pi).  box=None: the map footprint `bounds` (map frame) carried into the odom frame through the inverse of
+    m2o by the rule Engine.mode_grid uses (footprint_odom).  ValueError when M would exceed 65 536, what one match call
+    takes."""
+    if box is None:
+        if bounds is None:
+            raise ValueError('reseed_starts: a box, or the bounds of the map')
+        box = footprint_odom(bounds, m2o)
+    x_min, x_max, y_min, y_max = [float(v) for v in box]
+    pitch, n_yaw = float(pitch), int(n_yaw)
+    y0, y1 = float(yaw[0]), float(yaw[1])
+    if not (pitch > 0.0 and np.isfinite(pitch) and x_max >= x_min and y_max >= y_min and n_yaw >= 1 and y1 >= y0 and
+            np.all(np.isfinite([x_min, x_max, y_min, y_max, y0, y1]))):
+        raise ValueError('reseed_starts: bad pitch, box, yaw interval or n_yaw')
+    nx = max(1, int(math.ceil((x_max - x_min) / pitch)))
+    ny = max(1, int(math.ceil((y_max - y_min) / pitch)))
+    M = nx * ny * n_yaw
+    if M > RESEED_MAX_STARTS:
+        raise ValueError('reseed_starts: %d x %d x %d = %d starts, above the %d one match call takes (a coarser pitch, fewer '
+                         'yaws or a smaller box)' % (nx, ny, n_yaw, M, RESEED_MAX_STARTS))
+    xs = x_min + (np.arange(nx) + 0.5) * ((x_max - x_min) / nx)
+    ys = y_min + (np.arange(ny) + 0.5) * ((y_max - y_min) / ny)
+    ws = y0 + (np.arange(n_yaw) + 0.5) * ((y1 - y0) / n_yaw)
+    ws = np.mod(ws + math.pi, 2.0 * math.pi) - math.pi
+    out = np.zeros((6, M))
+    gy, gx, gw = np.meshgrid(ys, xs, ws, indexing='ij')
+    out[0], out[1], out[5] = gx.reshape(-1), gy.reshape(-1), gw.reshape(-1)
+    out[2], out[3], out[4] = float(z), float(roll), float(pitch_angle)
+    return out
 
 
 def localisability_map(engine, cell, z, yaws, beam_angles, sigma, r_max, sensor_offset=None, roll=0.0, pitch=0.0,

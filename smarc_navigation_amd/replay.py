@@ -608,7 +608,8 @@ def replay_bag(path, params=None, m2o=None, utm2map=None, grid=None, mesh=None, 
 def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=1.0, m2o=None, yaw=(-np.pi, np.pi),
                    process_cov=(0.01, 0.01, 0, 0, 0, 1e-4), resample_cov=(0.04, 0.04, 0, 0, 0, 1e-3), alpha_slow=0.001,
                    alpha_fast=0.1, max_fraction=0.1, inject=True, estimate='mean', mode_cell=1.0, mode_n_yaw=36,
-                   smooth_lag=0, credible=0.0):
+                   smooth_lag=0, credible=0.0, reseed=0, reseed_pitch=4.0, reseed_n_yaw=8, reseed_yaw_window=None,
+                   reseed_select=None):
     """Global localisation with kidnap recovery on a recorded stream (--recover): the cloud starts uniform over the map's
     footprint, and every ping runs the separate calls  predict ... -> update_mbes -> weight_stats -> resample ->
     inject_uniform(fraction)  with the fraction of recovery.AugmentedMCL (the likelihood per valid beam, a short-term
@@ -619,9 +620,19 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
     of the cloud about the published pose (out['credible_radius']); with a truth the summary gains credible_radius_median
     and credible_containment (credible_summary).  Returns dict(pf_xyz[m,3] published pose after every ping,
     pub_idx, fractions[m], injected[m], log_lik_per_beam[m], n_eff[m], summary).  smooth_lag > 0: also out['smooth'], the
-    lag-smooth_lag smoothed track (SmoothTrack), one entry per ping; an injected particle inherits its slot's past."""
+    lag-smooth_lag smoothed track (SmoothTrack), one entry per ping; an injected particle inherits its slot's past.
+    reseed = K > 0: sensor resetting (recovery.SensorResetting, include/mcl_reseed.h) instead of the uniform injection: a
+    ring of the last K pings with the odometry's poses at them (the stream's twist integrated without noise), offsets by
+    swath_offsets, a swath match from a lattice of reseed_pitch metres x reseed_n_yaw yaws (over the full circle, or with
+    reseed_yaw_window W within +-W of the odometry's heading) and the injection at its fixes (reseed_select: the keywords of
+    engine.make_reseed_select_config); the summary gains reseed_calls, reseed_fallbacks, reseed_components_median and,
+    with a truth, first_ping_within_1m_after_kidnap (the first ping from which the published pose stays within 1 m of the
+    truth after it was last farther away; None if it never does).  reseed = 0 is the path and the summary of before."""
     from . import engine as eng
     from . import recovery
+    from .auv_pf import euler_from_quaternion
+    if not 0 <= int(reseed) <= eng.SWATH_MAX_PINGS:
+        raise ValueError('replay_recover: reseed must be 0 ... %d pings' % eng.SWATH_MAX_PINGS)
     if 'mbes_idx' not in stream or (grid is None and mesh is None):
         raise ValueError('replay_recover: needs a stream with MBES pings and a map')
     if estimate not in ('mean', 'mode', 'median'):
@@ -637,6 +648,11 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
     smooth = SmoothTrack(e, smooth_lag) if smooth_lag > 0 else None
     lattice = e.mode_grid(mode_cell, mode_n_yaw) if estimate == 'mode' else None
     aug = recovery.AugmentedMCL(alpha_slow, alpha_fast, max_fraction)
+    resetting, reseed_components = None, []
+    if int(reseed) > 0:
+        resetting = recovery.SensorResetting(aug, eng.make_reseed_select_config(**dict(reseed_select or {})), reseed_pitch,
+                                             reseed_n_yaw, reseed_yaw_window, pings=int(reseed))
+        dr = [0.0] * 6   # the odometry's own pose: of x and y only differences enter, the heading is its quaternion's
     mbes_at = {int(k): j for j, k in enumerate(stream['mbes_idx'])}
     ang = np.asarray(stream['mbes_angles'], dtype=np.float32)
     r_max = float(stream['mbes_range_max']) if 'mbes_range_max' in stream else 100.0
@@ -647,11 +663,21 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
     for k in range(len(stream['stamp'])):
         t = float(stream['stamp'][k])
         e.predict(stream['v'][k], float(stream['wz'][k]), stream['q'][k], float(stream['z'][k]), t - t_prev, stamp=t)
+        if resetting is not None:   # the noise-free motion model (synth.odom_stream's): the twist turned by the sample's attitude
+            dt = t - t_prev
+            roll, pitch, hd = [float(a) for a in euler_from_quaternion(stream['q'][k])]
+            cr, sr, cp, sp, cy, sy = math.cos(roll), math.sin(roll), math.cos(pitch), math.sin(pitch), math.cos(hd), math.sin(hd)
+            vx, vy, vz = [float(c) * dt for c in stream['v'][k]]
+            dr = [dr[0] + cy * cp * vx + (cy * sp * sr - sy * cr) * vy + (cy * sp * cr + sy * sr) * vz,
+                  dr[1] + sy * cp * vx + (sy * sp * sr + cy * cr) * vy + (sy * sp * cr - cy * sr) * vz,
+                  float(stream['z'][k]), float(roll), float(pitch), hd]
         t_prev = t
         if k not in mbes_at:
             continue
         ranges = np.asarray(stream['mbes_ranges'][mbes_at[k]], dtype=np.float32)
         e.update_mbes(ranges, ang, sigma, r_max)
+        if resetting is not None:
+            resetting.push(ranges, dr)
         st = e.weight_stats()
         out['log_lik_per_beam'].append(aug.observe(st, int(np.count_nonzero(ranges > 0))))
         out['n_eff'].append(st.n_eff)
@@ -660,9 +686,14 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
             smooth.record(k, t)
         frac = aug.fraction() if inject else 0.0
         out['fractions'].append(frac)
-        out['injected'].append(e.inject_uniform(frac, yaw=yaw) if frac > 0.0 else 0)
-        if frac > 0.0:
-            aug.injected()
+        if resetting is not None:
+            out['injected'].append(resetting.step(e, ang, sigma, r_max) if frac > 0.0 else 0)
+            if frac > 0.0 and not resetting.last['fallback']:
+                reseed_components.append(resetting.last['components'])
+        else:
+            out['injected'].append(e.inject_uniform(frac, yaw=yaw) if frac > 0.0 else 0)
+            if frac > 0.0:
+                aug.injected()
         pose = e.mean_cov()[0][:3]
         if lattice is not None:
             modes = e.pose_modes(mode_cell, k=1, grid=lattice)[0]
@@ -685,6 +716,14 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
         if 'truth_xyz' in stream:
             ref = np.asarray(stream['truth_xyz'])[out['pub_idx']]
             summary['final_error_vs_truth'] = float(np.linalg.norm(out['pf_xyz'][-1, :2] - ref[-1, :2]))
+    if resetting is not None:
+        summary.update(reseed_calls=resetting.calls, reseed_fallbacks=resetting.fallbacks,
+                       reseed_components_median=float(np.median(reseed_components)) if reseed_components else 0.0)
+        if 'truth_xyz' in stream and len(out['pf_xyz']):
+            err = np.linalg.norm(out['pf_xyz'][:, :2] - np.asarray(stream['truth_xyz'])[out['pub_idx']][:, :2], axis=1)
+            far = np.flatnonzero(err > 1.0)
+            first = 0 if far.size == 0 else int(far[-1]) + 1
+            summary['first_ping_within_1m_after_kidnap'] = first if first < err.size else None
     if credible > 0.0:
         summary.update(credible_summary(credible, out['credible_radius'], out['pf_xyz'],
                                         np.asarray(stream['truth_xyz'])[out['pub_idx']]
@@ -749,6 +788,13 @@ def main(argv=None):
                          'published pose (include/mcl_swath.h); nothing is fed back; the summary gains swath_calls, '
                          'swath_converged_share, swath_rmse_xy (beside the filter\'s own swath_filter_rmse_xy) and '
                          'swath_rms_residual_median -- with --match, match_rmse_xy stands beside them; plain stream replay only')
+    ap.add_argument('--reseed', type=int, default=0, metavar='K',
+                    help='--recover: sensor resetting (include/mcl_reseed.h): inject at the fixes of a swath match of the last K '
+                         'pings started on a lattice over the map, instead of uniformly; the summary gains reseed_calls, '
+                         'reseed_fallbacks, reseed_components_median and first_ping_within_1m_after_kidnap; 0: off')
+    ap.add_argument('--reseed-pitch', type=float, default=4.0, metavar='P', help='--reseed: the lattice\'s spacing in metres')
+    ap.add_argument('--reseed-yaw-window', type=float, default=None, metavar='W',
+                    help='--reseed: start yaws within +-W radians of the odometry\'s heading (a compass) instead of the full circle')
     ap.add_argument('--mbes-every', type=int, default=0, metavar='K',
                     help='synthetic streams: a multibeam ping every K samples over a synthetic map the stream carries')
     ap.add_argument('--outliers', type=float, nargs=2, default=None, metavar=('FRACTION', 'SHORTEN_M'),
@@ -821,6 +867,9 @@ def main(argv=None):
     if a.swath is not None and (len(a.swath) > 2 or a.swath[0] < 1 or a.swath[0] > 64 or (len(a.swath) == 2 and a.swath[1] < 1)
                                 or a.bag or a.recover):
         ap.error('--swath K [EVERY]: 1 <= K <= 64, EVERY >= 1, and only with the plain stream replay')
+    if not 0 <= a.reseed <= 64 or (a.reseed > 0 and not a.recover) or not a.reseed_pitch > 0.0 or (
+            a.reseed_yaw_window is not None and not 0.0 < a.reseed_yaw_window <= np.pi):
+        ap.error('--reseed K: 0 <= K <= 64, only with --recover; --reseed-pitch P > 0; --reseed-yaw-window 0 < W <= pi')
     if a.sigma is not None and not (a.sigma > 0.0 and np.isfinite(a.sigma)):
         ap.error('--sigma must be finite and > 0')
     if (a.mbes_every != 0 or a.outliers is not None) and not synthetic:
@@ -864,7 +913,8 @@ def main(argv=None):
     grid = dict(np.load(a.map_grid)) if a.map_grid else None
     if a.recover:
         res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=1.0 if a.sigma is None else a.sigma, m2o=m2o,
-                             estimate=a.estimate, smooth_lag=a.smooth, credible=a.credible)
+                             estimate=a.estimate, smooth_lag=a.smooth, credible=a.credible, reseed=a.reseed,
+                             reseed_pitch=a.reseed_pitch, reseed_yaw_window=a.reseed_yaw_window)
         if a.out:
             np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz'], res['fractions']]), delimiter=',',
                        header='step,x,y,z,injected_fraction')
