@@ -1,6 +1,6 @@
 """ctypes loader for libmcl_hip.so (the C ABI in include/mcl.h, mcl_dr.h, mcl_map.h, mcl_recovery.h, mcl_modes.h,
 mcl_history.h, mcl_acoustic.h, mcl_temper.h, mcl_drift.h, mcl_regularise.h, mcl_quantile.h, mcl_innovation.h,
-mcl_information.h, mcl_match.h, mcl_swath.h and mcl_reseed.h).
+mcl_information.h, mcl_match.h, mcl_swath.h, mcl_reseed.h and mcl_kld.h).
 
 Fails loudly when the shared library is missing: there is no Python/CPU fallback for the hot
 path.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -390,6 +390,15 @@ RESEED_SYMBOLS = {
     'mcl_inject_gaussian': (C.c_int, [_vp, _d, _vp, _i32, _vp, C.POINTER(C.c_int64)]),
 }
 
+# include/mcl_kld.h: KLD-sampling across handles (occupied cells, the bound, the resample from one handle into another)
+KLD_SYMBOLS = {
+    'mcl_kld_grid_check': (C.c_int, [C.POINTER(ModeGrid), C.POINTER(C.c_int64)]),
+    'mcl_kld_bins': (C.c_int, [_vp, C.POINTER(ModeGrid), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'mcl_kld_bound': (C.c_int, [_i64, _d, _d, _i64, _i64, C.POINTER(C.c_int64)]),
+    'mcl_resample_into': (C.c_int, [_vp, _vp, _vp]),
+    'mcl_transfer_last_indices': (C.c_int, [_vp, _vp]),
+}
+
 _lib = None
 
 
@@ -407,7 +416,8 @@ def load():
                               list(TEMPER_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()) +
                               list(REGULARISE_SYMBOLS.items()) + list(QUANTILE_SYMBOLS.items()) +
                               list(INNOVATION_SYMBOLS.items()) + list(INFORMATION_SYMBOLS.items()) +
-                              list(MATCH_SYMBOLS.items()) + list(SWATH_SYMBOLS.items()) + list(RESEED_SYMBOLS.items())):
+                              list(MATCH_SYMBOLS.items()) + list(SWATH_SYMBOLS.items()) + list(RESEED_SYMBOLS.items()) +
+                              list(KLD_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

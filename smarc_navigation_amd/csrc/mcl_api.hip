@@ -22,6 +22,7 @@
 #include "mcl_host_recovery.h"
 #include "mcl_host_reseed.h"
 #include "mcl_host_modes.h"
+#include "mcl_host_kld.h"
 
 // dead-reckoning integrator (host only; uses euler_from_quat above)
 #include "mcl_dr_impl.h"
@@ -1486,6 +1487,45 @@ int mcl_inject_gaussian(mcl_handle* h, double fraction, const mcl_reseed_compone
   if (h->have_lw) return fail(h, MCL_ERR_STATE, "inject_gaussian: log-weights pending (resample first: they describe the particles as they are)");
   RET_IF(set_device(h));
   return reseed_inject(h, fraction, comps, n_comp, replay, n_injected);
+}
+
+// ---- KLD-sampling across handles (include/mcl_kld.h; host: mcl_host_kld.h, kernels: csrc/mcl_kld.h)
+int mcl_kld_grid_check(const mcl_mode_grid* g, int64_t* n_cells) { return kld_grid_check_impl(g, n_cells, nullptr); }
+
+int mcl_kld_bound(int64_t k, double epsilon, double z, int64_t n_min, int64_t n_max, int64_t* n) {
+  return kld_bound_impl(k, epsilon, z, n_min, n_max, n);
+}
+
+int mcl_kld_bins(mcl_handle* h, const mcl_mode_grid* g, int64_t* k, int64_t* n_inside, int64_t* n_outside) {
+  if (!h) return MCL_ERR_INVALID;
+  if (!g) return fail(h, MCL_ERR_INVALID, "kld_bins: null grid");
+  int64_t n_cells = 0;
+  const char* reason = nullptr;
+  if (kld_grid_check_impl(g, &n_cells, &reason) != MCL_OK) return fail(h, MCL_ERR_INVALID, std::string("kld_bins: ") + reason);
+  if (h->world > 1) return fail(h, MCL_ERR_UNSUPPORTED, "kld_bins: a sharded cloud (world > 1) is not supported");
+  if (!h->have_state) return fail(h, MCL_ERR_STATE, "kld_bins: no particles (call mcl_init_particles / mcl_set_particles first)");
+  RET_IF(set_device(h));
+  return kld_bins_run(h, g, n_cells, k, n_inside, n_outside);
+}
+
+int mcl_resample_into(mcl_handle* src, mcl_handle* dst, const double* uniform) {
+  if (!src || !dst) return MCL_ERR_INVALID;
+  if (src == dst) return fail(dst, MCL_ERR_INVALID, "resample_into: src and dst are the same handle");
+  uint64_t u53 = 0;
+  if (!kld_transfer_u53(uniform, dst->cfg.seed, dst->step_transfer, &u53)) return fail(dst, MCL_ERR_INVALID, "resample_into: u not in [0,1)");
+  int code = MCL_OK;
+  if (const char* why = transfer_refused(src, dst, &code)) return fail(dst, code, why);
+  RET_IF(set_device(dst));
+  return transfer_run(src, dst, u53);
+}
+
+int mcl_transfer_last_indices(mcl_handle* dst, int32_t* idx) {
+  if (!dst || !idx) return MCL_ERR_INVALID;
+  if (!dst->have_transfer) return fail(dst, MCL_ERR_STATE, "transfer_last_indices: no transfer into this handle yet");
+  RET_IF(set_device(dst));
+  HIPCHK(dst, hipMemcpyAsync(idx, dst->xfer_idx, sizeof(int) * (size_t)dst->n, hipMemcpyDeviceToHost, dst->stream));
+  HIPCHK(dst, hipStreamSynchronize(dst->stream));
+  return MCL_OK;
 }
 
 int mcl_timing_enable(mcl_handle* h, int32_t on) {

@@ -3,7 +3,7 @@
 // One translation unit: mcl_api.hip includes mcl_host.h, mcl_host_resample.h, mcl_host_moments.h, mcl_host_update.h,
 // mcl_host_landmarks.h, mcl_host_ranges.h, mcl_host_step.h, mcl_host_history.h, mcl_host_acoustic.h, mcl_host_temper.h,
 // mcl_host_drift.h, mcl_host_regularise.h, mcl_host_quantile.h, mcl_host_innovation.h (with the pipeline of the two ping
-// statistics), mcl_host_information.h (which includes it), mcl_host_recovery.h, mcl_host_modes.h
+// statistics), mcl_host_information.h (which includes it), mcl_host_recovery.h, mcl_host_modes.h, mcl_host_kld.h
 // in this order and then defines the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -224,6 +224,16 @@ struct mcl_handle {
   DevBuf<u64> modes_rec;       // per-workgroup records: MCL_MAX_GRID outside counts, then MCL_MAX_GRID selection keys
   DevBuf<double> modes_part;   // per-workgroup moment sums [k][MODES_SUMS][grid]
   DevBuf<double> modes_res;    // MODES_RES_WORDS: the summed moments, the peaks, the outside count
+  // KLD-sampling across handles (include/mcl_kld.h; all lazily)
+  DevBuf<u32> kld_bits;        // mcl_kld_bins: one bit per cell of the caller's lattice; all zero between calls
+  bool kld_dirty = false;      // ... unless a call ended between its mark and its count: the next one clears the bitmap
+  DevBuf<u64> kld_rec;         // per-workgroup records: MCL_MAX_GRID outside counts, MCL_MAX_GRID cell counts, then the two sums
+  uint32_t step_transfer = 0;  // mcl_resample_into with this handle as dst: successful calls so far, the Philox step of the next one
+  bool have_transfer = false;  // xfer_idx holds the ancestors of a transfer
+  DevBuf<u64> xfer_q;          // the transfer's scratch, sized by SRC: fixed-point weights (n_src)
+  DevBuf<u64> xfer_tile;       // ... tile sums, the total, MCL_MAX_SLOTS max-lw slots
+  DevBuf<u32> xfer_ncum;       // ... offspring CDF for this handle's n positions (n_src)
+  DevBuf<int> xfer_idx;        // n: the ancestors of the last transfer
   // particle genealogy (include/mcl_history.h; all allocated by mcl_history_enable, freed by mcl_history_disable)
   bool hist_on = false;
   int hist_depth = 0, hist_held = 0, hist_head = -1;   // ring: frames held, index of the newest (-1: none)
@@ -507,7 +517,7 @@ void history_clear(mcl_handle* h);
 int drift_after_resample(mcl_handle* h, bool alt);
 // The filter starts again from fresh particles (both init calls): the Philox steps count from 0, no weights, no CDF.
 void filter_restarted(mcl_handle* h) {
-  h->step_predict = h->step_resample = h->step_inject = 0;
+  h->step_predict = h->step_resample = h->step_inject = h->step_transfer = 0;
   h->have_lw = h->have_cdf = false;
 }
 

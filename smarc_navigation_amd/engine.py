@@ -550,6 +550,31 @@ class Engine(object):
         self._ck(self.lib.mcl_pose_modes(self.h, C.byref(g), k, out, C.byref(nm), C.byref(no)))
         return [PoseMode(out[j]) for j in range(nm.value)], int(no.value)
 
+    # ---- KLD-sampling across handles (include/mcl_kld.h)
+    def kld_grid(self, cell, n_yaw=36, box=None):
+        """the lattice of kld_bins: the box rule of mode_grid; the limits are those of kld_grid_check (2^27 cells)"""
+        return self.mode_grid(cell, n_yaw, box)
+
+    def kld_bins(self, cell=None, n_yaw=36, box=None, grid=None):
+        """(k, n_outside): the number of cells of a lattice of `cell` metres and n_yaw yaw bins that hold at least one
+        particle, and the particles that belong to no cell (mcl_kld_bins).  box, grid: as in pose_modes."""
+        g = grid if grid is not None else self.kld_grid(cell, n_yaw, box)
+        k, ni, no = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.mcl_kld_bins(self.h, C.byref(g), C.byref(k), C.byref(ni), C.byref(no)))
+        return int(k.value), int(no.value)
+
+    def resample_into(self, dst, uniform=None):
+        """dst's particles := dst.n systematic draws from this handle's weighted cloud, without noise (mcl_resample_into);
+        this handle is left as it was.  uniform: one number in [0, 1), or None: dst's own Philox draw."""
+        u = None if uniform is None else _f64(np.atleast_1d(uniform))
+        _lib.check(self.lib.mcl_resample_into(self.h, dst.h, _ptr(u)), dst.h)
+
+    def transfer_indices(self):
+        """the ancestors (slots of the source) of the last resample_into with this handle as dst"""
+        idx = np.zeros(self.n, np.int32)
+        self._ck(self.lib.mcl_transfer_last_indices(self.h, _ptr(idx)))
+        return idx
+
     # ---- exact order statistics of the cloud (include/mcl_quantile.h)
     def cloud_quantiles(self, quantity, probs, centre=None, weighted=False):
         """the quantiles of a quantity ('x', 'y', 'yaw_dev', 'abs_yaw_dev', 'radius2', or MCL_Q_*) about centre =
@@ -1562,6 +1587,26 @@ def reseed_select(match, sigma=None, cfg=None, **config):
     _lib.check(_lib.load().mcl_reseed_select(_ptr(res), res.size, C.byref(match.cfg), float(match.sigma if sigma is None else sigma),
                                              C.byref(c), _ptr(comps), _ptr(idx), C.byref(n)))
     return comps[:n.value].copy(), idx[:n.value].copy()
+
+
+KLD_Z_99 = 2.3263478740408408     # the upper 0.99 quantile of the standard normal (delta = 0.01)
+KLD_MAX_CELLS = 1 << 27
+KLD_MAX_YAW = 1024
+
+
+def kld_bound(k, epsilon=0.05, z=KLD_Z_99, n_min=1, n_max=2 ** 31):
+    """mcl_kld_bound (host arithmetic): the particle count Fox's bound asks for when k cells are occupied, the KL error
+    of the sampled posterior staying below epsilon with probability 1 - delta (z: the normal's upper 1 - delta quantile)"""
+    n = C.c_int64(0)
+    _lib.check(_lib.load().mcl_kld_bound(int(k), float(epsilon), float(z), int(n_min), int(n_max), C.byref(n)))
+    return int(n.value)
+
+
+def kld_grid_check(grid):
+    """the cell count of the lattice when mcl_kld_bins would accept it (up to 2^27 cells, n_yaw up to 1024), else None"""
+    n = C.c_int64(0)
+    rc = _lib.load().mcl_kld_grid_check(C.byref(grid) if grid is not None else None, C.byref(n))
+    return int(n.value) if rc == 0 else None
 
 
 def footprint_odom(bounds, m2o):

@@ -609,7 +609,7 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
                    process_cov=(0.01, 0.01, 0, 0, 0, 1e-4), resample_cov=(0.04, 0.04, 0, 0, 0, 1e-3), alpha_slow=0.001,
                    alpha_fast=0.1, max_fraction=0.1, inject=True, estimate='mean', mode_cell=1.0, mode_n_yaw=36,
                    smooth_lag=0, credible=0.0, reseed=0, reseed_pitch=4.0, reseed_n_yaw=8, reseed_yaw_window=None,
-                   reseed_select=None):
+                   reseed_select=None, kld=0.0, kld_sizes=None, kld_cell=0.5, kld_n_yaw=36):
     """Global localisation with kidnap recovery on a recorded stream (--recover): the cloud starts uniform over the map's
     footprint, and every ping runs the separate calls  predict ... -> update_mbes -> weight_stats -> resample ->
     inject_uniform(fraction)  with the fraction of recovery.AugmentedMCL (the likelihood per valid beam, a short-term
@@ -627,7 +627,14 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
     reseed_yaw_window W within +-W of the odometry's heading) and the injection at its fixes (reseed_select: the keywords of
     engine.make_reseed_select_config); the summary gains reseed_calls, reseed_fallbacks, reseed_components_median and,
     with a truth, first_ping_within_1m_after_kidnap (the first ping from which the published pose stays within 1 m of the
-    truth after it was last farther away; None if it never does).  reseed = 0 is the path and the summary of before."""
+    truth after it was last farther away; None if it never does).  reseed = 0 is the path and the summary of before.
+    kld = EPS > 0: KLD-sampling across handles (adaptive.AdaptiveCloud, include/mcl_kld.h) with the KL error EPS: one engine
+    per size of kld_sizes (default: particles, particles / 8, / 64, / 512, down to 256), each with its own copy of the map;
+    the cloud starts on the largest, every resample counts the occupied cells of a lattice of kld_cell metres x kld_n_yaw
+    bins and moves the cloud to the size adaptive.KldLadder asks for, and a positive injection fraction takes it back to
+    the largest first.  The summary gains kld_sizes_used, kld_final_size and kld_moves, out['kld_trace'] the (ping, k,
+    bound, size) rows.  kld = 0 is the path and the summary of before."""
+    from . import adaptive
     from . import engine as eng
     from . import recovery
     from .auv_pf import euler_from_quaternion
@@ -639,7 +646,20 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
         raise ValueError("replay_recover: estimate must be 'mean', 'mode' or 'median'")
     if not 0.0 <= credible <= 1.0:
         raise ValueError('replay_recover: credible must lie in [0, 1]')
-    e = eng.Engine(int(particles), process_cov=process_cov, resample_cov=resample_cov, m2o=m2o, seed=seed)
+    if not (0.0 <= float(kld) and math.isfinite(float(kld))):
+        raise ValueError('replay_recover: kld must be a finite KL error >= 0')
+    cloud = None
+    if float(kld) > 0.0:
+        if smooth_lag > 0:
+            raise ValueError('replay_recover: the genealogy of --smooth lives in one handle; not with kld')
+        sizes = sorted(set(int(s) for s in kld_sizes)) if kld_sizes else sorted(
+            set(max(int(particles) >> sh, min(256, int(particles))) for sh in (0, 3, 6, 9)))
+        if not sizes or sizes[0] < 1:
+            raise ValueError('replay_recover: kld_sizes must be positive')
+        engines = [eng.Engine(s, process_cov=process_cov, resample_cov=resample_cov, m2o=m2o, seed=seed) for s in sizes]
+        e = cloud = adaptive.AdaptiveCloud(engines, adaptive.KldLadder(sizes, float(kld)), kld_cell, kld_n_yaw)
+    else:
+        e = eng.Engine(int(particles), process_cov=process_cov, resample_cov=resample_cov, m2o=m2o, seed=seed)
     if grid is not None:
         e.set_map_grid(grid['z'], grid['origin'], float(grid['res']))
     else:
@@ -686,6 +706,8 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
             smooth.record(k, t)
         frac = aug.fraction() if inject else 0.0
         out['fractions'].append(frac)
+        if cloud is not None and frac > 0.0:
+            cloud.to_top()
         if resetting is not None:
             out['injected'].append(resetting.step(e, ang, sigma, r_max) if frac > 0.0 else 0)
             if frac > 0.0 and not resetting.last['fallback']:
@@ -708,6 +730,8 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
         out['pub_idx'].append(k)
     track = smooth.finish() if smooth is not None else None
     e.close()
+    if cloud is not None:
+        out['kld_trace'] = list(cloud.trace)
     for name in out:
         out[name] = np.array(out[name])
     summary = dict(pings=len(out['pub_idx']), injected_total=int(out['injected'].sum()) if len(out['injected']) else 0)
@@ -724,6 +748,10 @@ def replay_recover(stream, grid=None, mesh=None, particles=65536, seed=0, sigma=
             far = np.flatnonzero(err > 1.0)
             first = 0 if far.size == 0 else int(far[-1]) + 1
             summary['first_ping_within_1m_after_kidnap'] = first if first < err.size else None
+    if cloud is not None:
+        summary.update(kld_sizes_used=sorted(set(int(r[3]) for r in cloud.trace)),
+                       kld_final_size=int(cloud.trace[-1][3]) if cloud.trace else int(cloud.ladder.sizes[-1]),
+                       kld_moves=int(cloud.moves))
     if credible > 0.0:
         summary.update(credible_summary(credible, out['credible_radius'], out['pf_xyz'],
                                         np.asarray(stream['truth_xyz'])[out['pub_idx']]
@@ -795,6 +823,13 @@ def main(argv=None):
     ap.add_argument('--reseed-pitch', type=float, default=4.0, metavar='P', help='--reseed: the lattice\'s spacing in metres')
     ap.add_argument('--reseed-yaw-window', type=float, default=None, metavar='W',
                     help='--reseed: start yaws within +-W radians of the odometry\'s heading (a compass) instead of the full circle')
+    ap.add_argument('--kld', type=float, default=0.0, metavar='EPS',
+                    help='--recover: KLD-sampling across handles (include/mcl_kld.h) with the KL error EPS: the cloud moves '
+                         'between engines of the sizes of --kld-sizes as the occupied cells of its lattice ask')
+    ap.add_argument('--kld-sizes', type=int, nargs='+', default=None, metavar='N',
+                    help='--kld: the particle counts of the ladder (default: --particles and its 8th, 64th, 512th)')
+    ap.add_argument('--kld-cell', type=float, default=0.5, metavar='C', help='--kld: the cell of the lattice in metres')
+    ap.add_argument('--kld-n-yaw', type=int, default=36, metavar='Y', help='--kld: the yaw bins of the lattice')
     ap.add_argument('--mbes-every', type=int, default=0, metavar='K',
                     help='synthetic streams: a multibeam ping every K samples over a synthetic map the stream carries')
     ap.add_argument('--outliers', type=float, nargs=2, default=None, metavar=('FRACTION', 'SHORTEN_M'),
@@ -870,6 +905,11 @@ def main(argv=None):
     if not 0 <= a.reseed <= 64 or (a.reseed > 0 and not a.recover) or not a.reseed_pitch > 0.0 or (
             a.reseed_yaw_window is not None and not 0.0 < a.reseed_yaw_window <= np.pi):
         ap.error('--reseed K: 0 <= K <= 64, only with --recover; --reseed-pitch P > 0; --reseed-yaw-window 0 < W <= pi')
+    kld_given = a.kld != 0.0 or a.kld_sizes is not None
+    if (kld_given and not a.recover) or not (a.kld >= 0.0 and np.isfinite(a.kld)) or (a.kld_sizes is not None and (
+            a.kld == 0.0 or min(a.kld_sizes) < 1)) or not a.kld_cell > 0.0 or not 1 <= a.kld_n_yaw <= 1024 or (a.kld > 0 and a.smooth > 0):
+        ap.error('--kld EPS > 0, only with --recover and without --smooth; --kld-sizes N >= 1 with --kld; --kld-cell C > 0; '
+                 '--kld-n-yaw 1 ... 1024')
     if a.sigma is not None and not (a.sigma > 0.0 and np.isfinite(a.sigma)):
         ap.error('--sigma must be finite and > 0')
     if (a.mbes_every != 0 or a.outliers is not None) and not synthetic:
@@ -914,7 +954,8 @@ def main(argv=None):
     if a.recover:
         res = replay_recover(stream, grid=grid, particles=a.particles, seed=a.seed, sigma=1.0 if a.sigma is None else a.sigma, m2o=m2o,
                              estimate=a.estimate, smooth_lag=a.smooth, credible=a.credible, reseed=a.reseed,
-                             reseed_pitch=a.reseed_pitch, reseed_yaw_window=a.reseed_yaw_window)
+                             reseed_pitch=a.reseed_pitch, reseed_yaw_window=a.reseed_yaw_window, kld=a.kld,
+                             kld_sizes=a.kld_sizes, kld_cell=a.kld_cell, kld_n_yaw=a.kld_n_yaw)
         if a.out:
             np.savetxt(a.out, np.column_stack([res['pub_idx'], res['pf_xyz'], res['fractions']]), delimiter=',',
                        header='step,x,y,z,injected_fraction')
